@@ -12,9 +12,14 @@ every rank renders the chunks of its own band of image rows (``--scaling weak``,
 step; ``--scaling strong``: the 4096-ray step is split over the ranks) and the finished band is all-gathered ONCE PER
 FRAME over RCCL (what distributed.render_frame does).
 
-The LAST stdout line of rank 0 is the bounded contract line (<= 4096 bytes, strict JSON: the task statement's fields with `roofline`
-and `cpu_baseline`, plus scalars of the training legs and, at N > 1, what the process group was -- `rccl`); the FULL record (every leg,
-per-kernel tables, notes) goes to bench_full.json beside this file and, as one prefixed line, to stderr.  Modules: bench_common.py
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the last timed step's outputs
+(``--dump-outputs DIR``: DIR/rgb.npy, ins.npy, depth.npy of the chunk, float32) and print the line.  ``--full`` adds everything else
+described below: the check of the last chunk against dm_nerf, the CPU baselines, the training legs, at N > 1 the process-group
+evidence, and the full record.
+
+The LAST stdout line of rank 0 is the bounded contract line (<= 4096 bytes, strict JSON: the task statement's fields with `roofline`,
+and with --full `cpu_baseline`, scalars of the training legs and, at N > 1, what the process group was -- `rccl`); with --full the FULL
+record (every leg, per-kernel tables, notes) goes to bench_full.json beside this file and, as one prefixed line, to stderr.  Modules: bench_common.py
 (constants, MAC counts, peaks), bench_train.py (training legs), bench_extras.py (the `--extras` legs).  Secondary objects
 (never part of `value`): `frame` (one complete 640x480 pose through the frame driver), `train` (one optimisation step,
 its own per-kernel roofline and CPU baseline), `train_loop` (the shipped N_train = 3072 loop incl. batch selection),
@@ -54,22 +59,34 @@ def parse():
     p.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                    help="N > 1: weak = 4096 rays per rank and step; strong = one 4096-ray step (train: one 4096-ray batch, the "
                         "reference's batch semantics train_dmsr.py:24-31) split over the ranks")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-train", action="store_true", help="skip the training-step measurements")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline: the check of the last chunk against dm_nerf, the CPU baselines, the "
+                        "training legs, at N > 1 the process-group evidence, and the full record (bench_full.json).  Off: set up, warm "
+                        "up, time the steps, dump the outputs (--dump-outputs) and print the result line -- nothing else")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (rgb, ins, depth of the chunk) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="the --full run without the CPU baselines (implies --full)")
+    p.add_argument("--no-train", action="store_true", help="the --full run without the training-step measurements (implies --full)")
     p.add_argument("--extras", action="store_true",
                    help="also run the secondary legs (frame driver, opt-in fused-heads / split-MFMA modes, ins-59, manipulator, "
-                        "manipulation frame, graph replay): minutes of extra wall time, bench_full.json only -- never the contract line")
+                        "manipulation frame, graph replay): minutes of extra wall time, bench_full.json only -- never the contract line; "
+                        "implies --full")
     p.add_argument("--no-extras", action="store_true", help="(accepted for older command lines: extras are off unless --extras)")
     p.add_argument("--train-steps", type=int, default=5)
     p.add_argument("--cpu-seconds", type=float, default=22.0,
                    help="budget of the CPU baseline per leg: BASELINE.md section 4 asks for N=4096 render / N=1024 train, median "
                         "of 3 after a warm-up (--cpu-seconds 80 does that); the default keeps the sample and runs as many repetitions "
-                        "as fit -- one, on the GPU box's host -- so that the default bench stays near a minute; on a slow host the sample shrinks")
+                        "as fit -- one, on an MI355X node's host -- so that the --full bench stays near a minute; on a slow host the sample shrinks")
     p.add_argument("--full-record", default=os.path.join(ROOT, "bench_full.json"),
-                   help="where rank 0 writes the FULL record (every leg, per-kernel tables, notes); the stdout line is the bounded contract line")
+                   help="(--full) where rank 0 writes the FULL record (every leg, per-kernel tables, notes); the stdout line is the bounded "
+                        "contract line")
     p.add_argument("--ins-num", type=int, default=C.INS_NUM,
                    help="object-code width: 13 = DM-SR 'study' (the headline config); 59 / 93 = Replica office_0 / room_0 (BASELINE config 2)")
-    return p.parse_args()
+    a = p.parse_args()
+    a.full = a.full or a.extras or a.no_cpu_baseline or a.no_train          # (options of the --full run imply it)
+    if a.dump_outputs is not None and a.steps < 1:
+        p.error("--dump-outputs needs --steps >= 1 (it writes what the last timed step computed)")
+    return a
 
 
 def cpu_train_baseline(mc, mf, rays_cpu, z_cpu, seconds):
@@ -175,6 +192,8 @@ def self_launch(a):
     env.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or a.gpus) // a.gpus)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if a.dump_outputs is not None:                              # (the ranks run in ROOT: a relative DIR means the caller's directory)
+        cmd += ["--dump-outputs", os.path.abspath(a.dump_outputs)]
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, env=env, cwd=ROOT)
     line = None
     for out in p.stdout:                                        # relay as it comes: a hung rank must not hide what was printed before
@@ -274,10 +293,10 @@ def headline_leg(a, w, sc):
 
     def step(i, events=None):
         c = i % n_chunks
-        rgb, ins, depth = fr.step(c, events=events)
+        out = fr.step(c, events=events)                         # (rgb, ins, depth) of the chunk
         if w.world > 1 and c == n_chunks - 1:                   # the band is complete: one all-gather per frame
             gather_frame()
-        return rgb, ins
+        return out
 
     def barrier():
         if w.world > 1:
@@ -285,7 +304,7 @@ def headline_leg(a, w, sc):
         torch.cuda.synchronize()
 
     C.quiesce()
-    out_rgb = None
+    out = None
     with torch.no_grad():
         for i in range(a.warmup):
             step(i, ev_scratch)
@@ -294,7 +313,7 @@ def headline_leg(a, w, sc):
         host_t = []
         t0 = time.perf_counter()
         for i in range(a.steps):
-            out_rgb, _ = step(i, ev[i])
+            out = step(i, ev[i])
             host_t.append(time.perf_counter())
         if w.world > 1 and a.steps > 0 and gathers[0] == 0:
             gather_frame()                                      # fewer steps than a band has chunks: the frame's gather is still timed
@@ -309,7 +328,27 @@ def headline_leg(a, w, sc):
         cnt = torch.tensor([rays_rank], device=w.dev, dtype=torch.float64)
         dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
         rays_total = int(cnt.item())
-    return types.SimpleNamespace(dt=dt, rays_rank=rays_rank, rays_total=rays_total, ev=ev, gathers=gathers[0], host_t=host_t, t0=t0, out_rgb=out_rgb)
+    return types.SimpleNamespace(dt=dt, rays_rank=rays_rank, rays_total=rays_total, ev=ev, gathers=gathers[0], host_t=host_t, t0=t0,
+                                 out_rgb=None if out is None else out[0], out=out)
+
+
+DUMP_LIMIT = 64 << 20           # bytes: --dump-outputs writes at most this much in all
+DUMP_NAMES = ("rgb", "ins", "depth")
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor, what the last timed step returned) as ``path/<name>.npy``, float32 (float64 stays
+    float64), copied off the GPU after the timed region.  Returns {name: shape}."""
+    host = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy()
+        host[name] = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+    total = sum(x.nbytes for x in host.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes (limit {DUMP_LIMIT})"
+    os.makedirs(path, exist_ok=True)
+    for name, x in host.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+    return {name: list(x.shape) for name, x in host.items()}
 
 
 def device_identity(dev):
@@ -622,11 +661,14 @@ def main():
     C.HAVE_F16X2 = "dmnerf_mlp_fwd_rays_f16" in _lib.SIGNATURES
     sc = build_scene(w)
     h = headline_leg(a, w, sc)
-    rccl = rccl_evidence(w, sc, h) if w.world > 1 else None
-    train_multi, mani_multi = multi_rank_legs(a, w, sc)
+    if a.dump_outputs is not None and w.rank == 0:
+        dump_outputs(a.dump_outputs, dict(zip(DUMP_NAMES, h.out)))
+    # everything past the headline -- checks, CPU baselines, training legs, process-group evidence, full record -- is --full only
+    rccl = rccl_evidence(w, sc, h) if (a.full and w.world > 1) else None
+    train_multi, mani_multi = multi_rank_legs(a, w, sc) if a.full else (None, None)
     if w.rank == 0:
         res = headline_record(a, w, sc, h, rccl)
-        if w.world == 1:
+        if a.full and w.world == 1:
             wide = single_gpu_render_legs(a, w, sc, h, res)
             if not a.no_train:
                 single_gpu_train_legs(a, w, sc, res, wide)
@@ -641,7 +683,7 @@ def main():
         dist.barrier()                                          # nobody is still printing
     C.flush_c_stdio()
     if w.rank == 0:
-        path = write_full_record(res, a.full_record)
+        path = write_full_record(res, a.full_record) if a.full else None
         rel = None if path is None else (os.path.relpath(path, ROOT) if path.startswith(ROOT) else path)
         print(contract_line(res, rel), flush=True)               # the LAST stdout line: the contract, <= 4096 bytes, strict JSON
     if w.world > 1:

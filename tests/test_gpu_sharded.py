@@ -133,7 +133,7 @@ def _run_bench(world, steps, scaling, train_steps=1, timeout=800, tmp=None):
     # the driver's command line (task statement), with the two environment switches that put every rank on the box's one GPU
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", "1",
-           "--train-steps", str(train_steps), "--scaling", scaling, "--full-record", os.path.join(str(tmp), "bench_full.json")]
+           "--train-steps", str(train_steps), "--scaling", scaling, "--full", "--full-record", os.path.join(str(tmp), "bench_full.json")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     return _strict_line(p.stdout, only_line=False)
@@ -148,7 +148,7 @@ def _run_bench_plain(world, steps, timeout=800, tmp=None):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DMNERF_BENCH_ONE_DEVICE="1", DMNERF_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", "1", "--train-steps", "1",
-           "--full-record", os.path.join(str(tmp), "bench_full.json")]
+           "--full", "--full-record", os.path.join(str(tmp), "bench_full.json")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     return _strict_line(p.stdout)
