@@ -408,6 +408,8 @@ extern "C" int dmnerf_mlp_chain(const float* d_x, int64_t ldx, int64_t x_floats,
         return dmn_fail(DMNERF_E_ARG, "mlp_chain: rows must be 16-byte aligned (ldx=%lld ldo=%lld)", (long long)ldx, (long long)ldo);
     if (ldx * 4 * 128 > 0x3fffffffLL || ldo * 4 * 128 > 0x3fffffffLL) return dmn_fail(DMNERF_E_ARG, "mlp_chain: row stride too large");
     const int nbb = width / 32, nx = (x_cols + 31) / 32;
+    if (ldx < 32 * nx)          // X is fetched in 32-column chunks from every row start: a shorter row would read into the next one
+        return dmn_fail(DMNERF_E_ARG, "mlp_chain: x rows shorter than the 32-column chunks the kernel reads (ldx=%lld x_cols=%d)", (long long)ldx, x_cols);
     ChainArgs a{};
     a.X = d_x; a.ldx = ldx; a.x_floats = x_floats; a.nx = nx; a.out = d_out; a.ldo = ldo; a.M = M; a.n_layers = n_layers;
     a.last_aux_layer = -1; a.total_chunks = 0;

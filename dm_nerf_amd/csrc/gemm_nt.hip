@@ -554,6 +554,10 @@ extern "C" int dmnerf_gemm_nt(const float* d_A0, int64_t lda0, int64_t a0_floats
         return dmn_fail(DMNERF_E_ARG, "gemm_nt: operand rows must be 16-byte aligned (lda0=%lld lda1=%lld)", (long long)lda0, (long long)lda1);
     if (n_zero > ldc) return dmn_fail(DMNERF_E_ARG, "gemm_nt: n_zero=%d beyond the row length %lld", n_zero, (long long)ldc);
     const int nc0 = (k0 + 31) / 32, nc1 = (k1 + 31) / 32;
+    // the A operands are fetched in 32-column chunks from every row start: a shorter row would have its last chunk read the next row
+    if (lda0 < 32 * nc0 || (k1 > 0 && lda1 < 32 * nc1))
+        return dmn_fail(DMNERF_E_ARG, "gemm_nt: A rows shorter than the 32-column chunks the kernel reads (lda0=%lld k0=%d lda1=%lld k1=%d)",
+                        (long long)lda0, k0, (long long)lda1, k1);
     if (ldb != 32 * (nc0 + nc1)) return dmn_fail(DMNERF_E_ARG, "gemm_nt: ldb=%d does not match the K ranges", ldb);
     if (lda0 * 4 * 128 > 0x3fffffffLL || lda1 * 4 * 128 > 0x3fffffffLL || ldc * 4 * 128 > 0x3fffffffLL || ldm * 4 * 128 > 0x3fffffffLL)
         return dmn_fail(DMNERF_E_ARG, "gemm_nt: row stride too large for 32-bit tile offsets");

@@ -38,13 +38,16 @@ def _splits(I, J, K):
 
 
 def _ld(cols):
-    """Row length of an activation matrix with ``cols`` columns: rows stay 16-byte aligned (the LDS-DMA fetches 16 bytes per lane)."""
-    return (cols + 3) // 4 * 4
+    """Row length of an activation matrix with ``cols`` columns: a multiple of 32 floats.  gemm_nt and the chained trunk fetch an A
+    operand in 32-column (128-byte) chunks from each row start, so a shorter row would have its last chunk read the first columns of
+    the NEXT row -- products with zero weights, but 0 * NaN = NaN: one sample's non-finite input would reach its neighbour's output
+    (include/dmnerf_hip.h states the contract; the entry points refuse a shorter row)."""
+    return (cols + 31) // 32 * 32
 
 
 class _Act:
-    """An activation matrix [M, ld] with ``cols`` logical columns; the pad columns [cols, ld) hold zeros (the GEMM that reads it may
-    run over them; they meet zero weights, but a NaN bit pattern left in uninitialised memory would not vanish)."""
+    """An activation matrix [M, ld] with ``cols`` logical columns; the pad columns [cols, ld) hold zeros (the GEMM that reads it
+    runs over them; they meet zero weights, but a NaN bit pattern left in uninitialised memory would not vanish)."""
 
     def __init__(self, buf, cols):
         self.buf, self.cols, self.ld = buf, cols, buf.shape[1]
@@ -168,6 +171,12 @@ def _col(t, c):
     return t[:, c:]
 
 
+def _check_shape(model):
+    """Refuse, before anything is launched, a network the reference cannot run either."""
+    if (model.D - 1) in model.skips:
+        raise ValueError("DM_NeRF: a skip after the last trunk layer feeds W + input_ch_pts columns into W-column heads (the reference fails too)")
+
+
 class _Net:
     """The parameters of one DM_NeRF in forward order, with the dimensions the chain needs, and their packed forms."""
 
@@ -183,8 +192,7 @@ class _Net:
         self.rf, self.inf_, self.rh, self.ih = g("rgb_feature_linear"), g("ins_feature_linear"), g("rgb_feature_linears.0"), g("ins_feature_linears.0")
         self.den, self.io, self.ro = g("density_linear"), g("ins_linear"), g("rgb_linear")
         self.names = names
-        if (self.D - 1) in self.skips:
-            raise ValueError("DM_NeRF: a skip after the last trunk layer feeds W + input_ch_pts columns into W-column heads (the reference fails too)")
+        _check_shape(model)
         self._fwd = self._bwd = None
 
     def after_skip(self, i):
@@ -221,6 +229,13 @@ class _Net:
         return self._bwd
 
 
+def _chain_ok(W, inp, D):
+    """Whether the trunk of a D x W network on an ``inp``-column encoding fits csrc/gemm_chain.hip: its LDS budget
+    (dmnerf_mlp_chain_supported), at most DMNERF_CHAIN_MAX_LAYERS = 16 layers, and a bias table of D x (W / 32) x 128 bytes within
+    CH_BIAS_BYTES = 8192 (the size check of dmnerf_mlp_chain, gemm_chain.hip) -- where it does not, inference runs layer by layer."""
+    return bool(_lib.load().dmnerf_mlp_chain_supported(W, inp)) and 1 <= D <= 16 and D * (W // 32) * 128 <= 8192
+
+
 def forward_layers(net, x_pos, x_dir, save):
     """raw [M, 4 + C] for embedded inputs ``x_pos`` / ``x_dir`` (``_Act``: row-padded, pad columns zero); ``save``: dict filled with what
     backward needs.  One gemm_nt launch per linear layer; the cats of dm_nerf.py:87,90 are the second K range of the layer that reads
@@ -232,8 +247,7 @@ def forward_layers(net, x_pos, x_dir, save):
     h = None
     hs = []                                                  # the ReLU output of every trunk layer
     lib = _lib.load()
-    chained = save is None and bool(lib.dmnerf_mlp_chain_supported(W, net.inp)) and net.D <= 16 \
-        and os.environ.get("DMNERF_GENERIC_CHAIN", "1") != "0"
+    chained = save is None and _chain_ok(W, net.inp, net.D) and os.environ.get("DMNERF_GENERIC_CHAIN", "1") != "0"
     if chained:
         # inference on a narrow network: the whole trunk as ONE launch, activations LDS-resident from layer to layer (csrc/gemm_chain.hip)
         arr = (_lib.ChainLayer * net.D)()
@@ -351,6 +365,7 @@ class GenericMLPFunction(torch.autograd.Function):
 
 def mlp_embedded(model, x, train):
     """``DM_NeRF.forward`` on pre-embedded rows [..., inp + inv] through the generic path."""
+    _check_shape(model)
     x2 = _lib.f32(x.reshape(-1, x.shape[-1]))
     _lib.require_gpu(x2)
     if x2.shape[-1] != model.input_ch_pts + model.input_ch_views:
@@ -366,7 +381,8 @@ def _run(model, x_pos, x_dir, train):
     params = [p for _, p in model.named_parameters()]
     if train:
         return GenericMLPFunction.apply(model, x_pos, x_dir, *params)
-    # inference: the packed weights are kept with the model until a parameter changes (the key DM_NeRF.blob() uses)
+    # inference: the packed weights are kept with the model until a parameter changes (the key DM_NeRF.blob() uses) or
+    # DM_NeRF.invalidate_blobs() / install_packed() drops them (an update the key cannot see: .data, a graph replay)
     key = tuple((p.data_ptr(), p._version) for p in params)
     cached = getattr(model, "_generic_net", None)
     if cached is None or cached[0] != key:
@@ -377,6 +393,7 @@ def _run(model, x_pos, x_dir, train):
 
 def run_network(model, rays_o, rays_d, z, train=False):
     """pts = o + d z -> embed(pts) | embed(d/|d|) -> model, for any network shape: [N,3], [N,3], [N,S] -> raw [N,S,4+C]."""
+    _check_shape(model)
     lib = _lib.load()
     rays_o, rays_d, z = _lib.f32(rays_o.reshape(-1, 3)), _lib.f32(rays_d.reshape(-1, 3)), _lib.f32(z)
     _lib.require_gpu(rays_o, rays_d, z)

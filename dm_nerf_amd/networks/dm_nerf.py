@@ -106,6 +106,7 @@ class DM_NeRF(nn.Module):
         call this after them, or the kernels keep using the stale copy."""
         self._blob_key = self._blob_t_key = self._flat_key = None
         self._blob_f_key = self._blob_s_key = self._blob_ts_key = self._blob_h_key = self._blob_th_key = None
+        self._generic_net = None                            # the generic path's packed weights (generic.py ``_run``)
 
     def install_packed(self, flat, blob, blob_t):
         """Adopt kernel-layout copies made elsewhere from the CURRENT parameters (dm_nerf_amd.optim.FlatAdam re-packs all of them
@@ -116,6 +117,7 @@ class DM_NeRF(nn.Module):
         self._flat, self._blob, self._blob_t = flat, blob, blob_t
         self._flat_key = self._blob_key = self._blob_t_key = key
         self._blob_f_key = self._blob_s_key = self._blob_ts_key = self._blob_h_key = self._blob_th_key = None
+        self._generic_net = None
 
     def flat(self):
         """The parameters as ONE flat f32 vector in state_dict order (what the packers gather from and what the backward's

@@ -477,8 +477,10 @@ int dmnerf_copy_cols(const float* d_src, int64_t ld_src, float* d_dst, int64_t l
  *   dmnerf_gemm_nt: C[m*ldc + n] = act(sum_k A(m, k) Wp[n][k] + bias[n]) for m < M, n < n_store, zeros in columns [n_store, n_zero)
  *     (the pad columns that keep the NEXT layer's operand rows 16-byte aligned); A(m, k) = A0[m*lda0 + k] for k < k0, then
  *     A1[m*lda1 + (k - k0)] (k1 = 0: one range); lda0 / lda1 multiples of 4, base pointers 16-byte aligned, a*_floats = floats from the
- *     pointer to the end of its allocation (the kernel's descriptor bound: a row's tail may be read past k0 into the next row -- those
- *     products meet zero weights -- but never past the allocation).  relu; d_mask (nullable): C = mask[m*ldm + n] > 0 ? v : 0 (the
+ *     pointer to the end of its allocation (the kernel's descriptor bound).  A-operand contract: the kernel reads columns
+ *     [0, 32 ceil(k0 / 32)) of every A0 row (likewise A1 with k1), so lda0 >= 32 ceil(k0 / 32) and lda1 >= 32 ceil(k1 / 32) -- a shorter
+ *     row is refused with DMNERF_E_ARG, as its last chunk would read the next row -- and the columns read past k0 / k1 must be finite:
+ *     they meet zero weights, but 0 * NaN = NaN.  relu; d_mask (nullable): C = mask[m*ldm + n] > 0 ? v : 0 (the
  *     ReLU derivative of the data gradient); accumulate: C += before relu / mask.  Bias is the accumulator's initial value.
  *   dmnerf_ray_embed: pts = o + d z, viewdirs = d / |d| per sample (render.py:37,49-57) and Embedder.embed of both (dm_nerf.py:37-38)
  *     into row-padded buffers x_pos [N*S][ldp], x_dir [N*S][ldv], pad columns zeroed.
@@ -502,7 +504,10 @@ int dmnerf_gemm_tn(const float* d_dy, int64_t ldy, int64_t dy_floats, int n_out,
  * of a 128-sample tile stay in LDS from layer to layer, the weights of all layers stream through an LDS ring.  Layer l: h_l = relu?(
  * [h_{l-1} if from_act | x if from_x] W_l^T + b_l) with d_B packed by dmnerf_pack_nt (range 0 = the `width` columns of h, range 1 = the
  * x_cols columns of the encoding; layer 0: from_x only), d_bias [width]; d_x = the row-padded encoding [M][ldx] of dmnerf_ray_embed,
- * d_out = the last layer's output [M][ldo].  dmnerf_mlp_chain_supported: whether (width, x_cols) fits the CU's LDS.                    */
+ * d_out = the last layer's output [M][ldo].  d_x follows dmnerf_gemm_nt's A-operand contract: columns [0, 32 ceil(x_cols / 32)) of every
+ * row are read, so ldx >= 32 ceil(x_cols / 32) (else DMNERF_E_ARG) and the columns past x_cols must be finite.  Sizes are checked before
+ * the M = 0 return: n_layers in 1 .. DMNERF_CHAIN_MAX_LAYERS and n_layers x (width / 32) x 128 <= 8192 bytes of bias table.
+ * dmnerf_mlp_chain_supported: whether (width, x_cols) fits the CU's LDS (the layer-count bounds are the caller's to check).          */
 #define DMNERF_CHAIN_MAX_LAYERS 16
 typedef struct dmnerf_chain_layer {
     const float* d_B;

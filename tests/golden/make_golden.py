@@ -56,8 +56,11 @@ def npy(d):
     return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in d.items()}
 
 
+OUT = os.environ.get("DMNERF_GOLDEN_OUT", HERE)             # (another directory: compare a regeneration with the committed files)
+
+
 def save(name, **arrays):
-    path = os.path.join(HERE, name + ".npz")
+    path = os.path.join(OUT, name + ".npz")
     np.savez_compressed(path, **npy(arrays))
     print(f"  wrote {name}.npz  ({os.path.getsize(path) / 1024:.1f} KiB)")
 
@@ -92,6 +95,28 @@ def gen_mlp():
         out[f"seed_{ins_num}"] = np.int64(seed)
     out["gain"] = np.float64(1.7)
     save("mlp", **out)
+
+
+def gen_mlp_shapes():
+    """DM_NeRF.forward at network shapes other than the shipped one (the generic path's territory): a one-layer 32-wide trunk on
+    3-column encodings, a 13-layer 160-wide one, and the shipped width with 8 position octaves.  Weights from make_weights."""
+    out = {}
+    for tag, D, W, Lp, Lv, ins_num, seed in (("D1_W32_L0_0", 1, 32, 0, 0, 1, 111), ("D13_W160_L10_4", 13, 160, 10, 4, 13, 112),
+                                             ("D8_W256_L8_4", 8, 256, 8, 4, 13, 113)):
+        inp, inv = O.embed_out_dim(Lp), O.embed_out_dim(Lv)
+        sd = O.make_weights(seed, ins_num, W=W, gain=1.5, D=D, input_ch_pts=inp, input_ch_views=inv)
+        g = torch.Generator().manual_seed(seed)
+        pts = (torch.rand(64, 3, generator=g) * 2 - 1) * 6.0
+        dirs = torch.nn.functional.normalize(torch.randn(64, 3, generator=g), dim=-1)
+        x = torch.cat([O.embed(pts, Lp), O.embed(dirs, Lv)], -1)
+        m = R_model.DM_NeRF(D, W, inp, inv, [4], ins_num)
+        m.load_state_dict(sd)
+        with torch.no_grad():
+            y = m.eval()(x)
+            beq(O.mlp_forward(sd, x, input_ch_pts=inp, input_ch_views=inv, D=D), y, f"mlp {tag}")
+        out.update({f"{tag}_x": x, f"{tag}_y": y, f"{tag}_dims": np.array([D, W, Lp, Lv, ins_num, seed], dtype=np.int64)})
+    out["gain"] = np.float64(1.5)
+    save("mlp_shapes", **out)
 
 
 def gen_render_train():
@@ -787,6 +812,7 @@ if __name__ == "__main__":
         sys.exit(0)
     gen_embed()
     gen_mlp()
+    gen_mlp_shapes()
     gen_render_train()
     gen_sample_pdf()
     gen_rays()

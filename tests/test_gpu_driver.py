@@ -21,11 +21,12 @@ def A():
     return types.SimpleNamespace(M=M, H=H, R=R, D=D)
 
 
-def models(A, ins_num=13):
+def models(A, ins_num=13, D=8, W=256):
+    """Coarse and fine DM_NeRF with synthetic weights; D / W other than 8 / 256 give a generic-path shape (dm_nerf_amd/generic.py)."""
     out = []
     for seed in (61, 62):
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3))
+        m = A.M.DM_NeRF(D, W, 63, 27, [4], ins_num)
+        m.load_state_dict(O.make_weights(seed, ins_num, W=W, D=D, gain=1.7, sigma_bias=0.3))
         out.append(m.cuda().eval())
     return out
 
@@ -177,6 +178,17 @@ def test_eager_render_between_graph_replays_sees_the_current_weights(A):
     step must use the parameters as the LAST replay left them.  (Replays do not bump the parameters' ``_version``, the key of the
     models' packed-weight caches, so the second evaluation once reused the first one's weights.)  Replay, eval, replay, eval:
     both evaluations equal the render of an eagerly trained twin at the same point, bit for bit."""
+    eager_render_between_graph_replays(A, 8, 256)
+
+
+def test_eager_render_between_graph_replays_sees_the_current_weights_generic_shape(A):
+    """The same for a generic-path shape (6 x 128, dm_nerf_amd/generic.py), whose inference keeps its own packed weights
+    (generic.py ``_run``): GraphedTrainStep's invalidate_blobs() after a replay must reach that cache too."""
+    eager_render_between_graph_replays(A, 6, 128)
+
+
+def eager_render_between_graph_replays(A, depth, width):
+    """Replay, eval, replay, eval on a depth x width network; both evaluations equal an eagerly trained twin's, bit for bit."""
     from dm_nerf_amd import distributed as D
     from dm_nerf_amd.graphed import GraphedTrainStep
     N, ins_num = 64, 13
@@ -192,7 +204,7 @@ def test_eager_render_between_graph_replays_sees_the_current_weights(A):
     eval_rays = torch.stack([ro[150000:150000 + N], rd[150000:150000 + N]]).cuda()
 
     def fresh():
-        mc, mf = models(A)
+        mc, mf = models(A, D=depth, W=width)
         mc.train(); mf.train()
         opt = torch.optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=torch.tensor(5e-4, device="cuda"), capturable=True)
         return mc, mf, opt

@@ -335,4 +335,192 @@ def test_generic_entry_points_reject_what_they_cannot_do(A):
     assert chain([l0, l1], width=192) == -1 and "not supported" in L.last_error()
     assert chain([l0, l1], ldo=64) == -1
     assert chain([l0] * 17) == -1
+    # A rows shorter than the 32-column chunks the kernels fetch (the last chunk would read the next row): refused
+    xs = G._Act(torch.zeros(256, 64, device=dev), inp)
+    xs.ld = 60
+    arr = (L.ChainLayer * 2)(l0, l1)
+    assert lib.dmnerf_mlp_chain(L.ptr(xs.buf), 60, xs.buf.numel(), inp, arr, 2, W_, L.ptr(out.buf), out.ld, 256, L.stream()) == -1
+    assert "32-column" in L.last_error()
+    a27 = G._Act(torch.zeros(64, 28, device=dev), 27)
+    p27 = G._Packed(torch.randn(32, 27, device=dev), torch.zeros(32, device=dev), [(0, 27)])
+    y27 = torch.full((64, 32), 7.0, device=dev)
+    with pytest.raises(RuntimeError, match="32-column"):
+        G._linear_nt(a27, p27, y27, 32, 32, 32, 64)
     torch.cuda.synchronize()
+    assert torch.all(y27 == 7.0)
+
+
+# ---- the shape sweep: every corner of the generic path's shape space the five rows above do not reach, each against float64
+SWEEP = [dict(D=1, W=32, multires=0, multires_views=0, ins_num=1),       # one-layer trunk (backward's i = 0 only), the narrowest chained
+                                                                          # width, 3-column encodings (k = 3 inside one 32-column chunk), C = 2
+         dict(D=3, W=96, multires=4, multires_views=0, ins_num=7),       # D <= 4: the skip is never reached; a 3-column direction input to rh
+         dict(D=4, W=90, multires=6, multires_views=2, ins_num=13),      # W not a multiple of 32 (chain refused), HW = 45; 39- / 15-column encodings
+         dict(D=13, W=160, multires=10, multires_views=4, ins_num=13),   # the chain's bias table overflows at five out-blocks (13 * 5 * 128 > 8192)
+         dict(D=16, W=128, multires=10, multires_views=4, ins_num=13),   # DMNERF_CHAIN_MAX_LAYERS exactly, bias table exactly full (16 * 4 * 128)
+         dict(D=17, W=64, multires=6, multires_views=2, ins_num=5),      # one layer beyond the chain's limit
+         dict(D=8, W=256, multires=8, multires_views=4, ins_num=13),     # the shipped width with a non-shipped encoding
+         dict(D=6, W=256, multires=10, multires_views=4, ins_num=93),    # shipped width and encodings, shallower; C = 94
+         dict(D=8, W=512, multires=10, multires_views=4, ins_num=13)]    # widest: HW = 256, several output tiles per layer
+
+
+def chain_expected(lib, D, W, inp):
+    """Whether inference should take the chained trunk, from csrc/gemm_chain.hip's own limits: the LDS fit
+    (dmnerf_mlp_chain_supported), at most DMNERF_CHAIN_MAX_LAYERS = 16 layers, and a bias table of n_layers x (W / 32) x 128 bytes
+    within CH_BIAS_BYTES = 8192."""
+    return bool(lib.dmnerf_mlp_chain_supported(W, inp)) and 1 <= D <= 16 and D * (W // 32) * 128 <= 8192
+
+
+def spy_on(lib, monkeypatch, names):
+    """Count the calls of the library entry points ``names`` (the Python side resolves them on the loaded library each time)."""
+    calls = {n: 0 for n in names}
+    for n in names:
+        real = getattr(lib, n)
+
+        def spy(*a, _n=n, _real=real):
+            calls[_n] += 1
+            return _real(*a)
+        monkeypatch.setattr(lib, n, spy)
+    return calls
+
+
+@pytest.mark.parametrize("cfg", SWEEP, ids=lambda c: f"D{c['D']}_W{c['W']}_L{c['multires']}-{c['multires_views']}_C{c['ins_num'] + 1}")
+def test_generic_shape_sweep_against_float64(A, cfg, monkeypatch):
+    """The checks of test_model_forward_and_gradients_other_shapes at each SWEEP row, plus the trunk run both ways: layer by layer
+    (DMNERF_GENERIC_CHAIN=0) and as configured, equal bit for bit, with the chained launch counted so that a silent fallback cannot
+    pass as coverage of the chain.  M = 300 rows (two full 128-row tiles and a ragged one).  The existing tolerances hold at every
+    depth: make_weights' U(-g / sqrt(fan_in), g / sqrt(fan_in)) weights with g = 1.5 scale a ReLU layer's mean square by
+    fan_in * (g^2 / (3 fan_in)) / 2 = g^2 / 6 = 0.375, so activations shrink with depth (D = 17 included) instead of growing, and
+    neither the relative forward bound nor the gradient bound (relative to the largest gradient entry) needs widening."""
+    D, W, ins_num = cfg["D"], cfg["W"], cfg["ins_num"]
+    inp, inv = 3 + 6 * cfg["multires"], 3 + 6 * cfg["multires_views"]
+    sd = O.make_weights(7 + D, ins_num, W=W, gain=1.5, D=D, input_ch_pts=inp, input_ch_views=inv)
+    m = A.M.DM_NeRF(D, W, inp, inv, [4], ins_num)
+    m.load_state_dict(sd)
+    m = m.cuda()
+    assert not m._fused_ok()
+    lib = A.lib.load()
+    calls = spy_on(lib, monkeypatch, ["dmnerf_mlp_chain"])
+    g = torch.Generator().manual_seed(100 + D)
+    Mr = 300
+    pts = (torch.rand(Mr, 3, generator=g) * 2 - 1) * 5.0
+    dirs = torch.nn.functional.normalize(torch.randn(Mr, 3, generator=g), dim=-1)
+    x = torch.cat([O.embed(pts, cfg["multires"]), O.embed(dirs, cfg["multires_views"])], -1)
+    cot = torch.randn(Mr, 4 + ins_num + 1, generator=g)
+    sdg = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    want = O.mlp_forward(sdg, x, input_ch_pts=inp, input_ch_views=inv, D=D)
+    (want * cot).sum().backward()
+    with torch.no_grad():
+        monkeypatch.setenv("DMNERF_GENERIC_CHAIN", "0")
+        y_layers = m(x.cuda())
+        assert calls["dmnerf_mlp_chain"] == 0
+        monkeypatch.setenv("DMNERF_GENERIC_CHAIN", "1")
+        y0 = m(x.cuda())
+    assert calls["dmnerf_mlp_chain"] == int(chain_expected(lib, D, W, inp)), (calls, D, W, inp)
+    assert torch.equal(y0, y_layers), float((y0 - y_layers).abs().max())
+    assert y0.shape == want.shape and maxrel(cpu(y0), want.detach()) <= 1e-5, maxrel(cpu(y0), want.detach())
+    m.train()
+    y = m(x.cuda())
+    assert calls["dmnerf_mlp_chain"] == int(chain_expected(lib, D, W, inp))      # (training never chains: it keeps every activation)
+    assert y.requires_grad and torch.equal(y.detach(), y0)
+    (y * cot.cuda()).sum().backward()
+    for k, p in m.named_parameters():
+        assert p.grad is not None and p.grad.shape == p.shape, k
+        gw = sdg[k].grad.double()
+        err = float((p.grad.cpu().double() - gw).abs().max())
+        assert err <= 2e-4 * float(gw.abs().max()) + 1e-7, (k, err, float(gw.abs().max()))
+    m.zero_grad()
+    m(x.cuda())[:, 4:].square().sum().backward()
+    for k, p in m.named_parameters():
+        assert (float(p.grad.abs().max()) > 0) == k.startswith(("ins_feature_linear", "ins_feature_linears.0", "ins_linear")), k
+
+
+def test_skip_after_the_last_trunk_layer_is_refused_before_any_launch(A, monkeypatch):
+    """D = 5 with skips [4]: the skip's cat [h, pts] would feed W + input_ch_pts columns into the W-column heads (the reference's
+    forward fails too).  Inference, training and the per-ray path raise a ValueError that says so, and launch nothing."""
+    D, W, ins_num, inp, inv = 5, 64, 5, 39, 15
+    m = A.M.DM_NeRF(D, W, inp, inv, [4], ins_num)
+    m.load_state_dict(O.make_weights(3, ins_num, W=W, D=D, input_ch_pts=inp, input_ch_views=inv))
+    m = m.cuda()
+    x = torch.randn(40, inp + inv, device="cuda")
+    ro, rd, z = torch.zeros(4, 3, device="cuda"), torch.ones(4, 3, device="cuda"), torch.rand(4, 8, device="cuda")
+    torch.cuda.synchronize()
+    lib = A.lib.load()
+    calls = spy_on(lib, monkeypatch, ["dmnerf_copy_cols_pad", "dmnerf_ray_embed", "dmnerf_pack_nt", "dmnerf_gemm_nt", "dmnerf_mlp_chain",
+                                      "dmnerf_gemm_tn"])
+    with torch.no_grad(), pytest.raises(ValueError, match="skip after the last trunk layer"):
+        m(x)
+    m.train()
+    with pytest.raises(ValueError, match="skip after the last trunk layer"):
+        m(x)
+    with torch.no_grad(), pytest.raises(ValueError, match="skip after the last trunk layer"):
+        A.R.run_network(m, ro, rd, z)
+    with pytest.raises(ValueError, match="skip after the last trunk layer"):
+        A.G.run_network(m, ro, rd, z, train=True)
+    assert all(v == 0 for v in calls.values()), calls
+
+
+@pytest.mark.parametrize("D,W,multires,multires_views,i_embed", [(8, 256, 8, 4, 0), (8, 256, 10, 4, -1)], ids=["D8_W256_L8-4", "identity_embedder"])
+def test_dm_nerf_dict_generic_shapes_of_the_shipped_width(A, D, W, multires, multires_views, i_embed):
+    """create_nerf -> the 10-key dict against the oracle at the shipped width with a non-shipped encoding, and with i_embed = -1 (an
+    identity embedder: 3 + 3 input channels, so the shipped D and W go generic).  Same assertions as test_dm_nerf_dict_other_shapes."""
+    ins_num = 13
+    args = types.SimpleNamespace(multires=multires, multires_views=multires_views, i_embed=i_embed, netdepth=D, netwidth=W, ins_num=ins_num,
+                                 device=torch.device("cuda:0"))
+    with pytest.warns(RuntimeWarning, match="generic GEMM path"):
+        pe, ve, mc, mf, _ = A.Cfg.create_nerf(args)
+    # (the identity embedder is the input itself: what the oracle's encoding gives with zero octaves)
+    Lp, Lv = (multires, multires_views) if i_embed == 0 else (0, 0)
+    inp, inv = 3 + 6 * Lp, 3 + 6 * Lv
+    assert (mf.input_ch_pts, mf.input_ch_views) == (inp, inv) and not mf._fused_ok()
+    kw = dict(W=W, gain=1.7, sigma_bias=0.3, D=D, input_ch_pts=inp, input_ch_views=inv)
+    sd_c, sd_f = O.make_weights(33, ins_num, **kw), O.make_weights(34, ins_num, **kw)
+    mc.load_state_dict(sd_c); mf.load_state_dict(sd_f)
+    K = O.dmsr_intrinsics(480, 640)
+    ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(70.0, -65.0, 7.0))
+    sel = torch.from_numpy(np.random.RandomState(D + 17 * Lp).choice(480 * 640, 70, replace=False))
+    rays = torch.stack([ro.reshape(-1, 3)[sel], rd.reshape(-1, 3)[sel]], 0)
+    z = O.z_val_sample(70, 4.0, 15.0, 64).contiguous()
+    eargs = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
+    mc.eval(); mf.eval()
+    with torch.no_grad():
+        want = O.dm_nerf(rays, sd_c, sd_f, z, perturb=0., multires=Lp, multires_views=Lv)
+        got = {k: cpu(v) for k, v in A.R.dm_nerf(rays.cuda(), pe, ve, mc, mf, z.cuda(), eargs).items()}
+        raw_f = cpu(A.R.run_network(mf, rays[0].cuda(), rays[1].cuda(), want['z_vals_fine'].cuda()))
+    assert set(got) == set(want) and got['raw_fine'].shape == (70, 192, 4 + ins_num + 1)
+    assert maxrel(got['raw_coarse'], want['raw_coarse']) <= 1e-5 and maxrel(raw_f, want['raw_fine']) <= 1e-5
+    assert torch.allclose(got['rgb_coarse'], want['rgb_coarse'], rtol=2e-6, atol=2e-6)
+    assert torch.allclose(got['ins_coarse'], want['ins_coarse'], rtol=2e-6, atol=2e-6)
+    assert float(((got['z_vals_fine'] - want['z_vals_fine']).abs() <= 1e-4).float().mean()) >= 0.999
+    assert torch.allclose(got['rgb_fine'], want['rgb_fine'], atol=2e-3)
+    mc.train(); mf.train()
+    targs = types.SimpleNamespace(perturb=0.0, N_importance=128, is_train=True, N_ins=None)
+    out = A.R.dm_nerf(rays.cuda(), pe, ve, mc, mf, z.cuda(), targs)
+    (out['rgb_fine'].sum() + out['rgb_coarse'].sum() + out['ins_fine'].sum() + out['ins_coarse'].sum()).backward()
+    sdc = {k: v.clone().requires_grad_(True) for k, v in sd_c.items()}
+    sdf = {k: v.clone().requires_grad_(True) for k, v in sd_f.items()}
+    o = O.dm_nerf(rays, sdc, sdf, z, perturb=0., multires=Lp, multires_views=Lv, z_fine_override=out['z_vals_fine'].detach().cpu())
+    (o['rgb_fine'].sum() + o['rgb_coarse'].sum() + o['ins_fine'].sum() + o['ins_coarse'].sum()).backward()
+    for m_, sd_ in ((mc, sdc), (mf, sdf)):
+        for k, p in m_.named_parameters():
+            gw = sd_[k].grad.double()
+            rel_l2 = float((p.grad.cpu().double() - gw).norm() / (gw.norm() + 1e-30))
+            assert rel_l2 <= 2e-3, (k, rel_l2)
+
+
+def test_invalidate_blobs_after_a_data_update_generic_shape(A):
+    """The generic twin of test_gpu_edges.py::test_invalidate_blobs_after_a_data_update: inference keeps its packed weights with
+    the model (keyed like DM_NeRF.blob), so an update THROUGH ``.data`` is invisible until ``invalidate_blobs()`` -- which must then
+    reach that cache too."""
+    D, W, ins_num, inp, inv = 6, 128, 13, 63, 27
+    m = A.M.DM_NeRF(D, W, inp, inv, [4], ins_num)
+    m.load_state_dict(O.make_weights(4, ins_num, W=W, gain=1.7, D=D, input_ch_pts=inp, input_ch_views=inv))
+    m = m.cuda().eval()
+    x = torch.randn(64, inp + inv).cuda()
+    with torch.no_grad():
+        y0 = m(x)
+        m.density_linear.bias.data.add_(1.0)
+        y_stale = m(x)
+        m.invalidate_blobs()
+        y1 = m(x)
+    assert torch.equal(y_stale, y0)                                           # the documented pitfall
+    assert torch.allclose(y1[:, 3], y0[:, 3] + 1.0, atol=1e-5) and torch.equal(y1[:, :3], y0[:, :3])

@@ -236,3 +236,18 @@ def test_checkpoint_format_matches_the_module():
     assert [[k, list(v.shape)] for k, v in m.state_dict().items()] == fmt["model_keys"]
     assert fmt["top_keys"] == ['iteration', 'network_coarse_state_dict', 'network_fine_state_dict', 'optimizer_state_dict']
     assert fmt["state_shapes"][:2] == [[256, 63], [256]] and fmt["n_params"] == 60
+
+
+def test_mlp_at_generic_path_shapes(golden):
+    """The oracle's DM_NeRF.forward against the reference's at three shapes only the generic path runs: a one-layer 32-wide trunk
+    on 3-column encodings (C = 2), 13 layers of 160 (the skip mid-trunk), and the shipped width with 8 position octaves."""
+    g = golden("mlp_shapes")
+    for tag in ("D1_W32_L0_0", "D13_W160_L10_4", "D8_W256_L8_4"):
+        D, W, Lp, Lv, ins_num, seed = (int(v) for v in g[f"{tag}_dims"])
+        inp, inv = O.embed_out_dim(Lp), O.embed_out_dim(Lv)
+        sd = O.make_weights(seed, ins_num, W=W, gain=float(g["gain"]), D=D, input_ch_pts=inp, input_ch_views=inv)
+        x = g[f"{tag}_x"]
+        assert x.shape == (64, inp + inv)
+        y = O.mlp_forward(sd, x, input_ch_pts=inp, input_ch_views=inv, D=D)
+        assert y.shape == (64, 4 + ins_num + 1)
+        close(y, g[f"{tag}_y"], rtol=1e-5, atol=1e-5)
