@@ -12,7 +12,7 @@
 //                       with one workgroup this latency-bound sum was 0.8 of the 1.0 ms the loss took at ins_num 93
 //   cr_solve_kernel     sums -> cost matrices (rows = the labels that occur, ascending: the one-hot
 //                       compaction of :21-26), then the rectangular assignment by shortest augmenting paths
-//                       (the algorithm scipy implements, Crouse 2016) on one wavefront with the column scan
+//                       (the algorithm scipy implements, Crouse 2016; lsa_wave.h, shared with ins_eval.hip) on one wavefront with the column scan
 //                       spread over the lanes, then the three loss terms
 //   cr_bwd_kernel       d loss / d pred, elementwise (matched channels: cross-entropy + soft-IoU terms,
 //                       unmatched channels: 1 / (N U))
@@ -24,12 +24,13 @@
 
 #include "../../include/dmnerf_hip.h"
 #include "common.h"
+#include "lsa_wave.h"
 
 
 namespace {
 
 constexpr int CR_CHUNK = 64;      // rays per partial-sum block
-constexpr int CR_MAXC = 128;      // channels (= ins_num) supported by the solver's lane mapping (2 columns per lane)
+constexpr int CR_MAXC = LSA_MAXC;  // channels (= ins_num) supported by the solver's lane mapping (2 columns per lane)
 
 // Work buffer layout (byte offsets; everything 8-byte aligned).  L = C + 1 label values 0..C.
 struct CrLayout {
@@ -156,18 +157,6 @@ __global__ __launch_bounds__(256) void cr_reduce_kernel(int64_t N, int C, const 
 }
 
 // ---- cost matrices, assignment, loss terms: one workgroup ------------------------------------------------
-__device__ __forceinline__ double wave_min_key(double v, int key, int& key_out) {
-    // minimum of v over the wave; ties: smaller key.  Returns the minimum, key_out = its key.
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double ov = __shfl_xor(v, off);
-        const int ok = __shfl_xor(key, off);
-        if (ov < v || (ov == v && ok < key)) { v = ov; key = ok; }
-    }
-    key_out = key;
-    return v;
-}
-
 __global__ __launch_bounds__(256) void cr_solve_kernel(int64_t N, int C, const CrPair pr) {
     char* __restrict__ work = pr.work[blockIdx.x];
     float* __restrict__ out4 = pr.out4[blockIdx.x];
@@ -175,9 +164,7 @@ __global__ __launch_bounds__(256) void cr_solve_kernel(int64_t N, int C, const C
     const int L = w.L, tid = threadIdx.x;
     __shared__ int s_cnt[CR_MAXC + 1], s_rank[CR_MAXC + 1], s_V;
     __shared__ double s_A[CR_MAXC], s_S[CR_MAXC];
-    __shared__ double s_u[CR_MAXC], s_v[CR_MAXC], s_spc[CR_MAXC];
-    __shared__ int s_path[CR_MAXC], s_col4row[CR_MAXC], s_row4col[CR_MAXC];
-    __shared__ unsigned char s_SR[CR_MAXC], s_SC[CR_MAXC];
+    __shared__ LsaShared s_lsa;
     __shared__ int s_flags;
     if (tid == 0) s_flags = 0;
     __syncthreads();
@@ -235,60 +222,10 @@ __global__ __launch_bounds__(256) void cr_solve_kernel(int64_t N, int C, const C
 
     // 3. rectangular assignment of the V label rows to the C channels (V <= C) by shortest augmenting paths
     //    (evaluator.py:43-47 -> scipy linear_sum_assignment).  Wave 0; lane j owns columns j and j + 64.
-    if (tid < 64) {
-        const int lane = tid;
-        for (int j = lane; j < C; j += 64) { s_v[j] = 0.0; s_row4col[j] = -1; }
-        for (int i = lane; i < V; i += 64) { s_u[i] = 0.0; s_col4row[i] = -1; }
-        __builtin_amdgcn_wave_barrier();
-        for (int cur = 0; cur < V; ++cur) {
-            for (int j = lane; j < C; j += 64) { s_spc[j] = __builtin_inf(); s_SC[j] = 0; s_path[j] = -1; }
-            for (int i = lane; i < V; i += 64) s_SR[i] = 0;
-            __builtin_amdgcn_wave_barrier();
-            double min_val = 0.0;
-            int i = cur, sink = -1;
-            while (sink < 0) {
-                if (lane == 0) s_SR[i] = 1;
-                const double ui = s_u[i];
-                double best = __builtin_inf();
-                int best_key = 0x7fffffff;
-                for (int j = lane; j < C; j += 64) {
-                    if (s_SC[j]) continue;
-                    const double cost = (double)(ce[i * C + j] + siou[i * C + j]);      // f32 add as in `cost_ce + cost_siou` (:69)
-                    const double r = min_val + cost - ui - s_v[j];
-                    if (r < s_spc[j]) { s_spc[j] = r; s_path[j] = i; }
-                    const double sj = s_spc[j];
-                    // ties: an unassigned column first (it ends the search), then the lower index
-                    const int key = (s_row4col[j] < 0 ? 0 : CR_MAXC) + j;
-                    if (sj < best || (sj == best && key < best_key)) { best = sj; best_key = key; }
-                }
-                int key;
-                min_val = wave_min_key(best, best_key, key);
-                const int jstar = key >= CR_MAXC ? key - CR_MAXC : key;
-                if (lane == 0) s_SC[jstar] = 1;
-                __builtin_amdgcn_wave_barrier();
-                if (s_row4col[jstar] < 0) sink = jstar; else i = s_row4col[jstar];
-            }
-            // dual updates
-            for (int r = lane; r < V; r += 64)
-                if (s_SR[r]) s_u[r] += (r == cur) ? min_val : min_val - s_spc[s_col4row[r]];
-            for (int j = lane; j < C; j += 64)
-                if (s_SC[j]) s_v[j] -= min_val - s_spc[j];
-            __builtin_amdgcn_wave_barrier();
-            // augment along the path (serial; at most V steps)
-            if (lane == 0) {
-                int j = sink;
-                while (true) {
-                    const int r = s_path[j];
-                    s_row4col[j] = r;
-                    const int prev = s_col4row[r];
-                    s_col4row[r] = j;
-                    j = prev;
-                    if (r == cur) break;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
+    if (tid < 64)
+        lsa_solve_wave(s_lsa, V, C, tid, [&](int i, int j) {
+            return (double)(ce[i * C + j] + siou[i * C + j]);       // f32 add as in `cost_ce + cost_siou` (:69)
+        });
     __syncthreads();
 
     // 4. loss terms (evaluator.py:28-37) and what the backward needs
@@ -296,7 +233,7 @@ __global__ __launch_bounds__(256) void cr_solve_kernel(int64_t N, int C, const C
     float* tp_of_col = reinterpret_cast<float*>(work + w.tp_of_col);
     float* den_of_col = reinterpret_cast<float*>(work + w.den_of_col);
     for (int p = tid; p < C; p += blockDim.x) {
-        const int g = s_row4col[p];
+        const int g = s_lsa.row4col[p];
         row4col[p] = g;
         if (g >= 0) {
             const int l = lab_of_row[g];
@@ -307,10 +244,10 @@ __global__ __launch_bounds__(256) void cr_solve_kernel(int64_t N, int C, const C
     }
     if (tid == 0) {
         double sce = 0.0, ssi = 0.0, sinv = 0.0;
-        for (int g = 0; g < V; ++g) { sce += (double)ce[g * C + s_col4row[g]]; ssi += (double)siou[g * C + s_col4row[g]]; }
+        for (int g = 0; g < V; ++g) { sce += (double)ce[g * C + s_lsa.col4row[g]]; ssi += (double)siou[g * C + s_lsa.col4row[g]]; }
         int U = 0;
         for (int p = 0; p < C; ++p)
-            if (s_row4col[p] < 0) { sinv += s_S[p]; ++U; }
+            if (s_lsa.row4col[p] < 0) { sinv += s_S[p]; ++U; }
         const float valid_ce = V > 0 ? (float)(sce / V) : 0.f;
         const float valid_siou = V > 0 ? (float)(ssi / V) : 0.f;
         const float invalid_ce = U > 0 ? (float)(sinv / ((double)N * U)) : 0.f;     // torch.tensor([0]) when every channel is matched (:33)

@@ -488,7 +488,7 @@ def render_frame(H, W, K, c2w, models, near, far, args, chunk=4096, n_samples=64
     return fr.gather()
 
 
-def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, labels_only=False, **frame_kw):
+def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, labels_only=False, gt_labels=None, **frame_kw):
     """The pose loop of ``render_test`` (networks/tester.py:55-90) without its file output and CPU metrics: every pose of
     ``render_poses [P,3or4,4]`` through ``render_frame`` (rows sharded over the ranks, chunks of ``args.N_test`` rays),
     the ScanNet ``crop_mask`` applied as the reference applies it (:78-82: the pixels with mask 1, reshaped to
@@ -496,7 +496,15 @@ def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, l
     (data_range 1, what ``skimage.metrics.peak_signal_noise_ratio`` computes at :89).
 
     Returns a dict of stacked device tensors: ``rgb [P,h,w,3]``, ``depth [P,h,w]``, and either ``ins [P,h,w,ins_num]`` or,
-    with ``labels_only=True``, ``label [P,h,w]`` (int64) and ``conf [P,h,w]``; ``psnr [P]`` when ``gt_imgs`` is given."""
+    with ``labels_only=True``, ``label [P,h,w]`` (int64) and ``conf [P,h,w]``; ``psnr [P]`` when ``gt_imgs`` is given.
+
+    Given ``gt_labels [P,h,w]`` (the per-pixel instance labels of the test set, in the frame's shape), also the instance AP of every
+    pose as ``render_test`` scores it (tester.py:97-118 -> ``ins_eval``), on the device (``evaluator.ins_eval_device``): ``ap
+    [P,6]`` (AP50, AP75, AP80, AP85, AP90, AP95), ``matched [P,ins_num]`` (the predicted label matched to each gt row; -1 unmatched
+    and beyond the pose's row count: the data of ``matching_log.json``) and ``gt_num [P]``.  The rows are ``unique(gt_label)``, with
+    ``crop_mask`` ``unique(gt_label)[:-1]`` and the mask ``gt_label < ins_num``, as in the two branches of the reference.  A pose
+    without rows gets six APs of 1.0 (the reference appends ``tensor([1.0])`` there and fails later at tester.py:150).
+    ``labels_only=True`` is the cheap way to it: the AP needs only the label and the confidence of each pixel."""
     H, W, K = hwk
     chunk = int(getattr(args, "N_test", 4096))
     n_samples = int(getattr(args, "N_samples", 64))
@@ -520,7 +528,38 @@ def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, l
             gt = torch.as_tensor(gt_imgs[i]).to(cols["rgb"][-1])
             mse = torch.mean((cols["rgb"][-1] - gt) ** 2)
             cols.setdefault("psnr", []).append(-10.0 * torch.log10(mse))
+        if gt_labels is not None:
+            for name, t in zip(("ap", "matched", "gt_num"), _frame_ap(cols, gt_labels[i], crop_mask is not None, labels_only, args,
+                                                                       frame_kw)):
+                cols.setdefault(name, []).append(t)
     return {k: torch.stack(v, 0) for k, v in cols.items()}
+
+
+def _frame_ap(cols, gt_label, crop, labels_only, args, frame_kw):
+    """One pose's ``(ap [6], matched [ins_num], gt_num)`` for render_path: the rows and the mask of tester.py:97-118, then
+    ``ins_eval_device``."""
+    from .networks import evaluator
+    if labels_only:
+        label, conf = cols["label"][-1], cols["conf"][-1]
+        ins_num = frame_kw.get("ins_num") or getattr(args, "ins_num", None)
+        if ins_num is None:
+            raise ValueError("render_path(gt_labels=...): pass ins_num= or set args.ins_num")
+    else:
+        label, conf = evaluator.ins_label_conf(cols["ins"][-1])
+        ins_num = cols["ins"][-1].shape[-1]
+    ins_num = int(ins_num)
+    gl = torch.as_tensor(gt_label).to(device=label.device, dtype=torch.int64).reshape(label.shape)
+    rows = torch.unique(gl)
+    mask = None
+    if crop:
+        rows = rows[:-1]
+        mask = (gl < ins_num).to(torch.float32)
+    n = int(rows.numel())
+    if n == 0:
+        return (torch.ones(6, dtype=torch.float32, device=label.device), torch.full((ins_num,), -1, dtype=torch.int64, device=label.device),
+                torch.tensor(0, dtype=torch.int64, device=label.device))
+    _, ap, matched = evaluator.ins_eval_device(label, conf, gl, rows, ins_num, mask)
+    return ap, matched, torch.tensor(n, dtype=torch.int64, device=label.device)
 
 
 def _matmul4_f32(a, b):

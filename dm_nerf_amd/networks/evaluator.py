@@ -3,8 +3,9 @@
 
 ``ins_criterion`` runs entirely on the GPU stream (csrc/criterion.hip): the reference moves the cost matrix to the
 host for ``scipy.optimize.linear_sum_assignment`` and syncs twice per step.  The metrics half of
-the file (``calculate_ap``, ``ins_eval``) is evaluation tooling and stays with the reference, except the per-pixel
-label / confidence every rendered frame needs (``ins_label_conf``), which the frame driver computes on the device.
+the file runs on the device too: the per-pixel label / confidence every rendered frame needs (``ins_label_conf``) and the
+instance AP of a frame (``ins_eval``, ``ins_eval_device``: csrc/ins_eval.hip).  ``calculate_ap`` on its own has no device
+version: the AP integral is the last step of the ``ins_eval`` kernel, which works on counts, not on an IoU vector.
 """
 import torch
 
@@ -92,3 +93,110 @@ def ins_label_conf(pred_ins):
     _lib.check(_lib.load().dmnerf_ins_label_conf(_lib.ptr(flat), flat.shape[0], C, _lib.ptr(label), _lib.ptr(conf), _lib.stream()),
                "dmnerf_ins_label_conf")
     return label.reshape(x.shape[:-1]), conf.reshape(x.shape[:-1])
+
+
+IE_LABEL_RANGE, IE_GT_NOT_ONEHOT = 1, 2               # DMNERF_IE_* (include/dmnerf_hip.h)
+THRESHOLDS = (0.5, 0.75, 0.8, 0.85, 0.9, 0.95)        # evaluator.py:10
+
+
+def _rows_view(t):
+    """``t [..., K]`` as (tensor, number of rows, row stride in elements) without a copy when its rows are evenly spaced with a
+    unit inner stride (a channel slice such as ``ins[..., :-1]``); otherwise a contiguous f32 copy (plumbing)."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    lead = t.shape[:-1]
+    n = 1
+    for s in lead:
+        n *= int(s)
+    if t.dim() >= 2 and t.stride(-1) == 1:
+        rs = t.stride(-2)
+        expect, ok = rs, True
+        for d in range(t.dim() - 2, -1, -1):           # every leading dim must step by (inner rows) x row stride
+            if t.shape[d] != 1 and t.stride(d) != expect:
+                ok = False
+                break
+            expect *= int(t.shape[d])
+        if ok and rs >= t.shape[-1]:
+            return t, n, rs
+    t = t.contiguous()
+    return t, n, t.shape[-1]
+
+
+def _ins_eval_run(N, ins_num, gt_num, masked, device, prep_args):
+    lib = _lib.load()
+    nbytes = lib.dmnerf_ins_eval_work_bytes(N, ins_num)
+    if nbytes < 0:
+        raise ValueError(f"ins_eval: unsupported N={N} ins_num={ins_num} (ins_num <= 128)")
+    if not 0 <= gt_num <= ins_num:
+        raise ValueError(f"ins_eval: gt_num={gt_num} must lie in [0, ins_num={ins_num}]")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    label = torch.empty(N, dtype=torch.int64, device=device)
+    ap = torch.empty(6, dtype=torch.float32, device=device)
+    matched = torch.empty(ins_num, dtype=torch.int64, device=device)
+    args = prep_args(label)
+    _lib.check(lib.dmnerf_ins_eval_prep(*args, gt_num, N, ins_num, _lib.ptr(work), nbytes, _lib.stream()), "dmnerf_ins_eval_prep")
+    _lib.check(lib.dmnerf_ins_eval(N, ins_num, gt_num, 1 if masked else 0, _lib.ptr(work), nbytes, _lib.ptr(ap), _lib.ptr(matched),
+                                   _lib.stream()), "dmnerf_ins_eval")
+    return label, ap, matched, work
+
+
+def ins_eval_device(pred_label, pred_conf, gt_label, gt_rows, ins_num, mask=None):
+    """``ins_eval`` (networks/evaluator.py:125-175) of one frame from its per-pixel ``pred_label`` (int, argmax over the object
+    channels, in ``[0, ins_num)``) and ``pred_conf`` (the max) -- e.g. ``render_frame(..., labels_only=True)``'s output -- and the
+    ground truth as per-pixel labels ``gt_label`` with ``gt_rows`` (int64 ``[gt_num]``, ascending): the labels that form the rows,
+    the reference's ``valid_gt_labels``.  No host synchronisation, no allocation outside the returned tensors; capturable.
+
+    Returns device tensors ``(pred_label, ap [6], matched [ins_num])``: the labels with the mask rule applied (``ins_num`` where
+    ``mask == 0``), the six APs (float32) and the matched predicted label of each gt row (``return_labels``; -1 for an unmatched
+    row and beyond ``gt_num``).  Where the reference raises because no predicted label is valid, every row is unmatched and the
+    APs are 0."""
+    _lib.require_gpu(pred_label, pred_conf, gt_label, gt_rows, mask)
+    ins_num = int(ins_num)
+    shape = pred_label.shape
+    lab = pred_label.reshape(-1).to(torch.int64).contiguous()
+    conf = _lib.f32(pred_conf).reshape(-1)
+    gl = gt_label.reshape(-1).to(torch.int64).contiguous()
+    rows = gt_rows.reshape(-1).to(torch.int64).contiguous()
+    m = None if mask is None else _lib.f32(mask).reshape(-1)
+    N = lab.shape[0]
+    if conf.shape[0] != N or gl.shape[0] != N or (m is not None and m.shape[0] != N):
+        raise ValueError("ins_eval_device: pred_label, pred_conf, gt_label (and mask) must have one entry per pixel")
+    label, ap, matched, _ = _ins_eval_run(
+        N, ins_num, rows.shape[0], m is not None, lab.device,
+        lambda out: (None, 0, _lib.ptr(lab), _lib.ptr(conf), _lib.ptr(out), _lib.ptr(m), None, 0, _lib.ptr(gl), _lib.ptr(rows)))
+    return label.reshape(shape), ap, matched
+
+
+def ins_eval(pred_ins, gt_ins, gt_ins_num, ins_num, mask=None, check=None):
+    """``ins_eval(pred_ins, gt_ins, gt_ins_num, ins_num, mask)`` (networks/evaluator.py:125-175) on the device: ``pred_ins
+    [H, W, ins_num]`` (f32; rows may be strided, e.g. ``ins[..., :-1]``), the one-hot ``gt_ins [H, W, ins_num]`` (columns
+    ``< gt_ins_num``), the optional ``mask [H, W]``.  Returns ``(pred_label [H, W] int64 device tensor, ap: six floats,
+    return_labels: int64 numpy array [gt_ins_num], -1 for an unmatched row)`` -- one host synchronisation, for the returned values.
+
+    The counts behind the reference's ``[ins_num, ins_num, H W]`` broadcasts are formed in one pass over the frame; the
+    assignment is the criterion's solver (scipy's algorithm).  ``check=True`` raises ``ValueError`` when a pixel's
+    ``gt_ins[:gt_ins_num]`` is not one-hot (0 / 1 with at most one 1).  Where the reference raises because no predicted label is
+    valid, every row is unmatched and the APs are 0."""
+    for t in (pred_ins, gt_ins):
+        if not t.is_cuda:
+            _lib.require_gpu(t)                         # raises: no CPU fallback
+    _lib.require_gpu(mask)
+    p, N, ps = _rows_view(pred_ins)
+    g, Ng, gs = _rows_view(gt_ins)
+    ins_num, gt_num = int(ins_num), int(gt_ins_num)
+    if p.shape[-1] != ins_num or Ng != N:
+        raise ValueError("ins_eval: pred_ins must be [..., ins_num] and gt_ins one row per pixel")
+    if g.shape[-1] < gt_num:
+        raise ValueError("ins_eval: gt_ins has fewer than gt_ins_num columns")
+    m = None if mask is None else _lib.f32(mask).reshape(-1)
+    if m is not None and m.shape[0] != N:
+        raise ValueError("ins_eval: one mask entry per pixel")
+    label, ap, matched, work = _ins_eval_run(
+        N, ins_num, gt_num, m is not None, p.device,
+        lambda out: (_lib.ptr(p), ps, None, None, _lib.ptr(out), _lib.ptr(m), _lib.ptr(g), gs, None, None))
+    off = _lib.load().dmnerf_ins_eval_flags_offset(N, ins_num)
+    host = torch.cat([ap.double(), matched[:gt_num].double(), work[off:off + 4].view(torch.int32).double()]).cpu()   # the one sync
+    flags = int(host[-1])
+    if check and flags & IE_GT_NOT_ONEHOT:
+        raise ValueError(f"ins_eval: gt_ins[..., :{gt_num}] is not one-hot")
+    return label.reshape(pred_ins.shape[:-1]), [float(v) for v in host[:6]], host[6:6 + gt_num].numpy().astype("int64")

@@ -375,6 +375,41 @@ int dmnerf_exchanger(float* d_ori_raw, const float* const* h_tar_raws, const flo
  * d_conf [N] (nullable) = that maximum (np.max(pred_ins, -1)).                                                    */
 int dmnerf_ins_label_conf(const float* d_ins, int64_t N, int C, int64_t* d_label, float* d_conf, void* stream);
 
+/* ---- evaluator.py ins_eval + calculate_ap, the rest of it (networks/evaluator.py:77-175): instance AP of one frame ---------
+ * Replaces the host-side one-hot broadcast [ins_num, ins_num, H W] of hungarian (:55-70), the per-label np.median (:141-145),
+ * scipy's match (:43-47) and the AP integral (:77-122) with count-based kernels on the stream (csrc/ins_eval.hip).  ins_num
+ * <= 128, 0 <= gt_num <= ins_num.  No host synchronisation, no allocation; capturable.  The caller owns d_work
+ * (dmnerf_ins_eval_work_bytes; -1 for unsupported sizes); _prep clears what it needs, so one buffer serves any number of frames.
+ *
+ * _prep, one pass over the N pixels:
+ *   prediction: d_pred_ins (rows of pred_row_stride >= ins_num floats, first ins_num used: a view such as ins[..., :-1] needs no
+ *     copy) -> label = argmax (first maximum), conf = max (:127-137); or, with d_pred_ins NULL, d_label_in [N] int64 (in
+ *     [0, ins_num); others are flagged DMNERF_IE_LABEL_RANGE and join no count) with d_conf [N];
+ *   d_mask [N] (nullable, f32): label = ins_num where mask == 0 (:130-133);
+ *   d_label_out [N] int64 = the labels with the mask rule applied (may equal d_label_in: modified in place);
+ *   ground truth: d_gt_ins (rows of gt_row_stride >= gt_num floats, columns < gt_num one-hot; a row with another value or more
+ *     than one 1 sets DMNERF_IE_GT_NOT_ONEHOT) or, with d_gt_ins NULL, d_gt_label [N] int64 and d_gt_rows [gt_num] int64
+ *     ascending: a pixel whose label is d_gt_rows[g] belongs to row g, other pixels to no row.
+ * dmnerf_ins_eval then writes d_ap6 [6] f32 = calculate_ap(..., 'integral') at the thresholds 0.5 0.75 0.8 0.85 0.9 0.95, and
+ *   d_matched [ins_num] int64 = the returned labels (:169-173) of rows 0..gt_num-1, -1 for an unmatched row and beyond gt_num.
+ *   masked != 0: the call of _prep had a mask, and the largest label present is no channel (unique(pred_label)[:-1], :133).
+ * Cost entries: cost_siou from the exact counts in the reference's f32 order (bit-equal); cost_ce = 18.420681 x (pixels where
+ * the two one-hot maps differ) / N from the counts in f64, rounded once (the reference's last bit depends on ATen's summation
+ * order).  Ties of the confidences sort in index order.  No valid label (the reference raises at :172): every row unmatched.
+ * dmnerf_ins_eval_flags_offset: byte offset in d_work of the int32 DMNERF_IE_* word written by _prep;
+ * dmnerf_ins_eval_median_offset: of the f32 [ins_num] per-label median confidences written by dmnerf_ins_eval (0: no pixel). */
+#define DMNERF_IE_LABEL_RANGE 1
+#define DMNERF_IE_GT_NOT_ONEHOT 2
+int64_t dmnerf_ins_eval_work_bytes(int64_t N, int ins_num);
+int64_t dmnerf_ins_eval_flags_offset(int64_t N, int ins_num);
+int64_t dmnerf_ins_eval_median_offset(int64_t N, int ins_num);
+int dmnerf_ins_eval_prep(const float* d_pred_ins, int64_t pred_row_stride, const int64_t* d_label_in, const float* d_conf,
+                         int64_t* d_label_out, const float* d_mask, const float* d_gt_ins, int64_t gt_row_stride,
+                         const int64_t* d_gt_label, const int64_t* d_gt_rows, int gt_num, int64_t N, int ins_num,
+                         void* d_work, int64_t work_bytes, void* stream);
+int dmnerf_ins_eval(int64_t N, int ins_num, int gt_num, int masked, void* d_work, int64_t work_bytes, float* d_ap6,
+                    int64_t* d_matched, void* stream);
+
 /* ---- penalizer.py (the consumer of raw / z_vals / depth) ---------------------------
  * emptiness_penalizer (networks/penalizer.py:5-55) fused: _fwd writes per-ray partial sums
  * d_partials [N,4] (double): {sum BCE*w_before, sum m_before, sum loss_middle*w_middle, sum m_middle};
