@@ -147,6 +147,8 @@ SIGNATURES = {
     "dmnerf_ins_eval_median_offset": (c_i64, [c_i64, c_int]),
     "dmnerf_ins_eval_prep": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_int, c_vp, c_i64, c_vp]),
     "dmnerf_ins_eval": (c_int, [c_i64, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "dmnerf_img_metrics_work_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "dmnerf_img_metrics": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -488,7 +488,8 @@ def render_frame(H, W, K, c2w, models, near, far, args, chunk=4096, n_samples=64
     return fr.gather()
 
 
-def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, labels_only=False, gt_labels=None, **frame_kw):
+def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, labels_only=False, gt_labels=None,
+                image_metrics=False, **frame_kw):
     """The pose loop of ``render_test`` (networks/tester.py:55-90) without its file output and CPU metrics: every pose of
     ``render_poses [P,3or4,4]`` through ``render_frame`` (rows sharded over the ranks, chunks of ``args.N_test`` rays),
     the ScanNet ``crop_mask`` applied as the reference applies it (:78-82: the pixels with mask 1, reshaped to
@@ -504,7 +505,13 @@ def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, l
     and beyond the pose's row count: the data of ``matching_log.json``) and ``gt_num [P]``.  The rows are ``unique(gt_label)``, with
     ``crop_mask`` ``unique(gt_label)[:-1]`` and the mask ``gt_label < ins_num``, as in the two branches of the reference.  A pose
     without rows gets six APs of 1.0 (the reference appends ``tensor([1.0])`` there and fails later at tester.py:150).
-    ``labels_only=True`` is the cheap way to it: the AP needs only the label and the confidence of each pixel."""
+    ``labels_only=True`` is the cheap way to it: the AP needs only the label and the confidence of each pixel.
+
+    With ``image_metrics=True`` and ``gt_imgs``, also ``ssim [P]`` and ``psnr_f64 [P]`` (float64, on the device): the frame's
+    ``structural_similarity(..., multichannel=True, data_range=1)`` and ``peak_signal_noise_ratio(..., data_range=1)`` as
+    tester.py:89-90 computes them on a host copy (``evaluator.img_metrics_device``: one call for all poses after the loop, no
+    synchronisation; the scored frame is the cropped one in the ``crop_mask`` branch and must be at least 7 x 7).  ``psnr`` keeps
+    its float32 value.  The frames are complete on every rank, so every rank computes the same numbers; no collective is added."""
     H, W, K = hwk
     chunk = int(getattr(args, "N_test", 4096))
     n_samples = int(getattr(args, "N_samples", 64))
@@ -532,7 +539,37 @@ def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, l
             for name, t in zip(("ap", "matched", "gt_num"), _frame_ap(cols, gt_labels[i], crop_mask is not None, labels_only, args,
                                                                        frame_kw)):
                 cols.setdefault(name, []).append(t)
-    return {k: torch.stack(v, 0) for k, v in cols.items()}
+    out = {k: torch.stack(v, 0) for k, v in cols.items()}
+    if image_metrics and gt_imgs is not None and "rgb" in out:
+        from .networks import evaluator
+        gt = torch.stack([torch.as_tensor(gt_imgs[i]).to(out["rgb"]) for i in range(out["rgb"].shape[0])], 0)
+        out["ssim"], out["psnr_f64"] = evaluator.img_metrics_device(out["rgb"], gt)
+    return out
+
+
+def results_table(out, lpips=None):
+    """The array ``render_test`` hands to ``np.savetxt`` as ``test_results.txt`` (networks/tester.py:149-157) from a
+    ``render_path(..., gt_imgs=, gt_labels=, image_metrics=True)`` result: numpy float64 ``[P + 1, 9]`` with the columns PSNR, SSIM,
+    LPIPS, AP50, AP75, AP80, AP85, AP90, AP95, one row per pose and the column means as the last row.  LPIPS is not computed here
+    (its VGG weights are the reference's to load): the column is ``nan`` unless the caller passes its own ``lpips [P]``.  The one
+    host synchronisation of a whole test set."""
+    import numpy as np
+    for key in ("psnr_f64", "ssim", "ap"):
+        if key not in out:
+            raise ValueError(f"results_table: the result has no '{key}' (render_path(..., gt_imgs=, gt_labels=, image_metrics=True))")
+    dev = torch.cat([out["psnr_f64"].double().reshape(-1, 1), out["ssim"].double().reshape(-1, 1), out["ap"].double()], 1)
+    if dev.shape[1] != 8:
+        raise ValueError(f"results_table: ap must be [P, 6], got {tuple(out['ap'].shape)}")
+    host = dev.cpu().numpy()                            # the one sync
+    P = host.shape[0]
+    if lpips is None:
+        lp = np.full(P, np.nan)
+    else:
+        lp = np.asarray(lpips.detach().cpu() if isinstance(lpips, torch.Tensor) else lpips, dtype=np.float64).reshape(-1)
+    if lp.shape[0] != P:
+        raise ValueError(f"results_table: {lp.shape[0]} LPIPS values for {P} poses")
+    rows = np.concatenate([host[:, :2], lp[:, None], host[:, 2:]], 1)
+    return np.concatenate([rows, rows.mean(0, keepdims=True)], 0)
 
 
 def _frame_ap(cols, gt_label, crop, labels_only, args, frame_kw):
@@ -540,7 +577,7 @@ def _frame_ap(cols, gt_label, crop, labels_only, args, frame_kw):
     ``ins_eval_device``."""
     from .networks import evaluator
     if labels_only:
-        label, conf = cols["label"][-1], cols["conf"][-1]
+        label, conf = cols["label"][-1].contiguous(), cols["conf"][-1].contiguous()   # (views of the frame's packed output without a crop)
         ins_num = frame_kw.get("ins_num") or getattr(args, "ins_num", None)
         if ins_num is None:
             raise ValueError("render_path(gt_labels=...): pass ins_num= or set args.ins_num")

@@ -6,6 +6,8 @@ host for ``scipy.optimize.linear_sum_assignment`` and syncs twice per step (SURV
 the file runs on the device too: the per-pixel label / confidence every rendered frame needs (``ins_label_conf``) and the
 instance AP of a frame (``ins_eval``, ``ins_eval_device``: csrc/ins_eval.hip).  ``calculate_ap`` on its own has no device
 version: the AP integral is the last step of the ``ins_eval`` kernel, which works on counts, not on an IoU vector.
+The two image scores of ``render_test`` that the reference takes from ``skimage.metrics`` on a host copy of the frame
+(tester.py:89-90) are ``img_metrics_device`` / ``ssim`` / ``psnr`` (csrc/img_metrics.hip).
 """
 import torch
 
@@ -200,3 +202,61 @@ def ins_eval(pred_ins, gt_ins, gt_ins_num, ins_num, mask=None, check=None):
     if check and flags & IE_GT_NOT_ONEHOT:
         raise ValueError(f"ins_eval: gt_ins[..., :{gt_num}] is not one-hot")
     return label.reshape(pred_ins.shape[:-1]), [float(v) for v in host[:6]], host[6:6 + gt_num].numpy().astype("int64")
+
+
+def _img_metrics_run(pred, gt, with_channels=False):
+    """``dmnerf_img_metrics`` on ``pred, gt [P,H,W,C]``: ``(ssim [P], psnr [P], mse [P], ssim_ch [P,C] or None)``, f64 on the device."""
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"img_metrics: {name} must be a device tensor (there is no CPU path)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"img_metrics: {name} must be float32, got {t.dtype}")
+    if pred.shape != gt.shape or pred.dim() != 4 or pred.device != gt.device:
+        raise ValueError(f"img_metrics: pred and gt must share one [P,H,W,C] or [H,W,C] shape and device, got {tuple(pred.shape)} and "
+                         f"{tuple(gt.shape)}")
+    P, H, W, C = (int(s) for s in pred.shape)
+    if H < 7 or W < 7:
+        raise ValueError(f"img_metrics: win_size 7 exceeds the image extent {H} x {W}")
+    lib = _lib.load()
+    nbytes = lib.dmnerf_img_metrics_work_bytes(P, H, W, C)
+    if nbytes < 0:
+        raise ValueError(f"img_metrics: unsupported P={P} H={H} W={W} C={C} (C in 1..4, H, W <= 32768)")
+    pred, gt = pred.contiguous(), gt.contiguous()       # (the crop of render_path is a view)
+    dev = pred.device
+    work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    out = torch.empty(3, P, dtype=torch.float64, device=dev)
+    ch = torch.empty(P, C, dtype=torch.float64, device=dev) if with_channels else None
+    _lib.check(lib.dmnerf_img_metrics(_lib.ptr(pred), _lib.ptr(gt), P, H, W, C, _lib.ptr(work), nbytes, _lib.ptr(out[0]), _lib.ptr(ch),
+                                      _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream()), "dmnerf_img_metrics")
+    return out[0], out[2], out[1], ch
+
+
+def img_metrics_device(pred, gt):
+    """SSIM and PSNR of rendered frames as ``render_test`` scores them (networks/tester.py:89-90: ``skimage.metrics``'
+    ``structural_similarity(rgb, gt, multichannel=True, data_range=1)`` and ``peak_signal_noise_ratio(rgb, gt, data_range=1)``) on
+    the device (csrc/img_metrics.hip; float64 throughout, 7x7 uniform windows wholly inside the image, sample covariance).
+
+    ``pred, gt``: float32 device tensors ``[P,H,W,C]`` or ``[H,W,C]``, ``C`` in 1..4, ``H, W >= 7``; views are made contiguous.
+    Returns ``(ssim, psnr)``: float64 device tensors ``[P]``, or 0-d for the 3-d form.  No host synchronisation; capturable;
+    bit-identical from run to run and independent of ``P``.  What ``manipulate_frame`` returns goes in as it is."""
+    single = isinstance(pred, torch.Tensor) and pred.dim() == 3
+    if single and isinstance(gt, torch.Tensor) and gt.dim() == 3:
+        pred, gt = pred[None], gt[None]
+    ssim_, psnr_, _, _ = _img_metrics_run(pred, gt)
+    return (ssim_[0], psnr_[0]) if single else (ssim_, psnr_)
+
+
+def ssim(pred, gt):
+    """``structural_similarity(pred, gt, multichannel=True, data_range=1)`` of one ``[H,W,C]`` frame (tester.py:90) as a Python
+    float: ``img_metrics_device`` plus one synchronisation."""
+    if pred.dim() != 3:
+        raise ValueError("ssim: one [H,W,C] frame")
+    return float(img_metrics_device(pred, gt)[0])
+
+
+def psnr(pred, gt):
+    """``peak_signal_noise_ratio(pred, gt, data_range=1)`` of one ``[H,W,C]`` frame (tester.py:89) as a Python float (``inf`` for
+    identical frames): ``img_metrics_device`` plus one synchronisation."""
+    if pred.dim() != 3:
+        raise ValueError("psnr: one [H,W,C] frame")
+    return float(img_metrics_device(pred, gt)[1])

@@ -410,6 +410,26 @@ int dmnerf_ins_eval_prep(const float* d_pred_ins, int64_t pred_row_stride, const
 int dmnerf_ins_eval(int64_t N, int ins_num, int gt_num, int masked, void* d_work, int64_t work_bytes, float* d_ap6,
                     int64_t* d_matched, void* stream);
 
+/* ---- the image scores of render_test / manipulator_eval (networks/tester.py:89-90, networks/manipulator.py:277-278) ----------
+ * Replaces skimage.metrics.peak_signal_noise_ratio(rgb.cpu().numpy(), gt, data_range=1) and
+ * skimage.metrics.structural_similarity(rgb.cpu().numpy(), gt, multichannel=True, data_range=1): a device-to-host copy of the
+ * frame, a synchronisation and ~0.2 s of host filtering per 480x640 pose.  csrc/img_metrics.hip scores P frame pairs on the
+ * stream: d_pred, d_gt [P,H,W,C] f32 contiguous, C in 1..4, H, W >= 7 (and <= 32768).
+ * SSIM as scikit-image 0.18 documents it for these arguments -- written down without the library at hand, see the kernel file's
+ * header -- in float64 throughout: per channel the 7x7 box means ux, uy, uxx, uyy, uxy of x, y, x x, y y, x y; vx = 49/48 (uxx -
+ * ux ux), vy, vxy likewise (sample covariance); C1 = 1e-4, C2 = 9e-4;
+ *     S = ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2));
+ * the map is cropped by 3 on every side, so only the (H-6)(W-6) windows wholly inside the image count and there is no border
+ * rule; d_ssim_ch [P,C] (nullable) = the per-channel means of S, d_ssim [P] = their mean over the channels (summed in channel
+ * order, divided by C).  d_mse [P] = mean of (x - y)^2 with the difference and the square in f32 and the sum in f64, d_psnr [P] =
+ * 10 log10(1 / mse) in f64, +inf for mse == 0.  A NaN in a frame makes that frame's outputs NaN and touches no other frame.
+ * Every 7-tap sum is formed directly; the per-workgroup partials in d_work (dmnerf_img_metrics_work_bytes; -1 for unsupported
+ * sizes) are added in index order by a second launch, with no floating-point atomic: results are bit-identical from run to run
+ * and independent of P.  No host synchronisation, no allocation; capturable.  P == 0 is a successful no-op.               */
+int64_t dmnerf_img_metrics_work_bytes(int P, int H, int W, int C);
+int dmnerf_img_metrics(const float* d_pred, const float* d_gt, int P, int H, int W, int C, void* d_work, int64_t work_bytes,
+                       double* d_ssim, double* d_ssim_ch, double* d_mse, double* d_psnr, void* stream);
+
 /* ---- penalizer.py (the consumer of raw / z_vals / depth) ---------------------------
  * emptiness_penalizer (networks/penalizer.py:5-55) fused: _fwd writes per-ray partial sums
  * d_partials [N,4] (double): {sum BCE*w_before, sum m_before, sum loss_middle*w_middle, sum m_middle};
