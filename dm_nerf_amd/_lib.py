@@ -31,6 +31,18 @@ class RenderArgs(ctypes.Structure):
     ]
 
 
+class RenderFineArgs(ctypes.Structure):
+    """``dmnerf_render_fine_args`` (include/dmnerf_hip.h)."""
+    _fields_ = [
+        ("d_blob_coarse", c_vp), ("d_blob_fine", c_vp), ("ins_num", c_int),
+        ("d_rays_o", c_vp), ("d_rays_d", c_vp), ("d_z_in", c_vp), ("d_t_rand", c_vp), ("d_u", c_vp),
+        ("u_row_stride", c_i64), ("N", c_i64), ("S", c_int), ("n_imp", c_int),
+        ("d_z_coarse", c_vp), ("d_sigma_ws", c_vp), ("d_weights_ws", c_vp),
+        ("d_z_fine", c_vp), ("d_raw_fine", c_vp), ("d_rgb_fine", c_vp), ("d_depth_fine", c_vp), ("d_ins_fine", c_vp),
+        ("ev_fine_mlp_begin", c_vp), ("ev_fine_mlp_end", c_vp), ("fused_heads", c_int),
+    ]
+
+
 class RepackModel(ctypes.Structure):
     """``dmnerf_repack_model`` (include/dmnerf_hip.h)."""
     _fields_ = [("d_params_flat", c_vp), ("ins_num", c_int), ("d_flat_copy", c_vp), ("d_idx", c_vp), ("d_blob", c_vp),
@@ -67,6 +79,9 @@ SIGNATURES = {
     "dmnerf_mlp_fwd_rays": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "dmnerf_composite_fwd": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_render_rays_fwd": (c_int, [ctypes.POINTER(RenderArgs), c_vp]),
+    "dmnerf_mlp_fwd_rays_density": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
+    "dmnerf_weights_from_sigma": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
+    "dmnerf_render_rays_fwd_fine": (c_int, [ctypes.POINTER(RenderFineArgs), c_vp]),
     "dmnerf_composite_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
     "dmnerf_train_save_floats": (c_i64, [c_i64]),
     "dmnerf_mlp_fwd_embedded_train": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),

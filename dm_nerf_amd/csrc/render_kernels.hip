@@ -171,18 +171,12 @@ __device__ __forceinline__ float* ray_row(float* base, int k, int wv, int SP) { 
 inline size_t ray_lds_bytes(int rows, int S, int C) { return (size_t)rows * RAYS_PER_BLOCK * ray_row_len(S, C) * sizeof(float); }
 constexpr size_t RAY_LDS_MAX = (size_t)4 * RAYS_PER_BLOCK * MAX_S * sizeof(float);      // 80 KiB: four rows at MAX_S
 
-// (one ray = one wave; returns the ray's depth, the same float in every lane)
-__device__ __forceinline__ float composite_ray(
-    const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays_d, int64_t n, int lane,
-    int S, int C, int n_ins, float* __restrict__ rgb_map, float* __restrict__ weights, float* __restrict__ depth_map,
-    float* __restrict__ ins_map, float* wl) {
-    const int ch = 4 + C;
-    const float* __restrict__ rr = raw + n * (int64_t)S * ch;
-    const float* __restrict__ zr = z + n * (int64_t)S;
-
-    const float dx = rays_d[n * 3 + 0], dy = rays_d[n * 3 + 1], dz = rays_d[n * 3 + 2];
-    const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);            // torch.norm(rays_d[..., None, :], dim=-1)
-
+// The compositing weights of one ray (render.py:6-20), one wave per ray: alpha from the density channel, the exclusive product
+// scan in double, w = alpha T.  sig[s * sig_stride] = the density of sample s (raw rows: stride 4 + C; a compact sigma row: 1).
+// Writes weights_row[s] and, when wl is non-null, the same value to the wave's LDS row.  Returns this lane's partial of
+// sum_s w_s z_s (double), for the depth map.
+__device__ __forceinline__ double ray_weights(const float* __restrict__ sig, int sig_stride, const float* __restrict__ zr, float nrm,
+                                              int lane, int S, float* __restrict__ weights_row, float* wl) {
     double carry = 1.0;            // prod of (1 - alpha + 1e-10) over all earlier samples
     double depth_acc = 0.0;
     for (int base = 0; base < S; base += WAVE) {
@@ -193,8 +187,8 @@ __device__ __forceinline__ float composite_ray(
             zc = zr[s];
             float dist = (s == S - 1) ? 1e10f : zr[s + 1] - zc;
             dist = dist * nrm;
-            const float sig = fmaxf(rr[(int64_t)s * ch + 3], 0.f);    // F.relu
-            alpha = 1.f - expf(-sig * dist);
+            const float sg = fmaxf(sig[(int64_t)s * sig_stride], 0.f);    // F.relu
+            alpha = 1.f - expf(-sg * dist);
             f = (1.f - alpha) + 1e-10f;
         }
         // exclusive cumprod; ATen's CPU cumprod accumulates in double and rounds each element
@@ -204,12 +198,30 @@ __device__ __forceinline__ float composite_ray(
         const float T = (float)(carry * excl);
         const float w = alpha * T;
         if (ok) {
-            wl[s] = w;
-            weights[n * (int64_t)S + s] = w;
+            if (wl) wl[s] = w;
+            weights_row[s] = w;
             depth_acc += (double)(w * zc);
         }
         carry = carry * shfl_d(incl, WAVE - 1);
     }
+    return depth_acc;
+}
+
+__device__ __forceinline__ float ray_dir_norm(const float* __restrict__ rays_d, int64_t n) {
+    const float dx = rays_d[n * 3 + 0], dy = rays_d[n * 3 + 1], dz = rays_d[n * 3 + 2];
+    return sqrtf(dx * dx + dy * dy + dz * dz);                       // torch.norm(rays_d[..., None, :], dim=-1)
+}
+
+// (one ray = one wave; returns the ray's depth, the same float in every lane)
+__device__ __forceinline__ float composite_ray(
+    const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays_d, int64_t n, int lane,
+    int S, int C, int n_ins, float* __restrict__ rgb_map, float* __restrict__ weights, float* __restrict__ depth_map,
+    float* __restrict__ ins_map, float* wl) {
+    const int ch = 4 + C;
+    const float* __restrict__ rr = raw + n * (int64_t)S * ch;
+    const float* __restrict__ zr = z + n * (int64_t)S;
+
+    double depth_acc = ray_weights(rr + 3, ch, zr, ray_dir_norm(rays_d, n), lane, S, weights + n * (int64_t)S, wl);
     depth_acc = wave_sum_d(depth_acc);
     const float depth_f = (float)depth_acc;
     if (lane == 0) depth_map[n] = depth_f;
@@ -274,6 +286,18 @@ __global__ __launch_bounds__(WAVE* RAYS_PER_BLOCK) void composite_kernel(
     const int64_t n = (int64_t)blockIdx.x * RAYS_PER_BLOCK + wv;
     if (n >= N) return;
     composite_ray(raw, z, rays_d, n, lane, S, C, n_ins, rgb_map, weights, depth_map, ins_map, ray_row(ray_lds, 0, wv, ray_row_len(S, C)));
+}
+
+// The weights alone, from a compact density row: what the coarse level of an inference render hands to the resampling step
+// (render.py:66-70) when nobody reads its maps.  sigma [N,S] (dmnerf_mlp_fwd_rays_density) -> weights [N,S], the floats
+// composite_kernel writes for raw[..., 3] = sigma.
+__global__ __launch_bounds__(WAVE* RAYS_PER_BLOCK) void weights_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ z, const float* __restrict__ rays_d, int64_t N, int S,
+    float* __restrict__ weights) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t n = (int64_t)blockIdx.x * RAYS_PER_BLOCK + wv;
+    if (n >= N) return;
+    (void)ray_weights(sigma + n * (int64_t)S, 1, z + n * (int64_t)S, ray_dir_norm(rays_d, n), lane, S, weights + n * (int64_t)S, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -844,6 +868,16 @@ extern "C" int dmnerf_composite_fwd(const float* d_raw, const float* d_z, const 
     hipLaunchKernelGGL(composite_kernel, dim3(blocks_for(N, RAYS_PER_BLOCK)), dim3(WAVE * RAYS_PER_BLOCK), ray_lds_bytes(1, S, C), (hipStream_t)stream,
                        d_raw, d_z, d_rays_d, N, S, C, C - 1, d_rgb_map, d_weights, d_depth_map, d_ins_map);
     return dmn_check_launch("composite_fwd");
+}
+
+extern "C" int dmnerf_weights_from_sigma(const float* d_sigma, const float* d_z, const float* d_rays_d, int64_t N, int S,
+                                         float* d_weights, void* stream) {
+    if (N < 0 || S < 1 || S > MAX_S) return dmn_fail(DMNERF_E_ARG, "weights_from_sigma: bad N=%lld S=%d (max %d)", (long long)N, S, MAX_S);
+    if (N == 0) return DMNERF_OK;
+    if (!d_sigma || !d_z || !d_rays_d || !d_weights) return dmn_fail(DMNERF_E_ARG, "weights_from_sigma: null pointer");
+    hipLaunchKernelGGL(weights_kernel, dim3(blocks_for(N, RAYS_PER_BLOCK)), dim3(WAVE * RAYS_PER_BLOCK), 0, (hipStream_t)stream,
+                       d_sigma, d_z, d_rays_d, N, S, d_weights);
+    return dmn_check_launch("weights_from_sigma");
 }
 
 extern "C" int dmnerf_manipulator_render(const float* d_raw, const float* d_z, const float* d_rays_d, int64_t N,

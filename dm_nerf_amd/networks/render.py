@@ -171,3 +171,70 @@ def dm_nerf(rays, position_embedder, view_embedder, model_coarse, model_fine, z_
         out['ins_fine'] = out['ins_fine'][-args.N_ins:]          # render.py:88-90
         out['ins_coarse'] = out['ins_coarse'][-args.N_ins:]
     return out
+
+
+def _training(model_coarse, model_fine):
+    return torch.is_grad_enabled() and any(p.requires_grad for m in (model_coarse, model_fine) for p in m.parameters())
+
+
+def fine_eligible(model_coarse, model_fine, args):
+    """Can ``dm_nerf_fine`` serve this call?  Inference, the shipped 8 x 256 network in both models, hierarchical sampling on,
+    and the f32 kernels (the split-operand modes have no density-only variant)."""
+    return (not _training(model_coarse, model_fine) and model_coarse._fused_ok() and model_fine._fused_ok()
+            and int(args.N_importance) >= 1 and not weights.split_mode(args))
+
+
+def dm_nerf_fine(rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args,
+                 t_rand=None, u=None, _events=None):
+    """``dm_nerf`` for a caller that keeps the fine level only, as ``render_test`` does (networks/tester.py:71-77 reads
+    ``rgb_fine``, ``ins_fine``, ``depth_fine``): returns ``{'rgb_fine', 'ins_fine', 'depth_fine', 'z_vals_fine', 'raw_fine'}``,
+    each ``torch.equal`` to the same key of ``dm_nerf`` called with the same arguments and draws.
+
+    Of the coarse level only the compositing weights reach the fine one (render.py:66-70) and they depend on the density alone
+    (:6-20), so the coarse network is evaluated up to ``density_linear`` (``dmnerf_mlp_fwd_rays_density``): no heads, no
+    ``raw_coarse``, no coarse maps -- 29 % fewer MFMAs in that launch.  Arguments, validation and the order of the RNG draws are
+    ``dm_nerf``'s.  Only for calls that are ``fine_eligible``; anything else raises (there is no silent detour)."""
+    if not fine_eligible(model_coarse, model_fine, args):
+        raise ValueError("dm_nerf_fine: inference with the 8 x 256 network, N_importance >= 1 and no args.mfma_split only -- use dm_nerf")
+    for emb, want in ((position_embedder, model_fine.input_ch_pts), (view_embedder, model_fine.input_ch_views)):
+        if getattr(emb, "out_dim", want) != want:
+            raise ValueError("dm_nerf: the embedders' out_dim does not match the models' input channels")
+    rays_o, rays_d = rays
+    rays_o, rays_d = _lib.f32(rays_o.reshape(-1, 3)), _lib.f32(rays_d.reshape(-1, 3))
+    z_in = _lib.f32(z_vals_coarse)
+    _lib.require_gpu(rays_o, rays_d, z_in)
+    dev = rays_o.device
+    N, S = z_in.shape
+    n_imp = int(args.N_importance)
+    ins_num = model_fine.ins_num
+    C = ins_num + 1
+    t_rand, u, u_stride = check_draws(t_rand, u, N, S, n_imp, float(args.perturb), dev)
+    SF = S + n_imp
+    f = dict(dtype=torch.float32, device=dev)
+    out = {'rgb_fine': torch.empty(N, 3, **f), 'ins_fine': torch.empty(N, C - 1, **f), 'depth_fine': torch.empty(N, **f),
+           'z_vals_fine': torch.empty(N, SF, **f), 'raw_fine': torch.empty(N, SF, 4 + C, **f)}
+    z_c = torch.empty(N, S, **f) if t_rand is not None else z_in     # without jitter the coarse grid is read in place
+    sigma, ws = torch.empty(N, S, **f), torch.empty(N, SF, **f)
+    fused = bool(getattr(args, "fuse_heads", False))
+    pick = (lambda mdl: mdl.blob_fused()) if fused else (lambda mdl: mdl.blob())
+    a = _lib.RenderFineArgs()
+    a.fused_heads = 1 if fused else 0
+    a.d_blob_coarse = pick(model_coarse).data_ptr()                  # (the trunk and its table entries are the same in both blobs)
+    a.d_blob_fine = pick(model_fine).data_ptr()
+    a.ins_num = ins_num
+    a.d_rays_o, a.d_rays_d, a.d_z_in = rays_o.data_ptr(), rays_d.data_ptr(), z_in.data_ptr()
+    a.d_t_rand = t_rand.data_ptr() if t_rand is not None else None
+    a.d_u, a.u_row_stride = u.data_ptr(), u_stride
+    a.N, a.S, a.n_imp = N, S, n_imp
+    a.d_z_coarse, a.d_sigma_ws, a.d_weights_ws = z_c.data_ptr(), sigma.data_ptr(), ws.data_ptr()
+    a.d_z_fine, a.d_raw_fine = out['z_vals_fine'].data_ptr(), out['raw_fine'].data_ptr()
+    a.d_rgb_fine, a.d_depth_fine = out['rgb_fine'].data_ptr(), out['depth_fine'].data_ptr()
+    a.d_ins_fine = out['ins_fine'].data_ptr()
+    if _events is not None:          # (begin, end) torch.cuda.Event pair around the fine-network MLP kernel
+        for e in _events:
+            e.record()               # torch creates the hipEvent_t lazily; the library re-records it in place
+        a.ev_fine_mlp_begin, a.ev_fine_mlp_end = _events[0].cuda_event, _events[1].cuda_event
+    _lib.check(_lib.load().dmnerf_render_rays_fwd_fine(ctypes.byref(a), _lib.stream()), "dmnerf_render_rays_fwd_fine")
+    if getattr(args, "is_train", False) and getattr(args, "N_ins", None) is not None:
+        out['ins_fine'] = out['ins_fine'][-args.N_ins:]          # render.py:88-90
+    return out

@@ -504,6 +504,51 @@ typedef struct {
 } dmnerf_render_args;
 int dmnerf_render_rays_fwd(const dmnerf_render_args* args, void* stream);
 
+/* The same render for a caller that keeps only the fine outputs -- render_test (networks/tester.py:71-77) takes rgb_fine, ins_fine
+ * and depth_fine from the dict and drops the rest.  Of the coarse level only the compositing weights reach the fine one
+ * (networks/render.py:66-70), and they depend on the density channel alone (:6-20), so the coarse network runs as far as
+ * density_linear and no further; every fine output is bit-identical to dmnerf_render_rays_fwd's.  Additive: the struct above and
+ * dmnerf_render_rays_fwd are unchanged.
+ *   dmnerf_mlp_fwd_rays_density: render.py:49-61 + DM_NeRF.forward up to density_linear (networks/dm_nerf.py:80-88,101):
+ *     sigma [N,S] = raw[..., 3] of dmnerf_mlp_fwd_rays, bit for bit; d_blob: the forward blob (dmnerf_build_pack_index) or the
+ *     fused-heads blob (dmnerf_build_pack_index_fused) -- the trunk and the table entries used are the same in both.
+ *   dmnerf_weights_from_sigma: the weights of render_train (render.py:6-20) from that row: weights [N,S] = what
+ *     dmnerf_composite_fwd writes for raw[..., 3] = sigma.
+ *   dmnerf_render_rays_fwd_fine: jitter / z copy, density-only coarse, weights, resample + merge (render.py:66-70), the full fine
+ *     network and its compositing (render.py:71-86).  fused_heads: 0 or 1 (the f32 blobs; the split-operand blobs are refused).
+ *     d_z_coarse may alias d_z_in when d_t_rand is NULL.  Scratch: d_sigma_ws [N,S], d_weights_ws [N,S+n_imp].              */
+int dmnerf_mlp_fwd_rays_density(const float* d_blob, int ins_num, const float* d_rays_o, const float* d_rays_d,
+                                const float* d_z, int64_t N, int S, float* d_sigma, void* stream);
+int dmnerf_weights_from_sigma(const float* d_sigma, const float* d_z, const float* d_rays_d, int64_t N, int S,
+                              float* d_weights, void* stream);
+typedef struct {
+    const float* d_blob_coarse;
+    const float* d_blob_fine;
+    int ins_num;
+    const float* d_rays_o;
+    const float* d_rays_d;
+    const float* d_z_in;        /* [N,S] coarse depths before jitter */
+    const float* d_t_rand;      /* nullable */
+    const float* d_u;
+    int64_t u_row_stride;
+    int64_t N;
+    int S;
+    int n_imp;
+    float* d_z_coarse;          /* [N,S]        jittered coarse depths (workspace) */
+    float* d_sigma_ws;          /* scratch [N,S] */
+    float* d_weights_ws;        /* scratch [N,S+n_imp] */
+    /* outputs */
+    float* d_z_fine;            /* [N,S+n_imp]  'z_vals_fine'  */
+    float* d_raw_fine;          /* [N,S+n_imp,4+C] 'raw_fine'  */
+    float* d_rgb_fine;          /* [N,3]        'rgb_fine'     */
+    float* d_depth_fine;        /* [N]          'depth_fine'   */
+    float* d_ins_fine;          /* [N,C-1]      'ins_fine'     */
+    void* ev_fine_mlp_begin;    /* as in dmnerf_render_args */
+    void* ev_fine_mlp_end;
+    int fused_heads;            /* 0 / 1 */
+} dmnerf_render_fine_args;
+int dmnerf_render_rays_fwd_fine(const dmnerf_render_fine_args* args, void* stream);
+
 /* ---- network shapes other than D = 8, W = 256, multires 10 / 4 (config.py:126-138 passes args.netdepth / netwidth /
  * multires* through; no shipped config changes them): the layer-by-layer path of csrc/generic.hip.  One strided f32-MFMA
  * GEMM serves the three products of a linear layer; the Python mirror (dm_nerf_amd/generic.py) chains them as
