@@ -82,6 +82,8 @@ SIGNATURES = {
     "dmnerf_mlp_fwd_rays_density": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "dmnerf_weights_from_sigma": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "dmnerf_render_rays_fwd_fine": (c_int, [ctypes.POINTER(RenderFineArgs), c_vp]),
+    "dmnerf_mlp_fwd_points_density": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_float, c_vp]),
+    "dmnerf_occupancy_slab": (c_int, [c_vp, c_int, c_vp, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_i64, c_i64, c_vp, c_float, c_vp]),
     "dmnerf_composite_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
     "dmnerf_train_save_floats": (c_i64, [c_i64]),
     "dmnerf_mlp_fwd_embedded_train": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),

@@ -549,6 +549,25 @@ typedef struct {
 } dmnerf_render_fine_args;
 int dmnerf_render_rays_fwd_fine(const dmnerf_render_fine_args* args, void* stream);
 
+/* The density of the field off the rays: what mesh_main (tools/mesh_generator.py:12-143) asks the fine network for (csrc/mlp_fwd_points.hip).
+ * Both entries run dmnerf_mlp_fwd_rays_density's body -- encoding, trunk, density_linear; no direction, no heads -- so sigma is
+ * raw[..., 3] of the full network bit for bit, and both take the forward blob or the fused-heads blob.  Neither allocates nor
+ * synchronises.  voxel < 0: d_out [M] = sigma.  voxel >= 0: d_out [M] = 1 - exp(-relu(sigma) * voxel), occupancy_activation of
+ * mesh_generator.py:54-60 with distances = voxel, full-precision exp.  Additive (the ABI version stays).
+ *   dmnerf_mlp_fwd_points_density: d_pts [M,3] contiguous.  Replaces mesh_generator.py:36-51 for one chunk: embed(in_pcd) |
+ *     embed(zeros) -> model_fine(embedded)[..., 3], without the [n, 90] tensor.
+ *   dmnerf_occupancy_slab: samples [m0, m0 + M) of a dim^3 grid, flattened as reshape(-1, 3) flattens it (g = (i * dim + j) * dim + k);
+ *     sample g computes its own point and no point tensor exists.  Replaces mesh_generator.py:27-31 (grid_within_bound,
+ *     tools/visualizer.py:111-155, then the axis swap) and :36-63 for the slab.  d_t [dim] = torch.linspace(lo, hi, dim) as the host
+ *     evaluates it; scale [3] = float32(extents / (hi - lo)) and transform [12] = rows 0..2 of the 4 x 4 scene transform, row-major
+ *     (R_r0 R_r1 R_r2 T_r) -- HOST pointers, copied into the kernel arguments.  x = t[i] s0, y = t[j] s1, z = t[k] s2,
+ *     q_r = ((R_r0 x + R_r1 y) + R_r2 z) + T_r with every product and sum rounded to f32 on its own (the reference's unfused torch
+ *     ops), point = (q_0, -q_2, q_1).  1 <= dim <= 1024; 0 <= m0, m0 + M <= dim^3.                                              */
+int dmnerf_mlp_fwd_points_density(const float* d_blob, int ins_num, const float* d_pts, int64_t M, float* d_out, float voxel,
+                                  void* stream);
+int dmnerf_occupancy_slab(const float* d_blob, int ins_num, const float* d_t, int dim, const float* scale, const float* transform,
+                          int64_t m0, int64_t M, float* d_out, float voxel, void* stream);
+
 /* ---- network shapes other than D = 8, W = 256, multires 10 / 4 (config.py:126-138 passes args.netdepth / netwidth /
  * multires* through; no shipped config changes them): the layer-by-layer path of csrc/generic.hip.  One strided f32-MFMA
  * GEMM serves the three products of a linear layer; the Python mirror (dm_nerf_amd/generic.py) chains them as
