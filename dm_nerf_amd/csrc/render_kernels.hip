@@ -12,6 +12,7 @@
 #include "../../include/dmnerf_hip.h"
 #include "common.h"
 #include "mlp_common.h"
+#include "raygen.h"
 
 namespace {
 
@@ -74,9 +75,7 @@ __device__ __forceinline__ float sigmoidf_ref(float x) { return 1.f / (1.f + exp
 // get_rays_k  (networks/helpers.py:50-61)
 // ------------------------------------------------------------------------------------------
 struct RaygenArgs {
-    float fx, fy, cx, cy, k22;
-    float r[9];      // c2w[:3,:3] row-major
-    float t[3];      // c2w[:3,3]
+    RaygenCam cam;   // raygen.h
     int W, row0;
     int64_t n;       // rays to generate
     float* rays_o;
@@ -86,19 +85,7 @@ struct RaygenArgs {
 __global__ void raygen_kernel(const RaygenArgs a) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.n) return;
-    const int col = (int)(idx % a.W);
-    const int row = a.row0 + (int)(idx / a.W);
-    const float i = (float)col, j = (float)row;          // linspace(0, W-1, W) is exactly 0,1,2,...
-    const float d0 = (i - a.cx) / a.fx;
-    const float d1 = (j - a.cy) / a.fy;
-    const float d2 = a.k22 * 1.0f;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        // torch.sum(dirs[..., None, :] * c2w[:3,:3], -1): sequential over the 3 products
-        const float v = (d0 * a.r[3 * r + 0] + d1 * a.r[3 * r + 1]) + d2 * a.r[3 * r + 2];
-        a.rays_d[idx * 3 + r] = v;
-        a.rays_o[idx * 3 + r] = a.t[r];
-    }
+    dmn_raygen_ray(a.cam, (int)(idx % a.W), a.row0 + (int)(idx / a.W), a.rays_o + idx * 3, a.rays_d + idx * 3);
 }
 
 // rays of selected pixels only (get_select_full, helpers.py:99-111: flat index k -> row k / W, col k % W)
@@ -106,15 +93,7 @@ __global__ void raygen_select_kernel(const RaygenArgs a, const int64_t* __restri
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= a.n) return;
     const int64_t k = idx[t];
-    const float i = (float)(int)(k % a.W), j = (float)(int)(k / a.W);
-    const float d0 = (i - a.cx) / a.fx;
-    const float d1 = (j - a.cy) / a.fy;
-    const float d2 = a.k22 * 1.0f;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        a.rays_d[t * 3 + r] = (d0 * a.r[3 * r + 0] + d1 * a.r[3 * r + 1]) + d2 * a.r[3 * r + 2];
-        a.rays_o[t * 3 + r] = a.t[r];
-    }
+    dmn_raygen_ray(a.cam, (int)(k % a.W), (int)(k / a.W), a.rays_o + t * 3, a.rays_d + t * 3);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -821,11 +800,7 @@ extern "C" int dmnerf_raygen(int H, int W, const float* h_intr, const float* h_c
         return dmn_fail(DMNERF_E_ARG, "raygen: rows [%d,%d) outside image %dx%d", row0, row0 + nrows, H, W);
     if (nrows == 0) return DMNERF_OK;
     RaygenArgs a;
-    a.fx = h_intr[0]; a.fy = h_intr[1]; a.cx = h_intr[2]; a.cy = h_intr[3]; a.k22 = h_intr[4];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) a.r[3 * r + c] = h_c2w[4 * r + c];
-        a.t[r] = h_c2w[4 * r + 3];
-    }
+    a.cam = dmn_raygen_cam(h_intr, h_c2w);
     a.W = W; a.row0 = row0; a.n = (int64_t)nrows * W; a.rays_o = d_rays_o; a.rays_d = d_rays_d;
     hipLaunchKernelGGL(raygen_kernel, dim3(blocks_for(a.n, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return dmn_check_launch("raygen");
@@ -1074,11 +1049,7 @@ extern "C" int dmnerf_raygen_select(int H, int W, const float* h_intr, const flo
     if (n == 0) return DMNERF_OK;
     if (!h_intr || !h_c2w || !d_idx || !d_rays_o || !d_rays_d) return dmn_fail(DMNERF_E_ARG, "raygen_select: null pointer");
     RaygenArgs a;
-    a.fx = h_intr[0]; a.fy = h_intr[1]; a.cx = h_intr[2]; a.cy = h_intr[3]; a.k22 = h_intr[4];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) a.r[3 * r + c] = h_c2w[4 * r + c];
-        a.t[r] = h_c2w[4 * r + 3];
-    }
+    a.cam = dmn_raygen_cam(h_intr, h_c2w);
     a.W = W; a.row0 = 0; a.n = n; a.rays_o = d_rays_o; a.rays_d = d_rays_d;
     hipLaunchKernelGGL(raygen_select_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, a, d_idx);
     return dmn_check_launch("raygen_select");

@@ -623,6 +623,28 @@ def _default_draws(n, n_imp, count, device):
     return [torch.rand([n, n_imp], device=device) for _ in range(count)]
 
 
+def _default_target_rays(H, W, K, poses, kinds, offsets, row0, nrows):
+    from . import editing
+    return editing.edit_rays(H, W, K, poses, kinds, offsets, row0=row0, nrows=nrows)
+
+
+def _target_rays_from(raygen):
+    """``target_rays`` built on an injected ``raygen`` (CPU / gloo tests): the rays of each pose, a deformed object's origin x
+    plus its row's offset as the reference forms it (manipulator.py:428: f32 column + f64 tensor, rounded once).  The rows are
+    the band's ABSOLUTE image rows."""
+    def target_rays(H, W, K, poses, kinds, offsets, row0, nrows):
+        tars = []
+        for t, (pose, kind) in enumerate(zip(poses, kinds)):
+            to, td = raygen(H, W, K, pose, row0, nrows)
+            to, td = to.reshape(-1, 3).clone(), td.reshape(-1, 3)
+            if kind:
+                off = torch.from_numpy(offsets[t, row0:row0 + nrows].copy()).to(to.device).repeat_interleave(int(W))
+                to[:, 0] = to[:, 0] + off
+            tars.append(torch.stack([to, td]))
+        return torch.stack(tars)
+    return target_rays
+
+
 class ManipulationFrameRenderer:
     """One pose of the manipulation render, rows sharded over the ranks: the per-pose body of ``manipulator_eval``
     (networks/manipulator.py:232-270) -- original rays of ``ori_pose``, target rays of ``trans @ ori_pose``, the chunk loop around
@@ -630,7 +652,10 @@ class ManipulationFrameRenderer:
 
     * rank r owns a contiguous band of image rows and generates the original AND the ``T = len(trans_list)`` target rays of that
       band itself (raygen kernel, no scatter; the reference evaluates one transformation per call, ``trans_list`` generalises it
-      the way ``manipulator()``'s ``f_tar_rays`` list does);
+      the way ``manipulator()``'s ``f_tar_rays`` list does).  An entry of ``trans_list`` may also be an ``editing.Deform``
+      (``manipulator_demo``'s deformations, :397-429): that object's target rays are the ORIGINAL pose's with the origin's x shifted
+      by a per-image-row offset.  With any ``Deform`` present all target rays come from ONE launch of ``dmnerf_edit_rays``, the
+      offset table indexed by the absolute image row; with matrices only nothing changes;
     * the chunks are those of the WHOLE frame -- ``[c N_test, (c + 1) N_test)``, ragged last chunk (:241-244) -- and a rank renders
       the part of each chunk that falls into its band.  ``step(c)`` makes, on EVERY rank, the ``2 + T`` draws
       ``torch.rand([chunk rays, N_importance])`` that ``manipulator()`` makes for chunk c in a single process (it resamples with
@@ -641,12 +666,13 @@ class ManipulationFrameRenderer:
       (C = ins_num + 1: the manipulation render keeps the last object channel, :101-102), and ``gather()`` is ONE all-gather per
       frame.
 
-    ``manipulate_chunk(ori_rays [2,n,3], tar_rays [T,2,n,3], models, args, us)`` and ``raygen`` / ``draws`` are injectable
+    ``manipulate_chunk(ori_rays [2,n,3], tar_rays [T,2,n,3], models, args, us)``, ``raygen`` / ``draws`` and
+    ``target_rays(H, W, K, poses, kinds, offsets [T,H] float64, row0, nrows) -> [T,2,n,3]`` are injectable
     (CPU / gloo tests of the sharding logic); ``rank=`` / ``world=`` override the process group's view for the band arithmetic
     (a single process can then render band r of N, without collectives)."""
 
     def __init__(self, H, W, K, ori_pose, trans_list, models, args, chunk=None, raygen=None, manipulate_chunk=None, draws=None,
-                 ins_num=None, rank=None, world=None, dtype=torch.float32):
+                 ins_num=None, rank=None, world=None, dtype=torch.float32, target_rays=None):
         r_, w_ = world_info()
         self.rank, self.world = (r_ if rank is None else int(rank)), (w_ if world is None else int(world))
         self._collective = rank is None and world is None
@@ -659,6 +685,13 @@ class ManipulationFrameRenderer:
         self.n_imp = int(self.args.N_importance)
         self.manipulate_chunk = manipulate_chunk or _default_manipulate_chunk
         self.draws = draws or _default_draws
+        from .editing import Deform
+        deform = [isinstance(trans, Deform) for trans in trans_list]
+        self.T = len(deform)
+        if self.T == 0:
+            raise ValueError("ManipulationFrameRenderer: at least one transformation")
+        if target_rays is None and any(deform):
+            target_rays = _target_rays_from(raygen) if raygen is not None else _default_target_rays
         raygen = raygen or _default_raygen
         row0, nrows = row_band(H, self.rank, self.world)
         pose = torch.as_tensor(ori_pose, dtype=torch.float32)
@@ -668,15 +701,22 @@ class ManipulationFrameRenderer:
             pose_h = torch.cat([pose_h, torch.tensor([[0., 0., 0., 1.]])], 0)
         ro, rd = raygen(H, W, K, pose.to(dev_pose), row0, nrows)
         self.ori = torch.stack([ro.reshape(-1, 3), rd.reshape(-1, 3)])                      # [2, band, 3]
-        tars = []
-        for trans in trans_list:
-            tar_pose = _matmul4_f32(torch.as_tensor(trans, dtype=torch.float32).cpu(), pose_h)   # manipulator.py:235
-            to, td = raygen(H, W, K, tar_pose.to(dev_pose), row0, nrows)
-            tars.append(torch.stack([to.reshape(-1, 3), td.reshape(-1, 3)]))
-        self.T = len(tars)
-        if self.T == 0:
-            raise ValueError("ManipulationFrameRenderer: at least one transformation")
-        self.tar = torch.stack(tars)                                                        # [T, 2, band, 3]
+        # a rigid object's pose is trans @ ori_pose (manipulator.py:235, :432), a deformed object's the original pose (:427-429)
+        tar_poses = [pose_h if d else _matmul4_f32(torch.as_tensor(trans, dtype=torch.float32).cpu(), pose_h)
+                     for d, trans in zip(deform, trans_list)]
+        if target_rays is not None:
+            import numpy as np
+            offsets = np.zeros((self.T, self.H), dtype=np.float64)
+            for t, trans in enumerate(trans_list):
+                if deform[t]:
+                    offsets[t] = trans.offsets(self.H)
+            self.tar = target_rays(self.H, self.W, K, [p.to(dev_pose) for p in tar_poses], [int(d) for d in deform], offsets, row0, nrows)
+        else:
+            tars = []
+            for tar_pose in tar_poses:
+                to, td = raygen(H, W, K, tar_pose.to(dev_pose), row0, nrows)
+                tars.append(torch.stack([to.reshape(-1, 3), td.reshape(-1, 3)]))
+            self.tar = torch.stack(tars)                                                    # [T, 2, band, 3]
         self.dev = self.ori.device
         self.start = row0 * self.W                                                          # first frame ray of this band
         self.n_local = self.ori.shape[1]

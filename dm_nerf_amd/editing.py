@@ -1,0 +1,251 @@
+"""Scene editing on the device: the two manipulation drivers of the reference's ``networks/manipulator.py`` around
+``manipulator()`` -- ``manipulator_demo`` (:367-491) and ``manipulator_eval`` (:208-364) -- without their file output.
+
+    :381-382, :397-429   the per-image-row deformation of an object's target rays    ->  ``deform_offsets``, ``Deform``, ``edit_rays``
+    :384-488             the demo's pose loop: one edit per object per view           ->  ``manipulate_demo_path``
+    :233-339             the evaluation's pose loop with PSNR / SSIM / AP             ->  ``manipulate_eval_path``
+    :472-488, :310-323   8-bit frame, label, label mask, coloured object image        ->  ``frame_products``, ``label_lut``
+
+The frames are rendered by ``distributed.ManipulationFrameRenderer`` (rows sharded over the ranks, one all-gather per frame); the
+products are computed from the gathered frame's packed buffer in place (csrc/edit_frame.hip), so 7 bytes per pixel leave the
+device instead of the ``4 (3 + C)`` of the float maps the reference copies to the host.  Writing PNG files stays with the caller.
+"""
+import copy
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import distributed as D
+
+DEFORM_FUNCS = ("sin", "ex", "linear", "abs_linear", "ln")
+# manipulator.py:381-382
+DEFORM_V = np.concatenate((np.linspace(0, 0.18, 2), np.linspace(0.18, 0, 2), np.linspace(0, -0.18, 2), np.linspace(-0.18, 0, 2)))
+
+
+def deform_offsets(H, func, view_index):
+    """The x offset of every image row for a deformed object, numpy float64 ``[H]``: ``v_1`` of manipulator.py:398-426 before
+    its ``np.repeat`` over the columns, computed on the host with numpy exactly as there (the constants of the reference's
+    400-pixel frames are kept literally), so the values are the reference's bit for bit.  ``sin`` scales by
+    ``deform_v[view_index]`` (:381-382, eight views; a larger index raises ``IndexError`` as in the reference)."""
+    v = np.linspace(1, int(H), int(H))
+    if func == "sin":
+        v = ((8 * np.pi) / 400) * v
+        return np.sin(v) * DEFORM_V[view_index]
+    if func == "ex":
+        return np.exp(-1 * v / 50)
+    if func == "linear":
+        return (v - 200) / 215
+    if func == "abs_linear":
+        return np.abs(v - 200) / 200
+    if func == "ln":
+        return np.log(v / 200)
+    raise ValueError(f"deform_offsets: unknown deformation '{func}' (one of {', '.join(DEFORM_FUNCS)})")
+
+
+class Deform:
+    """A deformation as an entry of ``ManipulationFrameRenderer``'s ``trans_list``, next to 4 x 4 matrices: the object's target
+    rays are the ORIGINAL pose's rays with the origin's x shifted by ``deform_offsets(H, func, view_index)[row]``."""
+    __slots__ = ("func", "view_index")
+
+    def __init__(self, func, view_index=0):
+        if func not in DEFORM_FUNCS:
+            raise ValueError(f"Deform: unknown deformation '{func}' (one of {', '.join(DEFORM_FUNCS)})")
+        self.func, self.view_index = func, int(view_index)
+
+    def offsets(self, H):
+        return deform_offsets(H, self.func, self.view_index)
+
+    def __repr__(self):
+        return f"Deform({self.func!r}, {self.view_index})"
+
+    def __eq__(self, other):
+        return isinstance(other, Deform) and (self.func, self.view_index) == (other.func, other.view_index)
+
+    def __hash__(self):
+        return hash((self.func, self.view_index))
+
+
+def edit_rays(H, W, K, poses, kinds, offsets=None, row0=0, nrows=None, device=None):
+    """Target rays of ``T`` edited objects for image rows ``[row0, row0 + nrows)`` in one launch (``dmnerf_edit_rays``) ->
+    ``[T, 2, nrows W, 3]``, what ``manipulator()`` takes as ``f_tar_rays``.  ``poses``: T c2w ``[3or4, 4]`` (read on the host),
+    ``kinds [T]``: 0 rigid (``get_rays_k`` of the pose, bit for bit) or 1 deform (origin x + ``offsets[t][absolute row]``, summed
+    in float64 and rounded once); ``offsets``: numpy float64 ``[T, H]`` or a device tensor of that shape (needed with a deform)."""
+    H, W, row0 = int(H), int(W), int(row0)
+    nrows = H - row0 if nrows is None else int(nrows)
+    T = len(poses)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    K = np.asarray(K)
+    intr = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2], K[2, 2]], dtype=np.float64).astype(np.float32)
+    c = np.ascontiguousarray(np.stack([(p.detach().cpu().numpy() if torch.is_tensor(p) else np.asarray(p)).astype(np.float32)[:3, :4]
+                                       for p in poses])) if T else np.zeros((0, 3, 4), np.float32)
+    kind = (ctypes.c_int * max(T, 1))(*[int(k) for k in kinds])
+    off = None
+    if offsets is not None:
+        off = offsets if torch.is_tensor(offsets) else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.float64))
+        off = off.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(off.shape) != (T, H):
+            raise ValueError(f"edit_rays: offsets must be [T={T}, H={H}], got {tuple(off.shape)}")
+    rays = torch.empty(T, 2, nrows * W, 3, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().dmnerf_edit_rays(H, W, intr.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p), kind, T,
+                                            _lib.ptr(off), row0, nrows, _lib.ptr(rays), _lib.stream()), "dmnerf_edit_rays")
+    return rays
+
+
+def label_lut(C, rgbs, color_dict, ins_map, device=None):
+    """The table of ``render_label2img`` (tools/visualizer.py:73-86) for labels ``0 .. C - 1`` -> uint8 ``[C, 3]`` on the device:
+    ``rgbs[color_dict[str(ins_map[str(l)])]]``, 0 where ``ins_map`` has no ``l`` (``field.color_table``, the rule of
+    ``field.label_colors``)."""
+    from . import field
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    return torch.from_numpy(field.color_table(int(C), rgbs, color_dict, ins_map)).to(dev)
+
+
+def frame_products(rgb, ins=None, lut=None):
+    """What the drivers write out for a frame (manipulator.py:472-488), on the device (``dmnerf_edit_products``):
+
+    ``rgb [..., 3]`` -> ``rgb8`` uint8 ``[..., 3]`` = ``to8b`` (evaluator.py:13); ``ins [..., C]`` -> ``label`` int64 ``[...]`` =
+    ``torch.argmax(ins, -1)`` over ALL channels (first maximum) and ``mask`` uint8 = that label; ``lut`` uint8 ``[C, 3]``
+    (``label_lut``) -> ``ins_img`` uint8 ``[..., 3]`` = ``lut[label]``.  Returns ``(rgb8, label, mask, ins_img)``; what has no
+    input is ``None``.  Channel-slice views of a packed frame -- what ``manipulate_frame`` returns -- are read in place."""
+    from .networks import evaluator
+    _lib.require_gpu(lut)
+    for t in (rgb, ins):
+        if t is not None and not t.is_cuda:
+            _lib.require_gpu(t)                         # raises: no CPU fallback
+    if rgb.shape[-1] != 3:
+        raise ValueError(f"frame_products: rgb must be [..., 3], got {tuple(rgb.shape)}")
+    lead = rgb.shape[:-1]
+    r, n, rs = evaluator._rows_view(rgb)
+    dev = r.device
+    rgb8 = torch.empty(*lead, 3, dtype=torch.uint8, device=dev)
+    x, xs, C, label, mask, ins_img = None, 0, 0, None, None, None
+    if ins is not None:
+        if ins.shape[:-1] != lead:
+            raise ValueError(f"frame_products: ins {tuple(ins.shape)} does not match rgb {tuple(rgb.shape)}")
+        x, _, xs = evaluator._rows_view(ins)
+        C = int(x.shape[-1])
+        label = torch.empty(*lead, dtype=torch.int64, device=dev)
+        mask = torch.empty(*lead, dtype=torch.uint8, device=dev)
+        if lut is not None:
+            if lut.dtype != torch.uint8 or tuple(lut.shape) != (C, 3):
+                raise ValueError(f"frame_products: lut must be uint8 [{C}, 3], got {lut.dtype} {tuple(lut.shape)}")
+            ins_img = torch.empty(*lead, 3, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().dmnerf_edit_products(_lib.ptr(r), rs, _lib.ptr(x), xs, C, _lib.ptr(lut), n, _lib.ptr(rgb8), _lib.ptr(label),
+                                                _lib.ptr(mask), _lib.ptr(ins_img), _lib.stream()), "dmnerf_edit_products")
+    return rgb8, label, mask, ins_img
+
+
+def _render(H, W, K, pose, edits, models, args, frame_kw):
+    fr = D.ManipulationFrameRenderer(H, W, K, pose, edits, models, args, **frame_kw)
+    for c in range(fr.n_chunks):
+        fr.step(c)
+    return fr.gather()
+
+
+MAP_NAMES = ("rgb", "ins", "tar_rgb", "tar_ins")
+
+
+def manipulate_demo_path(view_poses, hwk, models, args, objs, objs_trans, ins_rgbs, color_dict, ins_map, keep_maps=False,
+                         products=None, **frame_kw):
+    """The pose loop of ``manipulator_demo`` (networks/manipulator.py:384-488) without its file output: per view ``i`` every
+    object of ``objs`` is edited at once -- ``obj['mani_mode'] == 'deform'``: ``Deform(obj['deform_func'], i)``, otherwise the
+    rigid ``objs_trans[obj['obj_name']][i]['transformation']`` -- with ``target_labels = [obj['tar_id'] ...]`` (:395, :437), one
+    ``ManipulationFrameRenderer`` frame (``frame_kw`` goes to it: ``raygen=``, ``target_rays=``, ``manipulate_chunk=``, ``draws=``,
+    ``rank=`` / ``world=`` ...), then ``frame_products`` with the table of ``render_label2img``.
+
+    Returns a dict of stacked device tensors: ``rgb8 [P,H,W,3]`` (``{i}_rgb.png``), ``ins_img [P,H,W,3]`` (``{i}_ins.png``),
+    ``mask [P,H,W]`` uint8 (``{i}_ins_pred_mask.png``), ``label [P,H,W]`` int64; ``keep_maps=True``: also the four float frames
+    ``rgb, ins, tar_rgb, tar_ins``.  Never synchronises with the host (poses and transformations are host data).  ``products``
+    (injectable, for tests of the loop on the CPU): a stand-in for ``frame_products``."""
+    H, W, K = hwk
+    products = products or frame_products
+    a = copy.copy(args)
+    a.target_labels = [obj["tar_id"] for obj in objs]
+    lut, cols = None, {}
+    for i, pose in enumerate(view_poses):
+        edits = [Deform(obj["deform_func"], i) if obj["mani_mode"] == "deform" else objs_trans[obj["obj_name"]][i]["transformation"]
+                 for obj in objs]
+        frame = _render(H, W, K, pose, edits, models, a, frame_kw)
+        if lut is None:
+            lut = label_lut(frame[1].shape[-1], ins_rgbs, color_dict, ins_map, device=frame[1].device)
+        for name, t in zip(("rgb8", "label", "mask", "ins_img"), products(frame[0], frame[1], lut)):
+            cols.setdefault(name, []).append(t)
+        if keep_maps:
+            for name, t in zip(MAP_NAMES, frame):
+                cols.setdefault(name, []).append(t)
+    return {k: torch.stack(v, 0) for k, v in cols.items()}
+
+
+def gt_color_table(rgbs, color_dict, device):
+    """``render_gt_label2img``'s colours (tools/visualizer.py:57-69) as a table: uint8 ``[G + 1, 3]`` on the device, row ``g`` =
+    ``rgbs[color_dict[str(g)]]`` for the labels ``color_dict`` holds, 0 elsewhere; row ``G`` (zeros) takes every other label."""
+    from . import field
+    keys = [int(k) for k in color_dict.keys() if int(k) >= 0]
+    G = max(keys, default=-1) + 1
+    return torch.from_numpy(field.color_table(G + 1, rgbs, color_dict, {str(k): k for k in keys})).to(device)
+
+
+def _gt_colors(table, labels):
+    G = table.shape[0] - 1
+    return table[torch.where((labels >= 0) & (labels < G), labels, torch.full_like(labels, G))]
+
+
+def manipulate_eval_path(ori_poses, hwk, models, args, trans, gt_rgbs=None, gt_labels=None, ins_rgbs=None, color_dict=None,
+                         image_metrics=True, keep_maps=False, **frame_kw):
+    """The pose loop of ``manipulator_eval`` (networks/manipulator.py:233-339) for one transformation ``trans`` (4 x 4, or a
+    ``Deform``), without its file output and LPIPS: per pose one ``ManipulationFrameRenderer`` frame with ``target_labels =
+    [args.target_label]`` (:231), then on the device
+
+    * ``rgb8``, ``tar_rgb8`` uint8 ``[P,H,W,3]``: the edited frame and the plain target render (:310-318);
+    * given ``gt_rgbs [P,H,W,3]``: ``psnr [P]`` (float32) and, with ``image_metrics``, ``psnr_f64`` / ``ssim`` of the edited frame
+      (:278-279, ``evaluator.img_metrics_device``: one call for all poses after the loop);
+    * given ``gt_labels [P,H,W]``: ``ap [P,6]``, ``matched [P,ins_num]``, ``gt_num [P]`` of ``ins[..., :-1]`` against the rows
+      ``unique(gt_label)`` (:287-297: the branch of ``render_path`` without a crop); with ``ins_rgbs`` and ``color_dict`` also
+      ``label [P,H,W]`` (argmax over ALL channels, :321), ``ins_img`` coloured through that pose's own matching (:299-323:
+      ``ins_map[str(matched row)] = gt label``, built on the device from ``matched`` and the rows) and ``gt_ins_img``
+      (``render_gt_label2img``, :327).  A gt label that ``color_dict`` does not hold is black (the reference raises ``KeyError``).
+
+    ``keep_maps=True`` adds the float frames ``rgb, ins, tar_rgb, tar_ins``.  ``distributed.results_table`` takes the result as it
+    is (LPIPS ``nan`` unless passed).  The frames are complete on every rank: every rank computes the same numbers."""
+    H, W, K = hwk
+    cols = {}
+    table = None
+    scored = image_metrics and gt_rgbs is not None
+    for i, pose in enumerate(ori_poses):
+        rgb, ins, tar_rgb, tar_ins = _render(H, W, K, pose, [trans], models, args, frame_kw)
+        cols.setdefault("rgb8", []).append(frame_products(rgb)[0])
+        cols.setdefault("tar_rgb8", []).append(frame_products(tar_rgb)[0])
+        if keep_maps or scored:
+            cols.setdefault("rgb", []).append(rgb)
+        if keep_maps:
+            for name, t in zip(MAP_NAMES[1:], (ins, tar_rgb, tar_ins)):
+                cols.setdefault(name, []).append(t)
+        if gt_rgbs is not None:
+            gt = torch.as_tensor(gt_rgbs[i]).to(rgb)
+            cols.setdefault("psnr", []).append(-10.0 * torch.log10(torch.mean((rgb - gt) ** 2)))
+        if gt_labels is not None:
+            C = ins.shape[-1]
+            ap, matched, gt_num = D._frame_ap({"ins": [ins[..., :C - 1]]}, gt_labels[i], False, False, args, frame_kw)
+            for name, t in zip(("ap", "matched", "gt_num"), (ap, matched, gt_num)):
+                cols.setdefault(name, []).append(t)
+            if ins_rgbs is not None and color_dict is not None:
+                if table is None:
+                    table = gt_color_table(ins_rgbs, color_dict, ins.device)
+                gl = torch.as_tensor(gt_labels[i]).to(device=ins.device, dtype=torch.int64).reshape(H, W)
+                rows = torch.unique(gl)                                             # the rows _frame_ap matched, ascending
+                m = matched[:rows.numel()]
+                lut = torch.zeros(C + 1, 3, dtype=torch.uint8, device=ins.device)   # row C: the unmatched gt rows
+                lut[torch.where(m >= 0, m, torch.full_like(m, C))] = _gt_colors(table, rows)
+                _, label, _, ins_img = frame_products(rgb, ins, lut[:C])
+                for name, t in zip(("label", "ins_img", "gt_ins_img"), (label, ins_img, _gt_colors(table, gl))):
+                    cols.setdefault(name, []).append(t)
+    out = {k: torch.stack(v, 0) for k, v in cols.items()}
+    if scored:
+        from .networks import evaluator
+        gt = torch.stack([torch.as_tensor(gt_rgbs[i]).to(out["rgb"]) for i in range(out["rgb"].shape[0])], 0)
+        out["ssim"], out["psnr_f64"] = evaluator.img_metrics_device(out["rgb"], gt)
+    if scored and not keep_maps:
+        del out["rgb"]
+    return out

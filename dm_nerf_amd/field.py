@@ -172,21 +172,27 @@ def label_points(vertices, normals, models, args, chunk=None):
     return label, conf
 
 
+def color_table(n_rows, rgbs, color_dict, ins_map):
+    """The host-built look-up table behind ``render_label2world`` / ``render_label2img`` (tools/visualizer.py:208-223, :73-86):
+    numpy uint8 ``[n_rows, 3]`` whose row ``l`` is ``rgbs[color_dict[str(ins_map[str(l)])]]``, or 0 where ``ins_map`` has no ``l``
+    (the reference leaves those pixels of its zero image untouched; ``astype(np.uint8)`` of the float64 image as there)."""
+    rgbs = np.asarray(rgbs)
+    lut = np.zeros((int(n_rows), 3))
+    for k in (int(k) for k in ins_map.keys()):
+        if 0 <= k < n_rows:
+            lut[k] = rgbs[color_dict[str(ins_map[str(k)])]]
+    return lut.astype(np.uint8)
+
+
 def label_colors(labels, rgbs, color_dict, ins_map):
     """``render_label2world`` (tools/visualizer.py:208-223) -> ``[V, 3]`` uint8 on the device: the colour
     ``rgbs[color_dict[str(ins_map[str(label)])]]`` of every label, 0 for a label that ``ins_map`` does not hold.  The two dicts
-    become one look-up table on the host; the device does one gather."""
+    become one look-up table on the host (``color_table``); the device does one gather."""
     _lib.require_gpu(labels)
     if labels.dtype != torch.int64:
         raise ValueError("label_colors expects int64 labels")
-    rgbs = np.asarray(rgbs)
-    keys = [int(k) for k in ins_map.keys()]
-    n = max([k for k in keys if k >= 0], default=-1) + 1
-    lut = np.zeros((n + 1, 3))                                # row n: every label without an entry
-    for k in keys:
-        if k >= 0:
-            lut[k] = rgbs[color_dict[str(ins_map[str(k)])]]
-    lut = torch.from_numpy(lut.astype(np.uint8)).to(labels.device)
+    n = max([int(k) for k in ins_map.keys() if int(k) >= 0], default=-1) + 1
+    lut = torch.from_numpy(color_table(n + 1, rgbs, color_dict, ins_map)).to(labels.device)   # row n: every label without an entry
     flat = labels.reshape(-1)
     idx = torch.where((flat >= 0) & (flat < n), flat, torch.full_like(flat, n))
     return lut[idx]

@@ -1,6 +1,9 @@
 """Drop-in for the render core of the reference's ``networks/manipulator.py``: ``exchanger``,
-``manipulator_render``, ``manipulator_nerf``, ``manipulator``.  The evaluation / demo drivers (image IO, LPIPS,
-pose JSON) of that file are out of scope; they call exactly these four functions."""
+``manipulator_render``, ``manipulator_nerf``, ``manipulator``.  The two drivers of that file call exactly these four functions;
+their pose loops live elsewhere in this package: one pose is ``dm_nerf_amd.distributed.manipulate_frame`` (rows sharded over
+the ranks), ``manipulator_eval`` (:208-364) is ``dm_nerf_amd.editing.manipulate_eval_path`` (frames, PSNR / SSIM / AP, the 8-bit
+and coloured images) and ``manipulator_demo`` (:367-491) is ``dm_nerf_amd.editing.manipulate_demo_path`` (several objects per
+view, rigid or deformed).  File output, LPIPS and the pose JSON stay with the caller."""
 import ctypes
 
 import torch

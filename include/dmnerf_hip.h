@@ -370,6 +370,38 @@ int dmnerf_exchanger(float* d_ori_raw, const float* const* h_tar_raws, const flo
                      const float* const* h_tar_accs, const int* h_labels, int T, int64_t N, int S, int C,
                      int64_t* d_ori_label, int64_t* d_tar_label, void* stream);
 
+/* ---- manipulator.py, the drivers around manipulator(): manipulator_eval / manipulator_demo (csrc/edit_frame.hip) --------------
+ * dmnerf_edit_rays: the target rays of T edited objects (1 .. DMNERF_EDIT_MAX_OBJECTS, the exchanger's limit) for image rows
+ *   [row0, row0 + nrows), one launch, written as d_rays [T, 2, n, 3] (n = nrows W; [t][0] origins, [t][1] directions) -- the
+ *   tensor manipulator() takes as f_tar_rays, replacing the per-object get_rays_k / clone / stack / reshape of networks/
+ *   manipulator.py:392-441.  h_intr as for dmnerf_raygen; h_poses [T][12] = the first 3 rows of each object's c2w; h_kind [T]:
+ *     0 rigid  -- exactly what dmnerf_raygen writes for that pose and band (the same device function: bit-identical rows;
+ *                 :431-433, the pose being trans @ ori_pose formed by the caller);
+ *     1 deform -- origin and direction of the pose given (the driver passes the ORIGINAL pose), origin x replaced by
+ *                 (float)((double)x + d_off[t][row]) with row the ABSOLUTE image row: tar_rays_o[:, 0] + v_1 of :428, an f32 column
+ *                 plus an f64 tensor, summed in f64 and rounded once.  y, z and the direction are unchanged (:427, :429).
+ *   d_off: device double [T, H], read only in the rows of deform objects (may be null when there is none).
+ * dmnerf_edit_products: what the drivers write out for n pixels (:472-488, :310-323), from STRIDED rows -- pixel p's colour at
+ *   d_rgb + p rgb_stride (3 floats), its object channels at d_ins + p ins_stride (C floats; strides in floats, >= 3 / >= C) -- so
+ *   the packed band of the frame driver or a channel slice of the gathered frame is read without a copy.  Outputs, each nullable:
+ *     d_rgb8 [n,3] uint8    (uint8)(255.f * min(max(x, 0), 1)), the product in f32, truncated: to8b (networks/evaluator.py:13);
+ *     d_label [n] int64     argmax over ALL C channels, first maximum (the tie rule of dmnerf_ins_label_conf): the drivers take
+ *                           torch.argmax(ins) with the last channel included (:321, :477);
+ *     d_mask [n] uint8      (uint8)label (:488);
+ *     d_ins_img [n,3] uint8 d_lut[label], d_lut = uint8 [C,3] (render_label2img, tools/visualizer.py:73-86, as a table).
+ *   d_ins null: only d_rgb8 is written; d_lut null: d_ins_img is not written.  C <= DMNERF_EDIT_MAX_CHANNELS.  Non-finite
+ *   inputs are outside the contract (a NaN colour or object channel gives an unspecified byte / label, never an access outside
+ *   the buffers).
+ * Both validate their arguments before touching a device (DMNERF_E_ARG), allocate nothing, do not synchronise, run on the
+ * caller's stream and are capturable.                                                                                        */
+#define DMNERF_EDIT_MAX_OBJECTS 8
+#define DMNERF_EDIT_MAX_CHANNELS 129
+int dmnerf_edit_rays(int H, int W, const float* h_intr, const float* h_poses, const int* h_kind, int T,
+                     const double* d_off, int row0, int nrows, float* d_rays, void* stream);
+int dmnerf_edit_products(const float* d_rgb, int64_t rgb_stride, const float* d_ins, int64_t ins_stride, int C,
+                         const uint8_t* d_lut, int64_t n, uint8_t* d_rgb8, int64_t* d_label, uint8_t* d_mask,
+                         uint8_t* d_ins_img, void* stream);
+
 /* ---- evaluator.py ins_eval, the part every frame needs (networks/evaluator.py:127-137) ----------------
  * d_label [N] int64 = argmax over the C object channels of d_ins [N,C] (first maximum, like torch.argmax on CPU);
  * d_conf [N] (nullable) = that maximum (np.max(pred_ins, -1)).                                                    */
