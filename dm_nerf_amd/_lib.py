@@ -98,6 +98,7 @@ SIGNATURES = {
     "dmnerf_sort_rows": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp]),
     "dmnerf_ins_label_conf": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),
     "dmnerf_exchanger": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
+    "dmnerf_edit_exchange": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
     "dmnerf_edit_rays": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
     "dmnerf_edit_products": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_penalizer_fwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_float, c_float, c_float, c_vp, c_vp]),

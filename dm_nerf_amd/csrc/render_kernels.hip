@@ -762,6 +762,68 @@ __global__ void exchanger_kernel(const ExchArgs a) {
     if (a.tar_label) a.tar_label[idx] = tar_lab_last;
 }
 
+// edit_exchange: the exchanger's per-sample decision generalised to three kinds of edit plus a keep mask.  A MOVE is the loop
+// body above; a COPY takes the target's rows but never gives up the original's; a REMOVE is the "eliminate" branch without a
+// target (no target rays, no target rows read).  The keep mask tests the sample's OWN label l0 (before any occlusion
+// correction), so what it zeroes does not depend on the order of the edits.
+constexpr int EDIT_MOVE = 0, EDIT_COPY = 1, EDIT_REMOVE = 2;
+constexpr int EDIT_MAX_C = 128;           // two 64-bit words of keep bits
+struct EditExchArgs {
+    float* ori_raw;                       // [N,S,4+C], modified in place
+    const float* tar_raw[MAX_MOVE];       // E x [N,S,4+C]; null for a REMOVE
+    const float* ori_acc;                 // [N,C]
+    const float* tar_acc[MAX_MOVE];       // E x [N,C]; null for a REMOVE
+    int labels[MAX_MOVE];
+    int kinds[MAX_MOVE];
+    uint64_t keep[2];
+    int has_keep;
+    int E, S, C;
+    int64_t N;
+    int64_t* ori_label;                   // [N,S] out (nullable): the original's label after the corrections
+};
+
+__global__ void edit_exchange_kernel(const EditExchArgs a) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= a.N * a.S) return;
+    const int64_t n = idx / a.S;
+    const int ch = 4 + a.C;
+    float* orow = a.ori_raw + idx * ch;
+    const int l0 = argmax_sigmoid(orow + 4, a.C);
+    int ori_lab = l0;
+    const int ori_acc_lab = a.E > 0 ? argmax_sigmoid(a.ori_acc + n * a.C, a.C - 1) : 0;
+    for (int e = 0; e < a.E; ++e) {
+        const int L = a.labels[e];
+        const int kind = a.kinds[e];
+        if (ori_acc_lab != L && ori_lab == L) ori_lab = ori_acc_lab;                 // occluded: take the ray's label
+        if (kind == EDIT_REMOVE) {
+            if (ori_lab == L)
+                for (int c = 0; c < ch; ++c) orow[c] = orow[c] * 0.f;                // ori_raw[...] * 0: -0, NaN of inf as there
+            continue;
+        }
+        const float* trow = a.tar_raw[e] + idx * ch;
+        int tar_lab = argmax_sigmoid(trow + 4, a.C);
+        const int tar_acc_lab = argmax_sigmoid(a.tar_acc[e] + n * a.C, a.C - 1);
+        if (tar_acc_lab != L && tar_lab == L) tar_lab = tar_acc_lab;
+        const int reduced = (tar_lab == L ? 1 : 0) + (ori_lab == L ? 2 : 0);
+        if (kind == EDIT_MOVE) {
+            const bool fill = ori_acc_lab == L && ori_lab != L;
+            if (fill || reduced == 1 || reduced == 3) {
+                for (int c = 0; c < ch; ++c) orow[c] = trow[c];
+            } else if (reduced == 2) {
+                for (int c = 0; c < ch; ++c) orow[c] = orow[c] * 0.f;
+            }
+        } else if (reduced == 1) {                                                   // COPY: only where the original is not L
+            for (int c = 0; c < ch; ++c) orow[c] = trow[c];
+        }
+    }
+    if (a.has_keep) {
+        const uint64_t word = l0 < 64 ? a.keep[0] : a.keep[1];                       // (a select, not a per-lane index into the arguments)
+        if (!((word >> (l0 & 63)) & 1))
+            for (int c = 0; c < ch; ++c) orow[c] = orow[c] * 0.f;
+    }
+    if (a.ori_label) a.ori_label[idx] = ori_lab;
+}
+
 __global__ void gather_kernel(const float* __restrict__ flat, const int32_t* __restrict__ idx,
                               float* __restrict__ blob, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1109,4 +1171,36 @@ extern "C" int dmnerf_exchanger(float* d_ori_raw, const float* const* h_tar_raws
     }
     hipLaunchKernelGGL(exchanger_kernel, dim3(blocks_for(N * S, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return dmn_check_launch("exchanger");
+}
+
+extern "C" int dmnerf_edit_exchange(float* d_ori_raw, const float* const* h_tar_raws, const float* d_ori_acc,
+                                    const float* const* h_tar_accs, const int* h_labels, const int* h_kinds, int E,
+                                    const uint64_t* h_keep, int64_t N, int S, int C, int64_t* d_ori_label, void* stream) {
+    if (E < 0 || E > MAX_MOVE || (E == 0 && !h_keep))
+        return dmn_fail(DMNERF_E_ARG, "edit_exchange: bad E=%d (1..%d, or 0 with a keep mask)", E, MAX_MOVE);
+    if (N < 0 || S < 1 || C < 2 || C > EDIT_MAX_C)
+        return dmn_fail(DMNERF_E_ARG, "edit_exchange: bad N=%lld S=%d C=%d (C in 2..%d)", (long long)N, S, C, EDIT_MAX_C);
+    if (E > 0 && (!h_labels || !h_kinds)) return dmn_fail(DMNERF_E_ARG, "edit_exchange: null pointer (labels / kinds)");
+    EditExchArgs a{};
+    for (int e = 0; e < E; ++e) {
+        const int kind = h_kinds[e], L = h_labels[e];
+        if (kind != EDIT_MOVE && kind != EDIT_COPY && kind != EDIT_REMOVE)
+            return dmn_fail(DMNERF_E_ARG, "edit_exchange: kind[%d]=%d (0 move, 1 copy, 2 remove)", e, kind);
+        if (L < 0 || L >= C) return dmn_fail(DMNERF_E_ARG, "edit_exchange: label[%d]=%d outside [0, %d)", e, L, C);
+        const float* raw = h_tar_raws ? h_tar_raws[e] : nullptr;
+        const float* acc = h_tar_accs ? h_tar_accs[e] : nullptr;
+        if (kind == EDIT_REMOVE) {
+            if (raw || acc) return dmn_fail(DMNERF_E_ARG, "edit_exchange: edit %d is a removal: its target pointers must be null", e);
+        } else if (!raw || !acc) {
+            return dmn_fail(DMNERF_E_ARG, "edit_exchange: null target pointer %d (kind %d)", e, kind);
+        }
+        a.tar_raw[e] = raw; a.tar_acc[e] = acc; a.labels[e] = L; a.kinds[e] = kind;
+    }
+    if (N == 0) return DMNERF_OK;
+    if (!d_ori_raw || (E > 0 && !d_ori_acc)) return dmn_fail(DMNERF_E_ARG, "edit_exchange: null pointer");
+    if (N > 0x7fffffffLL * 256 / S) return dmn_fail(DMNERF_E_ARG, "edit_exchange: N=%lld S=%d too large", (long long)N, S);
+    a.ori_raw = d_ori_raw; a.ori_acc = d_ori_acc; a.E = E; a.S = S; a.C = C; a.N = N; a.ori_label = d_ori_label;
+    if (h_keep) { a.has_keep = 1; a.keep[0] = h_keep[0]; a.keep[1] = h_keep[1]; }
+    hipLaunchKernelGGL(edit_exchange_kernel, dim3(blocks_for(N * S, 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return dmn_check_launch("edit_exchange");
 }

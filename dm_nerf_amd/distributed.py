@@ -616,7 +616,8 @@ def _matmul4_f32(a, b):
 
 def _default_manipulate_chunk(ori_rays, tar_rays, models, args, us):
     from .networks import manipulator as Mn
-    return Mn.manipulator(None, None, models[0], models[1], ori_rays, tar_rays, args, us=us)
+    return Mn.manipulator(None, None, models[0], models[1], ori_rays, tar_rays, args, us=us, kinds=getattr(args, "edit_kinds", None),
+                          keep_labels=getattr(args, "keep_labels", None))
 
 
 def _default_draws(n, n_imp, count, device):
@@ -666,13 +667,19 @@ class ManipulationFrameRenderer:
       (C = ins_num + 1: the manipulation render keeps the last object channel, :101-102), and ``gather()`` is ONE all-gather per
       frame.
 
+    * an entry may also be an ``editing.Remove()`` or an ``editing.Copy(matrix)``, and ``keep_labels`` isolates a set of objects
+      (``networks.manipulator.edit_exchanger``).  A removal has no target rays and no draws: ``T`` counts the entries WITH rays,
+      ``step`` draws ``2 + T``, and the kinds and the keep set travel to ``manipulate_chunk`` as ``args.edit_kinds`` (one per entry of
+      ``trans_list``) and ``args.keep_labels``.  Without target rays the ``tar_rgb | tar_ins`` columns of the band are zero.  With
+      ``keep_labels`` ``trans_list`` may be empty.
+
     ``manipulate_chunk(ori_rays [2,n,3], tar_rays [T,2,n,3], models, args, us)``, ``raygen`` / ``draws`` and
     ``target_rays(H, W, K, poses, kinds, offsets [T,H] float64, row0, nrows) -> [T,2,n,3]`` are injectable
     (CPU / gloo tests of the sharding logic); ``rank=`` / ``world=`` override the process group's view for the band arithmetic
     (a single process can then render band r of N, without collectives)."""
 
     def __init__(self, H, W, K, ori_pose, trans_list, models, args, chunk=None, raygen=None, manipulate_chunk=None, draws=None,
-                 ins_num=None, rank=None, world=None, dtype=torch.float32, target_rays=None):
+                 ins_num=None, rank=None, world=None, dtype=torch.float32, target_rays=None, keep_labels=None):
         r_, w_ = world_info()
         self.rank, self.world = (r_ if rank is None else int(rank)), (w_ if world is None else int(world))
         self._collective = rank is None and world is None
@@ -681,15 +688,23 @@ class ManipulationFrameRenderer:
         import copy
         self.args = copy.copy(args)
         if not hasattr(self.args, "target_labels"):                 # manipulator.py:229
-            self.args.target_labels = [self.args.target_label]
+            self.args.target_labels = [self.args.target_label] if len(trans_list) else []
         self.n_imp = int(self.args.N_importance)
         self.manipulate_chunk = manipulate_chunk or _default_manipulate_chunk
         self.draws = draws or _default_draws
-        from .editing import Deform
+        from .editing import Copy, Deform, edit_kind
+        kinds = [edit_kind(trans) for trans in trans_list]
+        if len(kinds) == 0 and keep_labels is None:
+            raise ValueError("ManipulationFrameRenderer: at least one transformation")
+        if any(kinds) or keep_labels is not None:                   # removals, copies, a keep set: manipulator()'s edit path
+            if len(self.args.target_labels) != len(kinds):
+                raise ValueError(f"ManipulationFrameRenderer: {len(self.args.target_labels)} target labels for {len(kinds)} edits")
+            self.args.edit_kinds = kinds
+            self.args.keep_labels = None if keep_labels is None else [int(l) for l in keep_labels]
+        # only MOVE and COPY entries have target rays (and draws): a removal reads no target
+        trans_list = [trans.matrix if isinstance(trans, Copy) else trans for trans, k in zip(trans_list, kinds) if k != 2]
         deform = [isinstance(trans, Deform) for trans in trans_list]
         self.T = len(deform)
-        if self.T == 0:
-            raise ValueError("ManipulationFrameRenderer: at least one transformation")
         if target_rays is None and any(deform):
             target_rays = _target_rays_from(raygen) if raygen is not None else _default_target_rays
         raygen = raygen or _default_raygen
@@ -704,7 +719,9 @@ class ManipulationFrameRenderer:
         # a rigid object's pose is trans @ ori_pose (manipulator.py:235, :432), a deformed object's the original pose (:427-429)
         tar_poses = [pose_h if d else _matmul4_f32(torch.as_tensor(trans, dtype=torch.float32).cpu(), pose_h)
                      for d, trans in zip(deform, trans_list)]
-        if target_rays is not None:
+        if self.T == 0:
+            self.tar = torch.zeros(0, 2, self.ori.shape[1], 3, dtype=self.ori.dtype, device=self.ori.device)
+        elif target_rays is not None:
             import numpy as np
             offsets = np.zeros((self.T, self.H), dtype=np.float64)
             for t, trans in enumerate(trans_list):

@@ -5,6 +5,7 @@
     :384-488             the demo's pose loop: one edit per object per view           ->  ``manipulate_demo_path``
     :233-339             the evaluation's pose loop with PSNR / SSIM / AP             ->  ``manipulate_eval_path``
     :472-488, :310-323   8-bit frame, label, label mask, coloured object image        ->  ``frame_products``, ``label_lut``
+    (extension)          remove, duplicate, isolate: entries next to matrices / ``Deform``  ->  ``Remove``, ``Copy``, ``keep_labels=``
 
 The frames are rendered by ``distributed.ManipulationFrameRenderer`` (rows sharded over the ranks, one all-gather per frame); the
 products are computed from the gathered frame's packed buffer in place (csrc/edit_frame.hip), so 7 bytes per pixel leave the
@@ -65,6 +66,43 @@ class Deform:
 
     def __hash__(self):
         return hash((self.func, self.view_index))
+
+
+class Remove:
+    """Removal of an object as an entry of ``trans_list``: its samples are zeroed in the original rays' field
+    (``networks.manipulator.REMOVE``).  It has no target rays, makes no draws and adds no samples to the merged depths."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "Remove()"
+
+    def __eq__(self, other):
+        return isinstance(other, Remove)
+
+    def __hash__(self):
+        return hash(Remove)
+
+
+class Copy:
+    """Duplication of an object as an entry of ``trans_list``: the object also appears where ``matrix`` (4 x 4, as for a move)
+    puts it, and stays where it is (``networks.manipulator.COPY``).  ``matrix`` may be a ``Deform``: the duplicate's target rays
+    are then the deformed ones -- the rays of an entry and what the exchange does with them are independent."""
+    __slots__ = ("matrix",)
+
+    def __init__(self, matrix):
+        if isinstance(matrix, (Remove, Copy)):
+            raise ValueError(f"Copy: cannot wrap {matrix!r} (a 4 x 4 matrix or a Deform)")
+        if not isinstance(matrix, Deform) and tuple(np.shape(matrix)) != (4, 4):
+            raise ValueError(f"Copy: the transformation must be 4 x 4 or a Deform, got shape {tuple(np.shape(matrix))}")
+        self.matrix = matrix
+
+    def __repr__(self):
+        return f"Copy({self.matrix!r})"
+
+
+def edit_kind(trans):
+    """The exchange kind of a ``trans_list`` entry: ``networks.manipulator.MOVE`` / ``COPY`` / ``REMOVE``."""
+    return 2 if isinstance(trans, Remove) else 1 if isinstance(trans, Copy) else 0
 
 
 def edit_rays(H, W, K, poses, kinds, offsets=None, row0=0, nrows=None, device=None):
@@ -148,7 +186,7 @@ MAP_NAMES = ("rgb", "ins", "tar_rgb", "tar_ins")
 
 
 def manipulate_demo_path(view_poses, hwk, models, args, objs, objs_trans, ins_rgbs, color_dict, ins_map, keep_maps=False,
-                         products=None, **frame_kw):
+                         products=None, keep_labels=None, **frame_kw):
     """The pose loop of ``manipulator_demo`` (networks/manipulator.py:384-488) without its file output: per view ``i`` every
     object of ``objs`` is edited at once -- ``obj['mani_mode'] == 'deform'``: ``Deform(obj['deform_func'], i)``, otherwise the
     rigid ``objs_trans[obj['obj_name']][i]['transformation']`` -- with ``target_labels = [obj['tar_id'] ...]`` (:395, :437), one
@@ -158,8 +196,13 @@ def manipulate_demo_path(view_poses, hwk, models, args, objs, objs_trans, ins_rg
     Returns a dict of stacked device tensors: ``rgb8 [P,H,W,3]`` (``{i}_rgb.png``), ``ins_img [P,H,W,3]`` (``{i}_ins.png``),
     ``mask [P,H,W]`` uint8 (``{i}_ins_pred_mask.png``), ``label [P,H,W]`` int64; ``keep_maps=True``: also the four float frames
     ``rgb, ins, tar_rgb, tar_ins``.  Never synchronises with the host (poses and transformations are host data).  ``products``
-    (injectable, for tests of the loop on the CPU): a stand-in for ``frame_products``."""
+    (injectable, for tests of the loop on the CPU): a stand-in for ``frame_products``.
+
+    Extension: a ``'transformation'`` of ``objs_trans`` may be a ``Remove()`` or a ``Copy(matrix)``, and ``keep_labels`` shows
+    only the objects of that set (isolate); ``objs`` may then be empty."""
     H, W, K = hwk
+    if keep_labels is not None:
+        frame_kw = dict(frame_kw, keep_labels=keep_labels)
     products = products or frame_products
     a = copy.copy(args)
     a.target_labels = [obj["tar_id"] for obj in objs]

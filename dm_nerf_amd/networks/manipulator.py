@@ -33,6 +33,50 @@ def exchanger(ori_raw, tar_raws, ori_raw_pred, tar_raw_preds, move_labels):
     return ori_raw, tar_raws, ori_label, tar_label
 
 
+MOVE, COPY, REMOVE = 0, 1, 2                    # the kinds of ``dmnerf_edit_exchange``
+
+
+def keep_words(keep_labels, C):
+    """The keep set as the two 64-bit words ``dmnerf_edit_exchange`` takes (bit ``l`` set: label ``l`` stays)."""
+    words = [0, 0]
+    for l in keep_labels:
+        l = int(l)
+        if not 0 <= l < C:
+            raise ValueError(f"keep_labels: label {l} outside [0, {C})")
+        words[l >> 6] |= 1 << (l & 63)
+    return words
+
+
+def edit_exchanger(ori_raw, tar_raws, ori_raw_pred, tar_raw_preds, move_labels, kinds, keep_labels=None, want_label=True):
+    """``exchanger`` (networks/manipulator.py:18-83) generalised (``dmnerf_edit_exchange``): edit ``e`` of label
+    ``move_labels[e]`` is a ``MOVE`` (the reference's loop body), a ``COPY`` (the target's rows where the target is the object and
+    the original is not; nothing is given up) or a ``REMOVE`` (the original's rows of the object times 0; ``tar_raws[e]`` and
+    ``tar_raw_preds[e]`` are ``None``).  ``keep_labels``: afterwards every row whose OWN label is not in the set is zeroed.
+    ``ori_raw`` is modified in place -> ``(ori_raw, ori_label [N,S] int64 or None)``."""
+    lib = _lib.load()
+    E = len(move_labels)
+    if len(kinds) != E or len(tar_raws) != E or len(tar_raw_preds) != E:
+        raise ValueError(f"edit_exchanger: {E} labels, {len(kinds)} kinds, {len(tar_raws)} / {len(tar_raw_preds)} targets")
+    _lib.require_gpu(ori_raw, ori_raw_pred, *tar_raws, *tar_raw_preds)
+    if ori_raw.dtype != torch.float32:
+        raise ValueError("edit_exchanger: ori_raw is edited in place and must be float32")
+    N, S, ch = ori_raw.shape
+    C = ch - 4
+    tr = [None if t is None else _lib.f32(t) for t in tar_raws]
+    ta = [None if t is None else _lib.f32(t) for t in tar_raw_preds]
+    oa = _lib.f32(ori_raw_pred)
+    P = ctypes.c_void_p * max(E, 1)
+    raws = P(*[None if t is None else t.data_ptr() for t in tr])
+    accs = P(*[None if t is None else t.data_ptr() for t in ta])
+    labels = (ctypes.c_int * max(E, 1))(*[int(v) for v in move_labels])
+    kind = (ctypes.c_int * max(E, 1))(*[int(v) for v in kinds])
+    keep = None if keep_labels is None else (ctypes.c_uint64 * 2)(*keep_words(keep_labels, C))
+    ori_label = torch.empty(N, S, dtype=torch.int64, device=ori_raw.device) if want_label else None
+    _lib.check(lib.dmnerf_edit_exchange(_lib.ptr(ori_raw), raws, _lib.ptr(oa), accs, labels, kind, E, keep, N, S, C,
+                                        _lib.ptr(ori_label), _lib.stream()), "dmnerf_edit_exchange")
+    return ori_raw, ori_label
+
+
 def manipulator_render(raw, z_vals, rays_d):
     """``manipulator_render`` (networks/manipulator.py:86-105) -> (rgb_map, weights, depth_map, ins_map [N,C])."""
     raw, z, d = _lib.f32(raw), _lib.f32(z_vals), _lib.f32(rays_d)
@@ -76,14 +120,79 @@ def sort_rows(x):
     return out
 
 
-def manipulator(position_embedder, view_embedder, model_coarse, model_fine, ori_rays, f_tar_rays, args, us=None):
+def _manipulator_edit(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, kinds, keep_labels):
+    """``manipulator`` with edit kinds: the chain below with ``edit_exchanger`` in place of ``exchanger``, the target side run for
+    the ``T_r`` entries that have rays (MOVE and COPY) only, and the original's fine network on the merged depths evaluated once."""
+    from .. import weights
+    split = weights.split_mode(args)
+    N_samples, N_importance, near, far = args.N_samples, args.N_importance, args.near, args.far
+    labels = [int(v) for v in args.target_labels]
+    kinds = [MOVE] * len(labels) if kinds is None else [int(k) for k in kinds]
+    if len(kinds) != len(labels):
+        raise ValueError(f"manipulator: {len(kinds)} kinds for {len(labels)} target labels")
+    if any(k not in (MOVE, COPY, REMOVE) for k in kinds):
+        raise ValueError(f"manipulator: kinds must be MOVE (0), COPY (1) or REMOVE (2), got {kinds}")
+    has_rays = [k != REMOVE for k in kinds]
+    if len(f_tar_rays) != sum(has_rays):
+        raise ValueError(f"manipulator: {len(f_tar_rays)} target ray sets for {sum(has_rays)} MOVE / COPY entries")
+    if not labels and keep_labels is None:
+        raise ValueError("manipulator: no edit and no keep_labels")
+    dev = ori_rays.device
+    Nr = ori_rays.shape[1]
+    us = list(us) if us is not None else None
+    draw = lambda: _lib.f32(us.pop(0)) if us is not None else torch.rand([Nr, N_importance], device=dev)
+    ori_raw, ori_z = manipulator_nerf(ori_rays, None, None, model_coarse, N_samples, near, far, split=split)
+    _, ori_w, _, _ = manipulator_render(ori_raw, ori_z, ori_rays[1])
+    ori_z_full = helpers.importance_resample(ori_z, ori_w, N_importance, u=draw())
+    ori_raw_full, _ = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z_full, split=split)
+    _, _, _, ori_ins_accum = manipulator_render(ori_raw_full, ori_z_full, ori_rays[1])
+    tar_raws, f_tar_z, f_tar_zs, tar_ins_accums = [], [], [], []
+    tar_rgb = tar_ins_accum = None
+    for tar_rays in f_tar_rays:
+        tar_raw, tar_z = manipulator_nerf(tar_rays, None, None, model_coarse, N_samples, near, far, split=split)
+        tar_raws.append(tar_raw); f_tar_z.append(tar_z)
+        tar_rgb, tar_w, _, _ = manipulator_render(tar_raw, tar_z, tar_rays[1])
+        tar_z_full, tar_zs = helpers.importance_resample(tar_z, tar_w, N_importance, u=draw(), return_samples=True)
+        tar_raw_full, _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z_full, split=split)
+        _, _, _, tar_ins_accum = manipulator_render(tar_raw_full, tar_z_full, tar_rays[1])
+        f_tar_zs.append(tar_zs); tar_ins_accums.append(tar_ins_accum)
+
+    def per_edit(with_rays):                    # one slot per edit: the next ray entry's tensor, None for a REMOVE
+        it = iter(with_rays)
+        return [next(it) if h else None for h in has_rays]
+    accs = per_edit(tar_ins_accums)
+    ori_raw, _ = edit_exchanger(ori_raw, per_edit(tar_raws), ori_ins_accum, accs, labels, kinds, keep_labels, want_label=False)
+    _, ori_w, _, _ = manipulator_render(ori_raw, ori_z, ori_rays[1])
+    _, ori_zs = helpers.importance_resample(ori_z, ori_w, N_importance, u=draw(), return_samples=True)
+    ori_z = sort_rows(torch.cat([ori_z, ori_zs] + f_tar_zs, dim=-1))
+    ori_raw, _ = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z, split=split)
+    for idx, tar_rays in enumerate(f_tar_rays):
+        tar_z = sort_rows(torch.cat([f_tar_z[idx], ori_zs] + f_tar_zs, dim=-1))
+        tar_raws[idx], _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z, split=split)
+    ori_raw, _ = edit_exchanger(ori_raw, per_edit(tar_raws), ori_ins_accum, accs, labels, kinds, keep_labels, want_label=False)
+    final_rgb, _, _, final_ins = manipulator_render(ori_raw, ori_z, ori_rays[1])
+    if not f_tar_rays:
+        tar_rgb, tar_ins_accum = torch.zeros_like(final_rgb), torch.zeros_like(final_ins)
+    return final_rgb, final_ins, tar_rgb, tar_ins_accum
+
+
+def manipulator(position_embedder, view_embedder, model_coarse, model_fine, ori_rays, f_tar_rays, args, us=None, kinds=None,
+                keep_labels=None):
     """``manipulator`` (networks/manipulator.py:137-205) -> (final_rgb, final_ins, tar_rgb, tar_ins_accum).
+
+    ``kinds`` / ``keep_labels`` (extension; both ``None``: the reference's chain below, unchanged): ``kinds[e]`` in ``MOVE``,
+    ``COPY``, ``REMOVE`` for ``args.target_labels[e]``; ``f_tar_rays`` then holds rays only for the ``T_r`` MOVE and COPY entries, in
+    order, the draws are ``2 + T_r`` (original, each target, original again) and the merged depth row has ``64 + 128 + 128 T_r``
+    samples: a removal alone costs one coarse and two fine launches of the original rays.  ``keep_labels``: only samples whose own
+    label is in the set survive (``edit_exchanger``).  With ``T_r == 0`` ``tar_rgb`` and ``tar_ins_accum`` are zeros.
 
     RNG: the reference calls ``sample_pdf(..., det=False)`` even at evaluation (:148,:170,:187): ``2 + T`` draws
     of ``torch.rand([N, N_importance])`` in the order original, each target, original again; the same draws are
     made here on the rays' device, or pass them as ``us`` (extension used by the tests).  ``args.mfma_split`` (extension, default
     off) evaluates the 3 + 4 T network launches on the opt-in split-operand kernels, as in ``dm_nerf``.
     """
+    if kinds is not None or keep_labels is not None:
+        return _manipulator_edit(model_coarse, model_fine, ori_rays, list(f_tar_rays), args, us, kinds, keep_labels)
     from .. import weights
     split = weights.split_mode(args)
     N_samples, N_importance, near, far = args.N_samples, args.N_importance, args.near, args.far

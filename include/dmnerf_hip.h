@@ -369,6 +369,21 @@ int dmnerf_sort_rows(const float* d_in, int64_t N, int K, float* d_out, void* st
 int dmnerf_exchanger(float* d_ori_raw, const float* const* h_tar_raws, const float* d_ori_acc,
                      const float* const* h_tar_accs, const int* h_labels, int T, int64_t N, int S, int C,
                      int64_t* d_ori_label, int64_t* d_tar_label, void* stream);
+/* dmnerf_edit_exchange: the exchanger (networks/manipulator.py:18-83) generalised to E edits of three kinds plus a keep mask;
+ *   d_ori_raw [N,S,4+C] is edited in place.  Per (ray, sample): l0 = the sample's own label (argmax of the sigmoid over C
+ *   channels, first maximum), the ray's label from d_ori_acc [N,C] over C - 1 channels; then the edits in order, each first
+ *   applying the occlusion correction of :32-33 to the running original label for its label L = h_labels[e]:
+ *     h_kinds[e] = 0 MOVE    the loop body of dmnerf_exchanger (:30-81): fill, exchange, eliminate;
+ *                  1 COPY    the target's label corrected as for a MOVE; the row is overwritten by the target's only where the
+ *                            target sample is L and the original is not; no fill, no eliminate;
+ *                  2 REMOVE  row = row * 0.f where the original's label is L (the form of :81, so -0 and NaN arise as there);
+ *                            h_tar_raws[e] and h_tar_accs[e] must be NULL (both arrays may be NULL when every edit is a REMOVE).
+ *   h_keep (nullable): 128 label bits in two words; after the edits the row becomes row * 0.f when bit l0 is clear.
+ *   1 <= E <= 8, or E == 0 with h_keep; 2 <= C <= 128; labels in [0, C).  d_ori_label (nullable): int64 [N,S], the original's
+ *   label after the corrections.  Arguments are validated before anything touches a device; no allocation, no sync.          */
+int dmnerf_edit_exchange(float* d_ori_raw, const float* const* h_tar_raws, const float* d_ori_acc,
+                         const float* const* h_tar_accs, const int* h_labels, const int* h_kinds, int E,
+                         const uint64_t* h_keep, int64_t N, int S, int C, int64_t* d_ori_label, void* stream);
 
 /* ---- manipulator.py, the drivers around manipulator(): manipulator_eval / manipulator_demo (csrc/edit_frame.hip) --------------
  * dmnerf_edit_rays: the target rays of T edited objects (1 .. DMNERF_EDIT_MAX_OBJECTS, the exchanger's limit) for image rows
