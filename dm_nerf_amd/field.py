@@ -1,11 +1,18 @@
-"""The trained field off the camera rays: density at points, the occupancy grid and the object label of surface points.
+"""The trained field off the camera rays: density at points, the occupancy grid, its iso-surface and the object label of surface
+points.
 
-This is what the reference's ``mesh_main`` (tools/mesh_generator.py:12-143) does around its two host libraries:
+This is the reference's ``mesh_main`` (tools/mesh_generator.py:12-143) without its file output (``mesh_scene`` chains the stages):
 
     mesh_generator.py:27-63    grid_within_bound + the fine network on 256^3 points + occupancy_activation  ->  ``occupancy_grid``
-    :68-104                    skimage marching cubes, trimesh, open3d clean_mesh                             (stay on the host)
+    :68-69                     skimage marching cubes at level 0.45 (classic table here)       ->  ``extract_surface``
+    :71-86, :100               the canonical transform of trimesh                                            ->  ``scene_vertices``
+    :93-94                     trimesh_to_open3d's compute_vertex_normals                                    ->  ``vertex_normals``
+    :98-104                    open3d clean_mesh(min_num_cluster=400), remove_unreferenced_vertices          ->  ``clean_surface``
     :106-136                   one ray per vertex against its normal, dm_nerf, argmax                        ->  ``label_points``
     :137                       render_label2world (tools/visualizer.py:208-223)                              ->  ``label_colors``
+    :89, :140                  the two .ply files                                                            ->  ``write_ply`` (host)
+
+The surface stages are csrc/surface.hip; only the vertex and triangle totals that size the outputs reach the host.
 
 The density depends on neither the view direction nor the heads, so the grid goes through the trunk-only kernel
 (csrc/mlp_fwd_points.hip): no ``[n, 90]`` embedding, no heads, no point tensor, no ``torch.cat`` and no host copy.  Tensors
@@ -196,3 +203,199 @@ def label_colors(labels, rgbs, color_dict, ins_map):
     flat = labels.reshape(-1)
     idx = torch.where((flat >= 0) & (flat < n), flat, torch.full_like(flat, n))
     return lut[idx]
+
+
+# ---- the iso-surface: mesh_generator.py:68-104 on the device (csrc/surface.hip; tests/_surface_restate.py states it in numpy)
+def _empty_surface(device):
+    return torch.zeros(0, 3, dtype=torch.float32, device=device), torch.zeros(0, 3, dtype=torch.int32, device=device)
+
+
+def extract_surface(occ, level=0.45):
+    """Marching cubes of ``occ [dx, dy, dz]`` at ``level`` (mesh_generator.py:68) -> ``(vertices [V, 3] f32 in index units, faces
+    [F, 3] int32)``: the classic 256-case triangulation, a point inside iff ``v > level``, a vertex at ``i + (level - a) / (b - a)``
+    in f32, winding of ``gradient_direction='ascent'``.  Vertices are ordered by (owning grid point, axis), triangles by (cell,
+    table position).  Everything stays on the device; the two totals that size the outputs are the only values the host reads.  An
+    empty surface gives ``[0, 3]`` tensors."""
+    occ = _lib.f32(occ)
+    _lib.require_gpu(occ)
+    if occ.dim() != 3:
+        raise ValueError(f"extract_surface expects occ [dx, dy, dz], got {tuple(occ.shape)}")
+    dx, dy, dz = occ.shape
+    n = occ.numel()
+    lib, stream = _lib.load(), _lib.stream()
+    counts = torch.empty(2, max(n, 1), dtype=torch.uint8, device=occ.device)
+    _lib.check(lib.dmnerf_surface_count(_lib.ptr(occ), dx, dy, dz, float(level), _lib.ptr(counts[0]), _lib.ptr(counts[1]), stream),
+               "dmnerf_surface_count")
+    scans = torch.cumsum(counts, dim=1, dtype=torch.int64)
+    V, F = scans[:, -1].tolist()
+    if V >= 2 ** 31 or F >= 2 ** 31:
+        raise ValueError(f"extract_surface: {V} vertices / {F} triangles do not fit int32 ids")
+    if V == 0:
+        return _empty_surface(occ.device)
+    vertices = torch.empty(V, 3, dtype=torch.float32, device=occ.device)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=occ.device)
+    _lib.check(lib.dmnerf_surface_emit(_lib.ptr(occ), dx, dy, dz, float(level), _lib.ptr(counts[0]), _lib.ptr(counts[1]),
+                                       _lib.ptr(scans[0]), _lib.ptr(scans[1]), V, F, _lib.ptr(vertices), _lib.ptr(faces), stream),
+               "dmnerf_surface_emit")
+    return vertices, faces
+
+
+def scene_vertices(vertices, dim, transform, extents=(1.9, 7.0, 7.0)):
+    """Index units -> scene coordinates, mesh_generator.py:72-86 and :100: ``/ (dim - 1)`` (``dim = occ.shape[0]``, as there),
+    translate -0.5, scale 2, scale by ``extents / 2``, apply the 4 x 4 ``transform``; float64 torch ops on ``[V, 3]`` where the
+    vertices live, rounded once to f32."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"scene_vertices expects vertices [V, 3], got {tuple(vertices.shape)}")
+    if int(dim) < 2:
+        raise ValueError("dim must be >= 2")
+    T = torch.as_tensor(np.asarray(transform.detach().cpu() if torch.is_tensor(transform) else transform, dtype=np.float64))
+    if T.shape != (4, 4):
+        raise ValueError("transform must be 4 x 4")
+    T = T.to(vertices.device)
+    half = torch.as_tensor(np.asarray(extents, dtype=np.float64) / 2.0, device=vertices.device)
+    if half.shape != (3,):
+        raise ValueError("extents must have 3 entries")
+    v = vertices.double() / (int(dim) - 1)
+    v = ((v + (-0.5)) * 2.0) * half
+    v = v @ T[:3, :3].T + T[:3, 3]
+    return v.float()
+
+
+def _mesh_args(vertices, faces, normals=None):
+    v = _lib.f32(vertices)
+    _lib.require_gpu(v, faces, normals)
+    if v.dim() != 2 or v.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"expected vertices [V, 3] f32 and faces [F, 3] int32, got {tuple(v.shape)} and {tuple(faces.shape)} {faces.dtype}")
+    if normals is not None and (normals.shape != v.shape or normals.dtype != torch.float32):
+        raise ValueError("normals must be [V, 3] f32")
+    return v
+
+
+def vertex_normals(vertices, faces, occ_shape=None):
+    """The vertex normals of ``trimesh_to_open3d`` -> ``compute_vertex_normals()`` -> ``[V, 3]`` f32: per vertex the f32 sum of the
+    unnormalised ``(p1 - p0) x (p2 - p0)`` of its triangles (area weights), normalised; a zero sum stays 0.  The triangles at a vertex
+    are those of the <= 4 cells round its grid edge; they are summed in ascending triangle index, which for ``extract_surface``'s
+    order is ascending cell index and table order.  A gather over the stably sorted incidence list: no float atomics, the same bits
+    every run.  ``occ_shape``, when given, only checks that the mesh can have come from such a grid."""
+    v = _mesh_args(vertices, faces)
+    V, F = v.shape[0], faces.shape[0]
+    if occ_shape is not None and V > 3 * int(np.prod(occ_shape)):
+        raise ValueError(f"{V} vertices cannot come from a grid of shape {tuple(occ_shape)}")
+    normals = torch.zeros(V, 3, dtype=torch.float32, device=v.device)
+    if V == 0 or F == 0:
+        return normals
+    inc_vertex, inc_slot = torch.sort(faces.reshape(-1), stable=True)
+    _lib.check(_lib.load().dmnerf_surface_normals(_lib.ptr(v), V, _lib.ptr(faces), F, _lib.ptr(inc_vertex), _lib.ptr(inc_slot),
+                                                  _lib.ptr(normals), _lib.stream()), "dmnerf_surface_normals")
+    return normals
+
+
+def surface_clusters(faces):
+    """``cluster_connected_triangles``: two triangles are connected iff they share a mesh edge (the same unordered vertex pair) ->
+    ``(rep [F] int32, size [F] int32)``: the smallest triangle index of every triangle's cluster and that cluster's triangle count."""
+    _lib.require_gpu(faces)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"surface_clusters expects faces [F, 3] int32, got {tuple(faces.shape)} {faces.dtype}")
+    rep, count = _clusters(faces)
+    return rep, count[rep.long()]
+
+
+def _clusters(faces):
+    F = faces.shape[0]
+    rep = torch.empty(F, dtype=torch.int32, device=faces.device)
+    count = torch.zeros(F, dtype=torch.int32, device=faces.device)
+    if F == 0:
+        return rep, count
+    a, b = faces.long(), faces[:, [1, 2, 0]].long()
+    key, slot = torch.sort(((torch.minimum(a, b) << 32) | torch.maximum(a, b)).reshape(-1))
+    parent = torch.arange(F, dtype=torch.int32, device=faces.device)
+    _lib.check(_lib.load().dmnerf_surface_clusters(_lib.ptr(key), _lib.ptr(slot), F, _lib.ptr(parent), _lib.ptr(rep), _lib.ptr(count),
+                                                   _lib.stream()), "dmnerf_surface_clusters")
+    return rep, count
+
+
+def clean_surface(vertices, normals, faces, min_triangles=400, keep_single_cluster=False):
+    """``clean_mesh`` (tools/visualizer.py) and ``remove_unreferenced_vertices`` -> ``(vertices, normals, faces, kept_vertex_index
+    [V'] int64)``: triangles whose cluster has fewer than ``min_triangles`` triangles go (with ``keep_single_cluster`` all but the
+    largest cluster, ties to the smallest representative), then the vertices nobody references; both compactions keep the order and
+    re-index the faces; the normals travel with their vertices."""
+    v = _mesh_args(vertices, faces, normals)
+    V, F = v.shape[0], faces.shape[0]
+    dev = v.device
+    rep, count = _clusters(faces)
+    single = torch.argmax(count).reshape(1) if keep_single_cluster and F else None        # first maximum: the smallest representative
+    keep = torch.zeros(F, dtype=torch.uint8, device=dev)
+    used = torch.zeros(V, dtype=torch.uint8, device=dev)
+    lib, stream = _lib.load(), _lib.stream()
+    _lib.check(lib.dmnerf_surface_clean_mark(_lib.ptr(faces), F, V, _lib.ptr(rep), _lib.ptr(count), int(min_triangles), _lib.ptr(single),
+                                             _lib.ptr(keep), _lib.ptr(used), stream), "dmnerf_surface_clean_mark")
+    fscan = torch.cumsum(keep, dim=0, dtype=torch.int32)
+    vscan = torch.cumsum(used, dim=0, dtype=torch.int32)
+    Fk, Vk = torch.stack([fscan[-1] if F else fscan.sum(), vscan[-1] if V else vscan.sum()]).tolist()
+    out_v = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+    out_n = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(Fk, 3, dtype=torch.int32, device=dev)
+    kept = torch.empty(Vk, dtype=torch.int64, device=dev)
+    _lib.check(lib.dmnerf_surface_clean_compact(_lib.ptr(v), _lib.ptr(normals), _lib.ptr(faces), V, F, _lib.ptr(keep), _lib.ptr(used),
+                                                _lib.ptr(fscan), _lib.ptr(vscan), Vk, Fk, _lib.ptr(out_v), _lib.ptr(out_n), _lib.ptr(out_f),
+                                                _lib.ptr(kept), stream), "dmnerf_surface_clean_compact")
+    return out_v, out_n, out_f, kept
+
+
+def mesh_scene(models, transform, args, ins_rgbs=None, color_dict=None, ins_map=None, grid_dim=256, level=0.45, min_triangles=400,
+               **grid_kw):
+    """``mesh_main`` (mesh_generator.py:12-143) without its file output: ``occupancy_grid`` -> ``extract_surface`` ->
+    ``scene_vertices`` -> ``vertex_normals`` -> ``clean_surface`` -> ``label_points`` (-> ``label_colors`` when ``ins_rgbs``,
+    ``color_dict`` and ``ins_map`` are given).  Returns a namespace with ``vertices``, ``faces``, ``normals``, ``labels``, ``conf``,
+    ``colors`` (or None) and the uncleaned ``vertices_raw`` / ``faces_raw`` (the first ``.ply`` of the reference).  No tensor goes
+    to the host."""
+    import types
+    extents = grid_kw.get("extents", (1.9, 7.0, 7.0))
+    occ = occupancy_grid(models[1], transform, args, grid_dim=grid_dim, **grid_kw)
+    v_idx, faces_raw = extract_surface(occ, level)
+    vertices_raw = scene_vertices(v_idx, occ.shape[0], transform, extents)
+    normals_raw = vertex_normals(vertices_raw, faces_raw, occ.shape)
+    vertices, normals, faces, _ = clean_surface(vertices_raw, normals_raw, faces_raw, min_triangles=min_triangles)
+    labels, conf = label_points(vertices, normals, models, args)
+    colors = None
+    if ins_rgbs is not None and color_dict is not None and ins_map is not None:
+        colors = label_colors(labels, ins_rgbs, color_dict, ins_map)
+    return types.SimpleNamespace(vertices=vertices, faces=faces, normals=normals, labels=labels, conf=conf, colors=colors,
+                                 vertices_raw=vertices_raw, faces_raw=faces_raw)
+
+
+def write_ply(path, vertices, faces, normals=None, colors=None):
+    """Binary little-endian PLY of a mesh (the one host step): ``vertices [V, 3]`` f32, optional ``normals [V, 3]`` f32 and
+    ``colors [V, 3]`` uint8 (written as given: red = column 0), ``faces [F, 3]`` as ``uchar 3, int, int, int``."""
+    def host(t):
+        return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    v = np.ascontiguousarray(host(vertices), dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(host(faces), dtype="<i4").reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}",
+              "property float x", "property float y", "property float z"]
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    rows = np.zeros(v.shape[0], dtype=np.dtype(fields))
+    rows["x"], rows["y"], rows["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        n = np.asarray(host(normals), dtype="<f4").reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError("normals must be [V, 3]")
+        rows["nx"], rows["ny"], rows["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    if colors is not None:
+        c = np.asarray(host(colors), dtype=np.uint8).reshape(-1, 3)
+        if c.shape != v.shape:
+            raise ValueError("colors must be [V, 3]")
+        rows["red"], rows["green"], rows["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    tris = np.zeros(f.shape[0], dtype=np.dtype([("n", "u1"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4")]))
+    tris["n"], tris["a"], tris["b"], tris["c"] = 3, f[:, 0], f[:, 1], f[:, 2]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(rows.tobytes())
+        fh.write(tris.tobytes())

@@ -722,6 +722,44 @@ int dmnerf_adam_step(float* d_params, const float* d_grads, float* d_exp_avg, fl
                      double lr, const float* d_lr, double beta1, double beta2, double eps, int64_t* d_state2, void* stream);
 int dmnerf_repack_train(const dmnerf_repack_model* models, int n_models, void* stream);
 
+/* ---- the iso-surface of the occupancy grid (tools/mesh_generator.py:68-104; csrc/surface.hip) -----------------------
+ * d_occ [dx, dy, dz] f32 row-major, linear index p = (i dy + j) dz + k; every dimension >= 2 and dx dy dz < 2^31, checked with
+ * the pointers before anything is launched (-1 and a message otherwise).  A point is inside iff v > level (NaN: outside).  The
+ * classic 256-case Lorensen-Cline triangulation, degenerate triangles kept; winding of skimage's gradient_direction='ascent'.
+ * dmnerf_surface_count: d_vcount [p] = crossing edges among the (up to) three that run from p along +i, +j, +k (0..3); d_tcount [p]
+ *   = triangles of the cell whose lowest corner is p (0..5; 0 where p is on an upper border).  The caller forms the INCLUSIVE prefix
+ *   sums d_vscan / d_tscan [p] int64 of the two (their last entries are V and F, the only values a host needs).
+ * dmnerf_surface_emit: d_vertices [V, 3] f32 in index units, ordered by (owning point, axis): on the edge between a = occ[p] and b at
+ *   the next point, i + t along that axis with t = (level - a) / (b - a) in f32.  d_faces [F, 3] int32, ordered by (cell, position
+ *   in the case's table row); a vertex id is the owner's scan - count + the rank of the axis among the owner's crossing edges,
+ *   recomputed from the grid.
+ * dmnerf_surface_normals: d_normals [V, 3] = normalise(sum over the triangles at the vertex, in ascending triangle index, of
+ *   (p1 - p0) x (p2 - p0)), every operation in f32, length sqrt((x x + y y) + z z); a zero sum stays 0.  d_inc_vertex [3 F] int32 is
+ *   d_faces flattened and STABLY sorted, d_inc_slot [3 F] int64 the position in flattened d_faces of each sorted entry.
+ * dmnerf_surface_clusters: two triangles are connected iff they share an unordered vertex pair.  d_edge_key [3 F] int64 sorted
+ *   (min << 32 | max of the two ends of each triangle side), d_edge_slot [3 F] the side 3 f + s of each sorted entry; d_parent [F]
+ *   int32 must hold 0..F-1 and d_count [F] zeros on entry.  d_rep [f] = the smallest triangle of f's cluster, d_count [r] = the
+ *   size of the cluster that r represents (0 for a non-representative).  Integer atomics only; the result is order-independent.
+ * dmnerf_surface_clean_mark: d_keep [f] = d_count[d_rep[f]] >= min_triangles, or with d_single (device int64, nullable) d_rep[f] ==
+ *   *d_single; d_used [v] = 1 for every vertex of a kept triangle (d_used must be zero on entry).
+ * dmnerf_surface_clean_compact: with the inclusive int32 prefix sums d_fscan / d_vscan of d_keep / d_used (Fk, Vk their totals),
+ *   the kept triangles re-indexed and the used vertices with their normals, both in their original order; d_out_kept [Vk] int64 =
+ *   the original index of every kept vertex.                                                                              */
+int dmnerf_surface_count(const float* d_occ, int dx, int dy, int dz, float level, uint8_t* d_vcount, uint8_t* d_tcount, void* stream);
+int dmnerf_surface_emit(const float* d_occ, int dx, int dy, int dz, float level, const uint8_t* d_vcount, const uint8_t* d_tcount,
+                        const int64_t* d_vscan, const int64_t* d_tscan, int64_t V, int64_t F, float* d_vertices, int32_t* d_faces,
+                        void* stream);
+int dmnerf_surface_normals(const float* d_vertices, int64_t V, const int32_t* d_faces, int64_t F, const int32_t* d_inc_vertex,
+                           const int64_t* d_inc_slot, float* d_normals, void* stream);
+int dmnerf_surface_clusters(const int64_t* d_edge_key, const int64_t* d_edge_slot, int64_t F, int32_t* d_parent, int32_t* d_rep,
+                            int32_t* d_count, void* stream);
+int dmnerf_surface_clean_mark(const int32_t* d_faces, int64_t F, int64_t V, const int32_t* d_rep, const int32_t* d_count,
+                              int min_triangles, const int64_t* d_single, uint8_t* d_keep, uint8_t* d_used, void* stream);
+int dmnerf_surface_clean_compact(const float* d_vertices, const float* d_normals, const int32_t* d_faces, int64_t V, int64_t F,
+                                 const uint8_t* d_keep, const uint8_t* d_used, const int32_t* d_fscan, const int32_t* d_vscan, int64_t Vk,
+                                 int64_t Fk, float* d_out_vertices, float* d_out_normals, int32_t* d_out_faces, int64_t* d_out_kept,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
