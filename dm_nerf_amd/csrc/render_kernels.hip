@@ -71,6 +71,13 @@ __device__ __forceinline__ void lds_sync_wave() {
 
 __device__ __forceinline__ float sigmoidf_ref(float x) { return 1.f / (1.f + expf(-x)); }
 
+// exp(x) of the compositing pass, rounded to float once (through double).  The device expf is good to 1 ulp; ATen's is almost
+// always the correctly rounded float.  One factor (1 - alpha) hardly shows the difference, but the transmittance is a product of up
+// to MAX_S of them: at S = 1280 the weights of a thin ray came out 47 ulp of the ray's largest weight from their float64 values,
+// where the reference's own float32 arithmetic stays within 8 (tests/test_gpu_ray_edges.py).  The forward, the weights-only pass
+// and both passes of the backward call this one function: they must form the same floats.
+__device__ __forceinline__ float expf_rn(float x) { return (float)exp((double)x); }
+
 // ------------------------------------------------------------------------------------------
 // get_rays_k  (networks/helpers.py:50-61)
 // ------------------------------------------------------------------------------------------
@@ -167,7 +174,7 @@ __device__ __forceinline__ double ray_weights(const float* __restrict__ sig, int
             float dist = (s == S - 1) ? 1e10f : zr[s + 1] - zc;
             dist = dist * nrm;
             const float sg = fmaxf(sig[(int64_t)s * sig_stride], 0.f);    // F.relu
-            alpha = 1.f - expf(-sg * dist);
+            alpha = 1.f - expf_rn(-sg * dist);
             f = (1.f - alpha) + 1e-10f;
         }
         // exclusive cumprod; ATen's CPU cumprod accumulates in double and rounds each element
@@ -330,7 +337,7 @@ __global__ __launch_bounds__(WAVE* RAYS_PER_BLOCK) void composite_bwd_kernel(
             float dist = (s == S - 1) ? 1e10f : zr[s + 1] - zc;
             dist = dist * nrm;
             const float sig = fmaxf(rr[(int64_t)s * ch + 3], 0.f);
-            alpha = 1.f - expf(-sig * dist);
+            alpha = 1.f - expf_rn(-sig * dist);
             f = (1.f - alpha) + 1e-10f;
         }
         const double incl = wave_scan_mul_d((double)f, lane);
@@ -365,7 +372,7 @@ __global__ __launch_bounds__(WAVE* RAYS_PER_BLOCK) void composite_bwd_kernel(
             dist = dist * nrm;
             const float rawsig = rr[(int64_t)s * ch + 3];
             const float sig = fmaxf(rawsig, 0.f);
-            const float e = expf(-sig * dist);            // = 1 - alpha
+            const float e = expf_rn(-sig * dist);         // = 1 - alpha
             const float f = ((1.f - (1.f - e))) + 1e-10f; // the forward's (1 - alpha) + 1e-10, bit for bit
             const float dLda = gl[s] * tl[s] - (float)R / f;
             dr[(int64_t)s * ch + 3] = rawsig > 0.f ? dLda * (dist * e) : 0.f;
@@ -898,7 +905,8 @@ extern "C" int dmnerf_composite_fwd(const float* d_raw, const float* d_z, const 
                                     float* d_ins_map, void* stream) {
     if (N < 0 || S < 1 || S > MAX_S || C < 1) return dmn_fail(DMNERF_E_ARG, "composite_fwd: bad N=%lld S=%d (max %d) C=%d", (long long)N, S, MAX_S, C);
     if (N == 0) return DMNERF_OK;
-    if (!d_raw || !d_z || !d_rays_d || !d_rgb_map || !d_weights || !d_depth_map || !d_ins_map)
+    // (C = 1: the object-code map has C - 1 = 0 columns, and an empty tensor has no storage; the kernel never touches it)
+    if (!d_raw || !d_z || !d_rays_d || !d_rgb_map || !d_weights || !d_depth_map || (C > 1 && !d_ins_map))
         return dmn_fail(DMNERF_E_ARG, "composite_fwd: null pointer");
     static DmnOncePerDevice once;
     if (int rc = ray_lds_allow(composite_kernel, once, "composite_fwd: hipFuncSetAttribute")) return rc;
@@ -975,7 +983,7 @@ extern "C" int dmnerf_composite_bwd(const float* d_raw, const float* d_z, const 
                                     const float* d_g_weights, int64_t N, int S, int C, float* d_grad_raw, void* stream) {
     if (N < 0 || S < 1 || S > MAX_S || C < 1) return dmn_fail(DMNERF_E_ARG, "composite_bwd: bad N=%lld S=%d (max %d) C=%d", (long long)N, S, MAX_S, C);
     if (N == 0) return DMNERF_OK;
-    if (!d_raw || !d_z || !d_rays_d || !d_ins_map || !d_g_rgb || !d_g_ins || !d_grad_raw)
+    if (!d_raw || !d_z || !d_rays_d || !d_g_rgb || !d_grad_raw || (C > 1 && (!d_ins_map || !d_g_ins)))      // (C = 1: see composite_fwd)
         return dmn_fail(DMNERF_E_ARG, "composite_bwd: null pointer");
     static DmnOncePerDevice once;
     if (int rc = ray_lds_allow(composite_bwd_kernel<false>, once, "composite_bwd: hipFuncSetAttribute")) return rc;
@@ -989,7 +997,7 @@ extern "C" int dmnerf_composite_pen_fwd(const float* d_raw, const float* d_z, co
                                         float* d_depth_map, float* d_ins_map, double* d_partials, void* stream) {
     if (N < 0 || S < 1 || S > MAX_S || C < 1) return dmn_fail(DMNERF_E_ARG, "composite_pen_fwd: bad N=%lld S=%d (max %d) C=%d", (long long)N, S, MAX_S, C);
     if (N == 0) return DMNERF_OK;
-    if (!d_raw || !d_z || !d_rays_d || !d_rgb_map || !d_weights || !d_depth_map || !d_ins_map || !d_partials)
+    if (!d_raw || !d_z || !d_rays_d || !d_rgb_map || !d_weights || !d_depth_map || (C > 1 && !d_ins_map) || !d_partials)   // (C = 1: see composite_fwd)
         return dmn_fail(DMNERF_E_ARG, "composite_pen_fwd: null pointer");
     PenArgs a{};
     a.raw = d_raw; a.z = d_z; a.depth = d_depth_map; a.rays_d = d_rays_d; a.N = N; a.S = S; a.C = C;
@@ -1007,7 +1015,7 @@ extern "C" int dmnerf_composite_pen_bwd(const float* d_raw, const float* d_z, co
                                         float two_deta_w_sq, float gauss_norm, float* d_grad_raw, void* stream) {
     if (N < 0 || S < 1 || S > MAX_S || C < 1) return dmn_fail(DMNERF_E_ARG, "composite_pen_bwd: bad N=%lld S=%d (max %d) C=%d", (long long)N, S, MAX_S, C);
     if (N == 0) return DMNERF_OK;
-    if (!d_raw || !d_z || !d_rays_d || !d_ins_map || !d_depth_map || !d_g_rgb || !d_g_ins || !d_g_partials || !d_grad_raw)
+    if (!d_raw || !d_z || !d_rays_d || !d_depth_map || !d_g_rgb || !d_g_partials || !d_grad_raw || (C > 1 && (!d_ins_map || !d_g_ins)))
         return dmn_fail(DMNERF_E_ARG, "composite_pen_bwd: null pointer");
     PenBwd pen{};
     pen.depth = d_depth_map; pen.g_part = d_g_partials; pen.tol = tolerance; pen.k2w = two_deta_w_sq; pen.kh = gauss_norm;

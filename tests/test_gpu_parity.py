@@ -128,7 +128,10 @@ def test_sample_pdf_golden(A, golden):
     s, inds = A.H.sample_from_cdf(bins, dev(g["cdf"]), dev(g["u_det"]))
     assert torch.equal(cpu(inds), g["inds_det"])
     assert torch.allclose(cpu(s), g["s_det"], rtol=1e-6, atol=1e-6)
-    # full sample_pdf: cdf within 1-2 ulp, indices >= 99.9 % equal, samples close where indices agree
+    # full sample_pdf: cdf within 1-2 ulp, indices >= 99.9 % equal, samples close where indices agree -- and EVERY sample, the
+    # ones whose index moved with the last bit of the cdf included, is the inverse of the cdf the kernel itself returned: indices
+    # exact and samples within 4 ulp of max|bins| of the float64 evaluation from (cdf_out, bins, u) (tests/_ray_restate.py)
+    import _ray_restate as RR
     for u_key, s_key, i_key in (("u_det", "s_det", "inds_det"), ("u_rnd", "s_rnd", "inds_rnd")):
         s, cdf, inds = A.H.sample_pdf(bins, w, 128, u=dev(g[u_key]), return_aux=True)
         s, cdf, inds = cpu(s), cpu(cdf), cpu(inds)
@@ -136,6 +139,8 @@ def test_sample_pdf_golden(A, golden):
         same = inds == g[i_key]
         assert same.float().mean() >= 0.999
         assert torch.allclose(s[same], g[s_key][same], rtol=1e-5, atol=1e-5)
+        RR.check_cdf(cdf, g["w"], "sample_pdf golden " + u_key)
+        RR.check_samples(s, inds, g["bins"], cdf, g[u_key], "sample_pdf golden " + u_key)
     # det=True path builds its own linspace
     s = cpu(A.H.sample_pdf(bins, w, 128, det=True))
     assert torch.allclose(s, g["s_det"], rtol=1e-5, atol=2e-4)
