@@ -169,6 +169,12 @@ SIGNATURES = {
     "dmnerf_ins_eval": (c_int, [c_i64, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "dmnerf_img_metrics_work_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "dmnerf_img_metrics": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_conv3x3_pack": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp]),
+    "dmnerf_conv3x3": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "dmnerf_maxpool2": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp]),
+    "dmnerf_lpips_prologue": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
+    "dmnerf_lpips_tail": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),
+    "dmnerf_lpips_work_bytes": (c_i64, [c_int, c_int, c_int]),
     "dmnerf_surface_count": (c_int, [c_vp, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp]),
     "dmnerf_surface_emit": (c_int, [c_vp, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "dmnerf_surface_normals": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),

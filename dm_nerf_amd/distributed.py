@@ -491,7 +491,7 @@ def render_frame(H, W, K, c2w, models, near, far, args, chunk=4096, n_samples=64
 
 
 def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, labels_only=False, gt_labels=None,
-                image_metrics=False, **frame_kw):
+                image_metrics=False, lpips=None, **frame_kw):
     """The pose loop of ``render_test`` (networks/tester.py:55-90) without its file output and CPU metrics: every pose of
     ``render_poses [P,3or4,4]`` through ``render_frame`` (rows sharded over the ranks, chunks of ``args.N_test`` rays),
     the ScanNet ``crop_mask`` applied as the reference applies it (:78-82: the pixels with mask 1, reshaped to
@@ -513,7 +513,11 @@ def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, l
     ``structural_similarity(..., multichannel=True, data_range=1)`` and ``peak_signal_noise_ratio(..., data_range=1)`` as
     tester.py:89-90 computes them on a host copy (``evaluator.img_metrics_device``: one call for all poses after the loop, no
     synchronisation; the scored frame is the cropped one in the ``crop_mask`` branch and must be at least 7 x 7).  ``psnr`` keeps
-    its float32 value.  The frames are complete on every rank, so every rank computes the same numbers; no collective is added."""
+    its float32 value.  The frames are complete on every rank, so every rank computes the same numbers; no collective is added.
+
+    With ``lpips=`` an ``evaluator.LPIPSVGG`` and ``gt_imgs``, also ``lpips [P]`` (float64, on the device): tester.py:91's
+    ``lpips.LPIPS(net="vgg")(rgb, gt)`` of the frame ``ssim`` scores (the cropped one in the ``crop_mask`` branch; at least
+    16 x 16), one call for all poses after the loop, no synchronisation."""
     H, W, K = hwk
     chunk = int(getattr(args, "N_test", 4096))
     n_samples = int(getattr(args, "N_samples", 64))
@@ -546,15 +550,18 @@ def render_path(render_poses, hwk, models, args, gt_imgs=None, crop_mask=None, l
         from .networks import evaluator
         gt = torch.stack([torch.as_tensor(gt_imgs[i]).to(out["rgb"]) for i in range(out["rgb"].shape[0])], 0)
         out["ssim"], out["psnr_f64"] = evaluator.img_metrics_device(out["rgb"], gt)
+    if lpips is not None and gt_imgs is not None and "rgb" in out:
+        gt = torch.stack([torch.as_tensor(gt_imgs[i]).to(out["rgb"]) for i in range(out["rgb"].shape[0])], 0)
+        out["lpips"] = lpips(out["rgb"], gt)
     return out
 
 
 def results_table(out, lpips=None):
     """The array ``render_test`` hands to ``np.savetxt`` as ``test_results.txt`` (networks/tester.py:149-157) from a
     ``render_path(..., gt_imgs=, gt_labels=, image_metrics=True)`` result: numpy float64 ``[P + 1, 9]`` with the columns PSNR, SSIM,
-    LPIPS, AP50, AP75, AP80, AP85, AP90, AP95, one row per pose and the column means as the last row.  LPIPS is not computed here
-    (its VGG weights are the reference's to load): the column is ``nan`` unless the caller passes its own ``lpips [P]``.  The one
-    host synchronisation of a whole test set."""
+    LPIPS, AP50, AP75, AP80, AP85, AP90, AP95, one row per pose and the column means as the last row.  The LPIPS column is the
+    caller's ``lpips [P]`` if given, else the result's own ``out["lpips"]`` (``render_path(..., lpips=model)``: an
+    ``evaluator.LPIPSVGG`` with the weights the caller holds), else ``nan``.  The one host synchronisation of a whole test set."""
     import numpy as np
     for key in ("psnr_f64", "ssim", "ap"):
         if key not in out:
@@ -562,9 +569,14 @@ def results_table(out, lpips=None):
     dev = torch.cat([out["psnr_f64"].double().reshape(-1, 1), out["ssim"].double().reshape(-1, 1), out["ap"].double()], 1)
     if dev.shape[1] != 8:
         raise ValueError(f"results_table: ap must be [P, 6], got {tuple(out['ap'].shape)}")
+    own = lpips is None and "lpips" in out
+    if own:                                             # (rides along in the one copy)
+        dev = torch.cat([dev, out["lpips"].double().reshape(-1, 1).to(dev.device)], 1)
     host = dev.cpu().numpy()                            # the one sync
     P = host.shape[0]
-    if lpips is None:
+    if own:
+        lp, host = host[:, 8], host[:, :8]
+    elif lpips is None:
         lp = np.full(P, np.nan)
     else:
         lp = np.asarray(lpips.detach().cpu() if isinstance(lpips, torch.Tensor) else lpips, dtype=np.float64).reshape(-1)

@@ -236,14 +236,15 @@ def _gt_colors(table, labels):
 
 
 def manipulate_eval_path(ori_poses, hwk, models, args, trans, gt_rgbs=None, gt_labels=None, ins_rgbs=None, color_dict=None,
-                         image_metrics=True, keep_maps=False, **frame_kw):
+                         image_metrics=True, keep_maps=False, lpips=None, **frame_kw):
     """The pose loop of ``manipulator_eval`` (networks/manipulator.py:233-339) for one transformation ``trans`` (4 x 4, or a
-    ``Deform``), without its file output and LPIPS: per pose one ``ManipulationFrameRenderer`` frame with ``target_labels =
+    ``Deform``), without its file output: per pose one ``ManipulationFrameRenderer`` frame with ``target_labels =
     [args.target_label]`` (:231), then on the device
 
     * ``rgb8``, ``tar_rgb8`` uint8 ``[P,H,W,3]``: the edited frame and the plain target render (:310-318);
     * given ``gt_rgbs [P,H,W,3]``: ``psnr [P]`` (float32) and, with ``image_metrics``, ``psnr_f64`` / ``ssim`` of the edited frame
-      (:278-279, ``evaluator.img_metrics_device``: one call for all poses after the loop);
+      (:278-279, ``evaluator.img_metrics_device``: one call for all poses after the loop); with ``lpips=`` an
+      ``evaluator.LPIPSVGG`` also ``lpips [P]`` (float64) of the edited frame (:280);
     * given ``gt_labels [P,H,W]``: ``ap [P,6]``, ``matched [P,ins_num]``, ``gt_num [P]`` of ``ins[..., :-1]`` against the rows
       ``unique(gt_label)`` (:287-297: the branch of ``render_path`` without a crop); with ``ins_rgbs`` and ``color_dict`` also
       ``label [P,H,W]`` (argmax over ALL channels, :321), ``ins_img`` coloured through that pose's own matching (:299-323:
@@ -251,16 +252,17 @@ def manipulate_eval_path(ori_poses, hwk, models, args, trans, gt_rgbs=None, gt_l
       (``render_gt_label2img``, :327).  A gt label that ``color_dict`` does not hold is black (the reference raises ``KeyError``).
 
     ``keep_maps=True`` adds the float frames ``rgb, ins, tar_rgb, tar_ins``.  ``distributed.results_table`` takes the result as it
-    is (LPIPS ``nan`` unless passed).  The frames are complete on every rank: every rank computes the same numbers."""
+    is (LPIPS from ``out["lpips"]``, ``nan`` without a model).  The frames are complete on every rank: every rank computes the same numbers."""
     H, W, K = hwk
     cols = {}
     table = None
     scored = image_metrics and gt_rgbs is not None
+    perceptual = lpips is not None and gt_rgbs is not None
     for i, pose in enumerate(ori_poses):
         rgb, ins, tar_rgb, tar_ins = _render(H, W, K, pose, [trans], models, args, frame_kw)
         cols.setdefault("rgb8", []).append(frame_products(rgb)[0])
         cols.setdefault("tar_rgb8", []).append(frame_products(tar_rgb)[0])
-        if keep_maps or scored:
+        if keep_maps or scored or perceptual:
             cols.setdefault("rgb", []).append(rgb)
         if keep_maps:
             for name, t in zip(MAP_NAMES[1:], (ins, tar_rgb, tar_ins)):
@@ -285,10 +287,13 @@ def manipulate_eval_path(ori_poses, hwk, models, args, trans, gt_rgbs=None, gt_l
                 for name, t in zip(("label", "ins_img", "gt_ins_img"), (label, ins_img, _gt_colors(table, gl))):
                     cols.setdefault(name, []).append(t)
     out = {k: torch.stack(v, 0) for k, v in cols.items()}
+    if scored or perceptual:
+        gt = torch.stack([torch.as_tensor(gt_rgbs[i]).to(out["rgb"]) for i in range(out["rgb"].shape[0])], 0)
     if scored:
         from .networks import evaluator
-        gt = torch.stack([torch.as_tensor(gt_rgbs[i]).to(out["rgb"]) for i in range(out["rgb"].shape[0])], 0)
         out["ssim"], out["psnr_f64"] = evaluator.img_metrics_device(out["rgb"], gt)
-    if scored and not keep_maps:
+    if perceptual:
+        out["lpips"] = lpips(out["rgb"], gt)
+    if (scored or perceptual) and not keep_maps:
         del out["rgb"]
     return out

@@ -7,7 +7,8 @@ the file runs on the device too: the per-pixel label / confidence every rendered
 instance AP of a frame (``ins_eval``, ``ins_eval_device``: csrc/ins_eval.hip).  ``calculate_ap`` on its own has no device
 version: the AP integral is the last step of the ``ins_eval`` kernel, which works on counts, not on an IoU vector.
 The two image scores of ``render_test`` that the reference takes from ``skimage.metrics`` on a host copy of the frame
-(tester.py:89-90) are ``img_metrics_device`` / ``ssim`` / ``psnr`` (csrc/img_metrics.hip).
+(tester.py:89-90) are ``img_metrics_device`` / ``ssim`` / ``psnr`` (csrc/img_metrics.hip), and the third, ``lpips.LPIPS(net="vgg")``
+(tester.py:43,91), is ``LPIPSVGG`` / ``lpips`` (csrc/conv3x3.hip, csrc/lpips.hip) with weights the caller hands over.
 """
 import torch
 
@@ -260,3 +261,223 @@ def psnr(pred, gt):
     if pred.dim() != 3:
         raise ValueError("psnr: one [H,W,C] frame")
     return float(img_metrics_device(pred, gt)[1])
+
+
+# ---- LPIPS (VGG16): lpips.LPIPS(net="vgg") of tester.py:43,91 and manipulator.py:216,280 ------------------------------------------
+# (index in torchvision's vgg16().features, slice of lpips' wrapper, Cin, Cout); a 2x2 max-pool precedes each slice but the first,
+# and each slice's last ReLU is tapped.
+LPIPS_VGG_CONVS = ((0, 1, 3, 64), (2, 1, 64, 64), (5, 2, 64, 128), (7, 2, 128, 128), (10, 3, 128, 256), (12, 3, 256, 256),
+                   (14, 3, 256, 256), (17, 4, 256, 512), (19, 4, 512, 512), (21, 4, 512, 512), (24, 5, 512, 512), (26, 5, 512, 512),
+                   (28, 5, 512, 512))
+LPIPS_VGG_TAPS = (64, 128, 256, 512, 512)
+LPIPS_MIN_SIZE = 16
+
+
+def lpips_parse_state_dicts(vgg_sd, lin_sd, conv_key):
+    """The 13 ``(weight [Cout,Cin,3,3], bias [Cout])`` pairs and the 5 ``lin`` weights (``[1,C,1,1]``) out of the mappings, shapes
+    checked: ``ValueError`` naming the key that is missing or misshapen.  ``conv_key(idx, slice, 'weight' | 'bias')`` names a
+    convolution's entry.  Needs no device and no library."""
+    convs, lins = [], []
+    for idx, sl, cin, cout in LPIPS_VGG_CONVS:
+        pair = []
+        for kind, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
+            key = conv_key(idx, sl, kind)
+            if key not in vgg_sd:
+                raise ValueError(f"LPIPSVGG: state dict has no '{key}'")
+            t = vgg_sd[key]
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+                raise ValueError(f"LPIPSVGG: '{key}' must be a tensor of shape {shape}, got {tuple(getattr(t, 'shape', ()))}")
+            pair.append((key, t))
+        convs.append(tuple(pair))
+    for k, c in enumerate(LPIPS_VGG_TAPS):
+        key = f"lin{k}.model.1.weight"
+        if key not in lin_sd:
+            raise ValueError(f"LPIPSVGG: state dict has no '{key}'")
+        t = lin_sd[key]
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (1, c, 1, 1):
+            raise ValueError(f"LPIPSVGG: '{key}' must be a tensor of shape {(1, c, 1, 1)}, got {tuple(getattr(t, 'shape', ()))}")
+        lins.append((key, t))
+    return convs, lins
+
+
+def lpips_parse_state_dict(sd):
+    """``lpips.LPIPS(net='vgg').state_dict()``'s form: ``net.slice{1..5}.{idx}.{weight,bias}`` and ``lin{0..4}.model.1.weight``; the
+    ``lins.{k}...`` duplicates and ``scaling_layer.*`` are ignored."""
+    return lpips_parse_state_dicts(sd, sd, lambda idx, sl, kind: f"net.slice{sl}.{idx}.{kind}")
+
+
+def lpips_parse_torchvision(vgg_sd, lin_sd):
+    """torchvision's ``vgg16().state_dict()`` (``features.{idx}.{weight,bias}``; the classifier is ignored) plus the ``lin`` weights."""
+    return lpips_parse_state_dicts(vgg_sd, lin_sd, lambda idx, sl, kind: f"features.{idx}.{kind}")
+
+
+def _pf_rows(n, h, w):
+    """Rows of a padded-flat buffer of ``n`` images ``h x w`` (include/dmnerf_hip.h): bordered images plus the two guards."""
+    return n * (h + 2) * (w + 2) + 2 * (w + 3)
+
+
+def conv3x3_pack(weight):
+    """``dmnerf_conv3x3_pack``: a ``[Cout,Cin,3,3]`` float32 device tensor as the kernel's ``[Cout][9 Cin -> 32]`` matrix."""
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    ldb = (9 * cin + 31) // 32 * 32
+    w = weight.detach().contiguous()
+    out = torch.empty(cout, ldb, dtype=torch.float32, device=w.device)
+    lib = _lib.load()
+    _lib.check(lib.dmnerf_conv3x3_pack(_lib.ptr(w), cout, cin, _lib.ptr(out), ldb, _lib.stream()), "dmnerf_conv3x3_pack")
+    return out
+
+
+def padded_flat(x):
+    """``x [N,H,W,C]`` as a padded-flat buffer ``[rows, C]`` (a host-side helper for tests and timing: plain torch copies)."""
+    n, h, w, c = x.shape
+    buf = torch.zeros(_pf_rows(n, h, w), c, dtype=x.dtype, device=x.device)
+    buf[w + 3:w + 3 + n * (h + 2) * (w + 2)].view(n, h + 2, w + 2, c)[:, 1:-1, 1:-1] = x
+    return buf
+
+
+def padded_flat_images(buf, n, h, w):
+    """The ``[N,H+2,W+2,C]`` view (borders included) of a padded-flat buffer."""
+    return buf[w + 3:w + 3 + n * (h + 2) * (w + 2)].view(n, h + 2, w + 2, buf.shape[1])
+
+
+def conv3x3(x_pf, packed, bias, n, h, w, relu=True, out=None):
+    """``dmnerf_conv3x3`` (taps = 9) on a padded-flat ``[rows, Cin]`` buffer of ``n`` images ``h x w``: the padded-flat
+    ``[rows, Cout]`` output, borders and guards exactly zero."""
+    cin, cout = int(x_pf.shape[1]), int(packed.shape[0])
+    if out is None:
+        out = torch.empty(_pf_rows(n, h, w), cout, dtype=torch.float32, device=x_pf.device)
+    lib = _lib.load()
+    _lib.check(lib.dmnerf_conv3x3(_lib.ptr(x_pf), x_pf.numel(), _lib.ptr(packed), packed.numel(), _lib.ptr(bias), _lib.ptr(out), out.numel(),
+                                  n, h, w, cin, cout, 9, 1 if relu else 0, _lib.stream()), "dmnerf_conv3x3")
+    return out
+
+
+def maxpool2(x_pf, n, h, w):
+    """``dmnerf_maxpool2``: padded-flat ``n`` images ``h x w`` -> padded-flat ``h // 2 x w // 2``."""
+    c = int(x_pf.shape[1])
+    out = torch.empty(_pf_rows(n, h // 2, w // 2), c, dtype=torch.float32, device=x_pf.device)
+    lib = _lib.load()
+    _lib.check(lib.dmnerf_maxpool2(_lib.ptr(x_pf), x_pf.numel(), _lib.ptr(out), out.numel(), n, h, w, c, _lib.stream()), "dmnerf_maxpool2")
+    return out
+
+
+class LPIPSVGG:
+    """``lpips.LPIPS(net="vgg")`` (lpips 0.1.4, version 0.1, ``spatial=False``) on the device, with weights the caller already holds:
+
+        model = LPIPSVGG.from_state_dict(their_lpips_module.state_dict())        # or from_state_dicts(vgg16_sd, lin_sd)
+        d = model(pred, gt)                                                      # [P,H,W,3] or [H,W,3] float32 device tensors
+
+    Nothing here constructs ``lpips.LPIPS`` or a torchvision model (those constructors fetch weights).  The thirteen convolutions are
+    csrc/conv3x3.hip, the scaling layer, pooling and the tail csrc/lpips.hip.  Weights are packed once at construction; the
+    workspace is cached per ``(P, H, W)``.  The result is float64 ``[P]`` (0-d for one frame), with no host synchronisation; the
+    call is capturable once its workspace exists, bit-identical from run to run and independent of ``P``."""
+
+    def __init__(self, convs, lins):
+        dev = None
+        for pair in list(convs) + [(l,) for l in lins]:
+            for key, t in pair:
+                if not t.is_cuda:
+                    raise ValueError(f"LPIPSVGG: '{key}' must be a device tensor (there is no CPU path)")
+                if dev is None:
+                    dev = t.device
+                elif t.device != dev:
+                    raise ValueError(f"LPIPSVGG: '{key}' is on {t.device}, other weights on {dev}")
+        self.device = dev
+        with torch.cuda.device(dev):
+            self.packed = [conv3x3_pack(w.detach().float()) for (_, w), _ in convs]
+            self.bias = [b.detach().float().contiguous().clone() for _, (_, b) in convs]
+            self.lin = [t.detach().float().reshape(-1).contiguous().clone() for _, t in lins]
+        self._work = {}
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        return cls(*lpips_parse_state_dict(sd))
+
+    @classmethod
+    def from_state_dicts(cls, vgg_sd, lin_sd):
+        return cls(*lpips_parse_torchvision(vgg_sd, lin_sd))
+
+    def _workspace(self, P, H, W):
+        key = (P, H, W)
+        ws = self._work.get(key)
+        if ws is None:
+            lib = _lib.load()
+            nbytes = lib.dmnerf_lpips_work_bytes(P, H, W)
+            if nbytes < 0:
+                raise ValueError(f"LPIPSVGG: unsupported P={P} H={H} W={W} (H, W in {LPIPS_MIN_SIZE} .. 4096)")
+            al = lambda b: (b + 255) // 256 * 256
+            m = 2 * P * (H + 2) * (W + 2)
+            n_taps, n_act = m * 32, _pf_rows(2 * P, H, W) * 64
+            n_part = P * ((H * W + 255) // 256)
+            assert al(4 * n_taps) + 2 * al(4 * n_act) + al(8 * n_part) == nbytes, "workspace layout out of step with dmnerf_lpips_work_bytes"
+            raw = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            o1 = al(4 * n_taps)
+            o2 = o1 + al(4 * n_act)
+            o3 = o2 + al(4 * n_act)
+            ws = dict(raw=raw, taps=raw[:4 * n_taps].view(torch.float32), a=raw[o1:o1 + 4 * n_act].view(torch.float32),
+                      b=raw[o2:o2 + 4 * n_act].view(torch.float32), part=raw[o3:o3 + 8 * n_part].view(torch.float64))
+            self._work[key] = ws
+        return ws
+
+    def __call__(self, pred, gt, normalize=False, features=None):
+        """``pred, gt``: ``[P,H,W,3]`` or ``[H,W,3]`` float32 device tensors, ``H, W >= 16`` -- what ``render_path`` and
+        ``manipulate_frame`` return.  ``normalize``: the library's flag (``2 x - 1`` first; the reference passes ``[0,1]`` frames
+        without it).  ``features``: a list that receives the five tapped feature maps ``[2P,h,w,C]`` (pred then gt) as copies -- a
+        debug output for the tests."""
+        for name, t in (("pred", pred), ("gt", gt)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f"LPIPSVGG: {name} must be a device tensor (there is no CPU path)")
+            if t.dtype != torch.float32:
+                raise ValueError(f"LPIPSVGG: {name} must be float32, got {t.dtype}")
+        single = pred.dim() == 3 and gt.dim() == 3
+        if single:
+            pred, gt = pred[None], gt[None]
+        if pred.shape != gt.shape or pred.dim() != 4 or pred.device != gt.device or pred.shape[-1] != 3:
+            raise ValueError(f"LPIPSVGG: pred and gt must share one [P,H,W,3] or [H,W,3] shape and device, got {tuple(pred.shape)} and "
+                             f"{tuple(gt.shape)}")
+        if pred.device != self.device:
+            raise ValueError(f"LPIPSVGG: frames on {pred.device}, weights on {self.device}")
+        P, H, W, _ = (int(s) for s in pred.shape)
+        if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
+            raise ValueError(f"LPIPSVGG: frames of {H} x {W} are below the {LPIPS_MIN_SIZE} x {LPIPS_MIN_SIZE} the five levels need")
+        out = torch.empty(P, dtype=torch.float64, device=self.device)
+        if P == 0:
+            return out
+        lib = _lib.load()
+        ws = self._workspace(P, H, W)
+        pred, gt = pred.contiguous(), gt.contiguous()       # (the crop of render_path is a view)
+        st = _lib.stream()
+        N = 2 * P
+        _lib.check(lib.dmnerf_lpips_prologue(_lib.ptr(pred), _lib.ptr(gt), P, H, W, 1 if normalize else 0, _lib.ptr(ws["taps"]),
+                                             ws["taps"].numel(), st), "dmnerf_lpips_prologue")
+        src, dst = ws["taps"], ws["a"]
+        other = ws["b"]
+        h, w, level = H, W, 0
+        for i, (idx, sl, cin, cout) in enumerate(LPIPS_VGG_CONVS):
+            if i > 0 and sl != LPIPS_VGG_CONVS[i - 1][1]:     # the pool in front of slices 2 .. 5
+                _lib.check(lib.dmnerf_maxpool2(_lib.ptr(src), src.numel(), _lib.ptr(dst), dst.numel(), N, h, w, cin, st), "dmnerf_maxpool2")
+                h, w = h // 2, w // 2
+                src, dst = dst, src
+            first = i == 0
+            _lib.check(lib.dmnerf_conv3x3(_lib.ptr(src), src.numel(), _lib.ptr(self.packed[i]), self.packed[i].numel(), _lib.ptr(self.bias[i]),
+                                          _lib.ptr(dst), dst.numel(), N, h, w, 32 if first else cin, cout, 1 if first else 9, 1, st),
+                       "dmnerf_conv3x3")
+            if first:
+                src, dst = dst, other
+            else:
+                src, dst = dst, src
+            if i + 1 == len(LPIPS_VGG_CONVS) or LPIPS_VGG_CONVS[i + 1][1] != sl:      # the slice's last ReLU: a tap
+                _lib.check(lib.dmnerf_lpips_tail(_lib.ptr(src), src.numel(), _lib.ptr(self.lin[level]), P, h, w, cout, 1 if level == 0 else 0,
+                                                 _lib.ptr(ws["part"]), ws["part"].numel(), _lib.ptr(out), st), "dmnerf_lpips_tail")
+                if features is not None:
+                    features.append(padded_flat_images(src[:_pf_rows(N, h, w) * cout].view(-1, cout), N, h, w)[:, 1:-1, 1:-1].clone())
+                level += 1
+        return out[0] if single else out
+
+
+def lpips(model, pred, gt):
+    """``float(lpips.LPIPS(net="vgg")(pred, gt))`` of one ``[H,W,3]`` frame (tester.py:91) as a Python float: ``model(pred, gt)``
+    plus one synchronisation."""
+    if pred.dim() != 3:
+        raise ValueError("lpips: one [H,W,3] frame")
+    return float(model(pred, gt))

@@ -3,7 +3,7 @@
 their pose loops live elsewhere in this package: one pose is ``dm_nerf_amd.distributed.manipulate_frame`` (rows sharded over
 the ranks), ``manipulator_eval`` (:208-364) is ``dm_nerf_amd.editing.manipulate_eval_path`` (frames, PSNR / SSIM / AP, the 8-bit
 and coloured images) and ``manipulator_demo`` (:367-491) is ``dm_nerf_amd.editing.manipulate_demo_path`` (several objects per
-view, rigid or deformed).  File output, LPIPS and the pose JSON stay with the caller."""
+view, rigid or deformed).  File output and the pose JSON stay with the caller (LPIPS: ``manipulate_eval_path(..., lpips=evaluator.LPIPSVGG...)``)."""
 import ctypes
 
 import torch

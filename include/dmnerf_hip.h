@@ -477,6 +477,42 @@ int64_t dmnerf_img_metrics_work_bytes(int P, int H, int W, int C);
 int dmnerf_img_metrics(const float* d_pred, const float* d_gt, int P, int H, int W, int C, void* d_work, int64_t work_bytes,
                        double* d_ssim, double* d_ssim_ch, double* d_mse, double* d_psnr, void* stream);
 
+/* ---- LPIPS (VGG16) of rendered frames: lpips.LPIPS(net="vgg")(rgb, gt) of render_test / manipulator_eval (networks/tester.py:43,91,
+ * networks/manipulator.py:216,280) -- csrc/conv3x3.hip, csrc/lpips.hip; the definition (lpips 0.1.4, net='vgg', version='0.1',
+ * spatial=False) is written down in lpips.hip's header.  All activations are NHWC f32 in the PADDED-FLAT layout: per image
+ * (H+2)(W+2) rows of C floats with a zero border, the N images of a batch stacked, W+3 zeroed guard rows before the first and after
+ * the last image: N (H+2)(W+2) + 2 (W+3) rows in all; *_floats = floats the buffer holds (checked).  Pointers 16-byte aligned.
+ *   dmnerf_conv3x3_pack: torch's [Cout][Cin][3][3] weights as d_out [Cout][ldb], column (3 dy + dx) Cin + c, ldb = 9 Cin rounded up
+ *     to 32 (only Cin = 3 rounds: columns 27 .. 31 zero); Cin = 3 or a multiple of 32.
+ *   dmnerf_conv3x3: out = relu?(conv3x3(in) + bias), stride 1, zero padding 1, exact f32 (an fmaf chain per output, taps in (dy, dx,
+ *     c) order from the bias), padded-flat in, padded-flat out (P images of H x W): the border rows and the guard rows of the output
+ *     are written as exact zeros whatever was accumulated there.  Cin, Cout multiples of 32 (32 .. 4096).  taps = 9: the 3x3
+ *     convolution; taps = 1 (Cin = 32): d_in is [P (H+2)(W+2)][32] rows WITHOUT guard rows, each holding a whole K range
+ *     (dmnerf_lpips_prologue's), and the product is per row -- the first VGG layer.  ReLU keeps a NaN.
+ *   dmnerf_maxpool2: 2x2 / stride 2 maximum (floor: an odd last row / column is dropped) of N images H x W x C, padded-flat to
+ *     padded-flat (H/2 x W/2), borders and guards written zero; a NaN wins.  C a multiple of 4.
+ *   dmnerf_lpips_prologue: frames d_pred, d_gt [P,H,W,3] f32 -> d_taps [2P (H+2)(W+2)][32]: per pixel the 27 taps (3 dy + dx) 3 + c
+ *     of the scaled image (x - shift) / scale (normalize != 0: of 2 x - 1), zero outside the image, columns 27 .. 31 and border
+ *     rows zero; images 0 .. P-1 = pred, P .. 2P-1 = gt.
+ *   dmnerf_lpips_tail: one tapped layer d_feat (padded-flat, 2P images of H x W x C, pred then gt) and its lin weights d_lin [C]:
+ *     per pixel sum_c w_c (f0_c / (n0 + 1e-10) - f1_c / (n1 + 1e-10))^2 in f32, n = sqrt(sum_c f_c^2); the mean over the pixels in
+ *     f64 through per-workgroup partials (d_partials: P ceil(H W / 256) doubles) added in index order by a second launch;
+ *     d_out [P] (f64) = that mean (first != 0) or d_out + that mean.  No floating-point atomics: bit-identical from run to run,
+ *     independent of P; a NaN stays in its frame.
+ *   dmnerf_lpips_work_bytes: bytes of the whole metric's workspace for P frame pairs of H x W: [tap rows | activations A |
+ *     activations B | partials], each rounded up to 256 bytes (tap rows 2P (H+2)(W+2) x 32 floats; an activation buffer (2P (H+2)(W+2)
+ *     + 2 (W+3)) x 64 floats; partials P ceil(H W / 256) doubles); -1 for unsupported sizes (H, W in 16 .. 4096).
+ * None allocates or synchronises; all are capturable; P (N) == 0 is a successful no-op; bad sizes return DMNERF_E_ARG.           */
+int dmnerf_conv3x3_pack(const float* d_w, int Cout, int Cin, float* d_out, int ldb, void* stream);
+int dmnerf_conv3x3(const float* d_in, int64_t in_floats, const float* d_wp, int64_t w_floats, const float* d_bias, float* d_out,
+                   int64_t out_floats, int P, int H, int W, int Cin, int Cout, int taps, int relu, void* stream);
+int dmnerf_maxpool2(const float* d_in, int64_t in_floats, float* d_out, int64_t out_floats, int N, int H, int W, int C, void* stream);
+int dmnerf_lpips_prologue(const float* d_pred, const float* d_gt, int P, int H, int W, int normalize, float* d_taps, int64_t taps_floats,
+                          void* stream);
+int dmnerf_lpips_tail(const float* d_feat, int64_t feat_floats, const float* d_lin, int P, int H, int W, int C, int first, double* d_partials,
+                      int64_t partials_count, double* d_out, void* stream);
+int64_t dmnerf_lpips_work_bytes(int P, int H, int W);
+
 /* ---- penalizer.py (the consumer of raw / z_vals / depth) ---------------------------
  * emptiness_penalizer (networks/penalizer.py:5-55) fused: _fwd writes per-ray partial sums
  * d_partials [N,4] (double): {sum BCE*w_before, sum m_before, sum loss_middle*w_middle, sum m_middle};
