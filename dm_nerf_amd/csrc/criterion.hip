@@ -5,9 +5,10 @@
 // them to the host, lets scipy's linear_sum_assignment match labels to channels (:43-54), and sums the
 // matched entries plus the mean prediction of the unmatched channels (:19-37) -- two GPU->CPU syncs per
 // training step.  Here the whole loss stays on the stream:
-//   cr_partial_kernel   per 64-ray chunk: sums over the chunk's rays of -log(1-P), P (per channel) and of
-//                       log(1-P) - log(P), P per (label, channel) -- each element is visited once, its label
-//                       picks the LDS row; one thread per channel adds in ray order (deterministic)
+//   cr_partial_kernel   per 64-ray chunk: sums over the chunk's rays of P (per channel) and of -log(P), -log(1-P), P per
+//                       (label, channel) -- the element's label picks the LDS row; one thread per channel adds in ray
+//                       order (deterministic).  Two sweeps over the chunk (logs, then P) so that two [L][C] arrays of LDS do
+//                       for three sums; rays whose label forms no row feed a per-channel remainder of -log(1-P)
 //   cr_reduce_kernel    the chunk partials of every entry summed in f64 (16 lanes per entry, fixed order), many workgroups:
 //                       with one workgroup this latency-bound sum was 0.8 of the 1.0 ms the loss took at ins_num 93
 //   cr_solve_kernel     sums -> cost matrices (rows = the labels that occur, ascending: the one-hot
@@ -18,6 +19,13 @@
 //                       unmatched channels: 1 / (N U))
 // Sums are accumulated in f32 per 64-ray chunk and in f64 across chunks; the cost entries are rounded to f32
 // and added in f32 like the reference's `cost_ce + cost_siou` before the solver sees them as doubles.
+// A cross-entropy entry (label l, channel p) is [sum over the rays of OTHER labels of -log(1-P)] + [sum over l's rays of -log(P)],
+// formed in f64 from per-(label, channel) f32 partials: on a converged channel both brackets hold small terms only.  (Summing
+// -log(1-P) over ALL rays in f32 and taking the label's own rays back out loses the entry to cancellation: 3e-4 relative at
+// P = 0.999, all of it at P = 1 - 2^-24.)
+// Cost of keeping the two logarithm sums apart (a third [chunks][L][C] partial array, the second sweep, 1.5 x the entries of
+// cr_reduce_kernel, an L-long loop per channel in cr_solve_kernel), forward, HIP events, median of 50 warm calls on MI355X:
+// N = 4096: ins_num 13 88 -> 103 us, 59 375 -> 405 us, 93 460 -> 501 us; N = 1024, ins_num 128 381 -> 435 us.  Backward 11 us, unchanged.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -34,9 +42,9 @@ constexpr int CR_MAXC = LSA_MAXC;  // channels (= ins_num) supported by the solv
 
 // Work buffer layout (byte offsets; everything 8-byte aligned).  L = C + 1 label values 0..C.
 struct CrLayout {
-    int64_t part_b, part_t, part_a, part_s, part_cnt;     // chunk partials
+    int64_t part_x, part_y, part_t, part_r, part_s, part_cnt;   // chunk partials: [L][C] -log P, -log(1-P), P; [C] remainder, P; [L] counts
     int64_t part_flag;                                    // int [nch]: DMNERF_CRIT_* conditions seen by the chunk (plain stores: nothing to zero)
-    int64_t red;                                          // double [L + 2 C + 2 L C]: counts | A | S | b | t summed over the chunks
+    int64_t red;                                          // double [L + 2 C + 3 L C]: counts | R | S | x | y | t summed over the chunks
     int64_t ce, siou, tp_all;                             // float [C][C]: rows g < V (tp_all: the soft true-positive sums)
     int64_t row4col, lab_of_row, tp_of_col, den_of_col;   // int [C], int [C], float [C], float [C]
     int64_t scal;                                         // int V, int U, int flags (DMNERF_CRIT_*), pad
@@ -50,13 +58,14 @@ __host__ __device__ inline CrLayout cr_layout(int64_t N, int C) {
     w.L = C + 1;
     int64_t o = 0;
     auto take = [&](int64_t bytes) { const int64_t at = o; o += (bytes + 7) & ~(int64_t)7; return at; };
-    w.part_b = take((int64_t)w.nch * w.L * C * 4);
+    w.part_x = take((int64_t)w.nch * w.L * C * 4);
+    w.part_y = take((int64_t)w.nch * w.L * C * 4);
     w.part_t = take((int64_t)w.nch * w.L * C * 4);
-    w.part_a = take((int64_t)w.nch * C * 4);
+    w.part_r = take((int64_t)w.nch * C * 4);
     w.part_s = take((int64_t)w.nch * C * 4);
     w.part_cnt = take((int64_t)w.nch * w.L * 4);
     w.part_flag = take((int64_t)w.nch * 4);
-    w.red = take((int64_t)(w.L + 2 * C + 2 * w.L * C) * 8);
+    w.red = take((int64_t)(w.L + 2 * C + 3 * w.L * C) * 8);
     w.ce = take((int64_t)C * C * 4);
     w.siou = take((int64_t)C * C * 4);
     w.tp_all = take((int64_t)C * C * 4);
@@ -81,18 +90,19 @@ struct CrPair {
 
 // ---- per-chunk partial sums ---------------------------------------------------------------------------
 __global__ __launch_bounds__(CR_MAXC) void cr_partial_kernel(const CrPair pr, const int* __restrict__ labels, int64_t N, int C) {
-    extern __shared__ float lds[];                       // [L][C] b-sums, [L][C] P-sums, [L] counts
+    extern __shared__ float lds[];                       // [L][C] -log P sums (second sweep: P sums), [L][C] -log(1-P) sums, [L] counts
     const float* __restrict__ pred = pr.pred[blockIdx.y];
     char* __restrict__ work = pr.work[blockIdx.y];
     const CrLayout w = cr_layout(N, C);
     const int L = w.L, p = threadIdx.x;
-    float* lb = lds;
-    float* lt = lds + L * C;
+    float* lx = lds;
+    float* ly = lds + L * C;
     int* lc = reinterpret_cast<int*>(lds + 2 * L * C);
     for (int i = p; i < 2 * L * C + L; i += blockDim.x) lds[i] = 0.f;       // (int 0 == float 0 bit pattern)
     __syncthreads();
     const int64_t n0 = (int64_t)blockIdx.x * CR_CHUNK;
-    float acc_a = 0.f, acc_s = 0.f;
+    double acc_r = 0.0, acc_s = 0.0;     // per-channel sums over the whole chunk: small terms onto a large partial sum (a converged
+                                         // channel adds 0.001s to its label's 0.999s), so in f64 -- registers, no LDS
     int bad = 0;
     for (int r = 0; r < CR_CHUNK; ++r) {
         const int64_t n = n0 + r;
@@ -103,11 +113,12 @@ __global__ __launch_bounds__(CR_MAXC) void cr_partial_kernel(const CrPair pr, co
             const float P = pred[n * C + p];
             const float x = logf(P + 1e-8f);                 // log(pred + 1e-8)             (:57)
             const float y = logf((1.f - P) + 1e-8f);         // log(1 - pred + 1e-8)
-            acc_a -= y;
-            acc_s += P;
+            acc_s += (double)P;
             if (lab_ok) {                                    // this thread owns column p of every LDS row: no race
-                lb[l * C + p] += (float)((double)y - (double)x);
-                lt[l * C + p] += P;
+                lx[l * C + p] -= x;
+                ly[l * C + p] -= y;
+            } else {
+                acc_r -= (double)y;                          // an "other" ray of every row
             }
         }
         if (p == 0 && lab_ok) lc[l] += 1;
@@ -116,26 +127,41 @@ __global__ __launch_bounds__(CR_MAXC) void cr_partial_kernel(const CrPair pr, co
         if (!lab_ok) bad = DMNERF_CRIT_LABEL_RANGE;
     }
     __syncthreads();
-    float* pb = reinterpret_cast<float*>(work + w.part_b) + (int64_t)blockIdx.x * L * C;
+    float* px = reinterpret_cast<float*>(work + w.part_x) + (int64_t)blockIdx.x * L * C;
+    float* py = reinterpret_cast<float*>(work + w.part_y) + (int64_t)blockIdx.x * L * C;
     float* pt = reinterpret_cast<float*>(work + w.part_t) + (int64_t)blockIdx.x * L * C;
-    for (int i = p; i < L * C; i += blockDim.x) { pb[i] = lb[i]; pt[i] = lt[i]; }
+    for (int i = p; i < L * C; i += blockDim.x) { px[i] = lx[i]; py[i] = ly[i]; }
     if (p < C) {
-        reinterpret_cast<float*>(work + w.part_a)[(int64_t)blockIdx.x * C + p] = acc_a;
-        reinterpret_cast<float*>(work + w.part_s)[(int64_t)blockIdx.x * C + p] = acc_s;
+        reinterpret_cast<float*>(work + w.part_r)[(int64_t)blockIdx.x * C + p] = (float)acc_r;
+        reinterpret_cast<float*>(work + w.part_s)[(int64_t)blockIdx.x * C + p] = (float)acc_s;
     }
     int* pc = reinterpret_cast<int*>(work + w.part_cnt) + (int64_t)blockIdx.x * L;
     for (int i = p; i < L; i += blockDim.x) pc[i] = lc[i];
     if (p == 0) reinterpret_cast<int*>(work + w.part_flag)[blockIdx.x] = bad;
+    // second sweep: the P sums per (label, channel) in the first array (the chunk's predictions come from cache)
+    __syncthreads();
+    float* lt = lx;
+    for (int i = p; i < L * C; i += blockDim.x) lt[i] = 0.f;
+    __syncthreads();
+    if (p < C)
+        for (int r = 0; r < CR_CHUNK; ++r) {
+            const int64_t n = n0 + r;
+            if (n >= N) break;
+            const int l = labels[n];
+            if (l >= 0 && l < L) lt[l * C + p] += pred[n * C + p];
+        }
+    __syncthreads();
+    for (int i = p; i < L * C; i += blockDim.x) pt[i] = lt[i];
 }
 
-// ---- sums over the chunks: entry e of [counts (L) | A (C) | S (C) | b (L C) | t (L C)], 16 neighbouring lanes per entry (every 16th
+// ---- sums over the chunks: entry e of [counts (L) | R (C) | S (C) | x (L C) | y (L C) | t (L C)], 16 neighbouring lanes per entry (every 16th
 // chunk partial each, loads in flight together), combined in a fixed butterfly order; exact for the counts
 __global__ __launch_bounds__(256) void cr_reduce_kernel(int64_t N, int C, const CrPair pr) {
     char* __restrict__ work = pr.work[blockIdx.y];
     const CrLayout w = cr_layout(N, C);
     const int L = w.L, sub = threadIdx.x & 15;
     const int e = blockIdx.x * 16 + (threadIdx.x >> 4);
-    const int n_ent = L + 2 * C + 2 * L * C;
+    const int n_ent = L + 2 * C + 3 * L * C;
     double v = 0.0;
     if (e < L) {
         const int* __restrict__ pc = reinterpret_cast<const int*>(work + w.part_cnt);
@@ -146,10 +172,11 @@ __global__ __launch_bounds__(256) void cr_reduce_kernel(int64_t N, int C, const 
         const float* __restrict__ src;
         int64_t stride;
         int off;
-        if (e < L + C) { src = reinterpret_cast<const float*>(work + w.part_a); stride = C; off = e - L; }
+        if (e < L + C) { src = reinterpret_cast<const float*>(work + w.part_r); stride = C; off = e - L; }
         else if (e < L + 2 * C) { src = reinterpret_cast<const float*>(work + w.part_s); stride = C; off = e - L - C; }
-        else if (e < L + 2 * C + L * C) { src = reinterpret_cast<const float*>(work + w.part_b); stride = (int64_t)L * C; off = e - L - 2 * C; }
-        else { src = reinterpret_cast<const float*>(work + w.part_t); stride = (int64_t)L * C; off = e - L - 2 * C - L * C; }
+        else if (e < L + 2 * C + L * C) { src = reinterpret_cast<const float*>(work + w.part_x); stride = (int64_t)L * C; off = e - L - 2 * C; }
+        else if (e < L + 2 * C + 2 * L * C) { src = reinterpret_cast<const float*>(work + w.part_y); stride = (int64_t)L * C; off = e - L - 2 * C - L * C; }
+        else { src = reinterpret_cast<const float*>(work + w.part_t); stride = (int64_t)L * C; off = e - L - 2 * C - 2 * L * C; }
         for (int k = sub; k < w.nch; k += 16) v += (double)src[(int64_t)k * stride + off];
     }
     v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
@@ -177,16 +204,21 @@ __global__ __launch_bounds__(256) void cr_solve_kernel(int64_t N, int C, const C
     float* ce = reinterpret_cast<float*>(work + w.ce);
     float* siou = reinterpret_cast<float*>(work + w.siou);
     float* tp_all = reinterpret_cast<float*>(work + w.tp_all);
-    const double* red = reinterpret_cast<const double*>(work + w.red);      // cr_reduce_kernel: counts | A | S | b | t
-    const double* red_b = red + L + 2 * C;
-    const double* red_t = red_b + L * C;
+    const double* red = reinterpret_cast<const double*>(work + w.red);      // cr_reduce_kernel: counts | R | S | x | y | t
+    const double* red_x = red + L + 2 * C;
+    const double* red_y = red_x + L * C;
+    const double* red_t = red_y + L * C;
 
     // 1. label counts, the labels that occur (ascending) -> rows (evaluator.py:21-26)
     for (int e = tid; e < L + 2 * C; e += blockDim.x) {
         const double v = red[e];
         if (e < L) s_cnt[e] = (int)v;
-        else if (e < L + C) s_A[e - L] = v;
-        else s_S[e - L - C] = v;
+        else if (e < L + C) {                               // A_p: -log(1-P) over ALL rays = the remainder + every label's sum
+            const int p = e - L;
+            double a = v;
+            for (int l = 0; l < L; ++l) a += red_y[l * C + p];
+            s_A[p] = a;
+        } else s_S[e - L - C] = v;
     }
     __syncthreads();
     if (tid == 0) {
@@ -210,7 +242,7 @@ __global__ __launch_bounds__(256) void cr_solve_kernel(int64_t N, int C, const C
         const int l = e / C, p = e - l * C;
         const int g = s_rank[l];
         if (g >= 0) {
-            ce[g * C + p] = (float)((s_A[p] + red_b[e]) / (double)N);
+            ce[g * C + p] = (float)(((s_A[p] - red_y[e]) + red_x[e]) / (double)N);   // other labels' rays + the label's own
             const float TP = (float)red_t[e];
             tp_all[g * C + p] = TP;
             const float FP = (float)s_S[p] - TP;
@@ -324,7 +356,7 @@ static int cr_forward(const CrPair& pr, int levels, const int32_t* d_labels, int
     hipLaunchKernelGGL(cr_partial_kernel, dim3((unsigned)w.nch, (unsigned)levels), dim3(CR_MAXC), lds, (hipStream_t)stream, pr, (const int*)d_labels, N, ins_num);
     int rc = dmn_check_launch("ins_criterion: partial sums");
     if (rc) return rc;
-    const int n_ent = w.L + 2 * ins_num + 2 * w.L * ins_num;
+    const int n_ent = w.L + 2 * ins_num + 3 * w.L * ins_num;
     hipLaunchKernelGGL(cr_reduce_kernel, dim3((unsigned)((n_ent + 15) / 16), (unsigned)levels), dim3(256), 0, (hipStream_t)stream, N, ins_num, pr);
     rc = dmn_check_launch("ins_criterion: chunk sums");
     if (rc) return rc;
