@@ -43,6 +43,17 @@ class RenderFineArgs(ctypes.Structure):
     ]
 
 
+class SkipGridArgs(ctypes.Structure):
+    """``dmnerf_skip_grid`` (include/dmnerf_hip.h)."""
+    _fields_ = [("lo", c_float * 3), ("inv_cell", c_float * 3), ("dims", c_int * 3), ("outside", c_int), ("d_bits", c_vp)]
+
+
+class RenderFineSkipArgs(ctypes.Structure):
+    """``dmnerf_render_fine_skip_args`` (include/dmnerf_hip.h)."""
+    _fields_ = [("fine", RenderFineArgs), ("grid", SkipGridArgs), ("d_sel", c_vp), ("d_n_eval", c_vp), ("d_flag", c_vp),
+                ("d_select_ws", c_vp), ("levels", c_int)]
+
+
 class RepackModel(ctypes.Structure):
     """``dmnerf_repack_model`` (include/dmnerf_hip.h)."""
     _fields_ = [("d_params_flat", c_vp), ("ins_num", c_int), ("d_flat_copy", c_vp), ("d_idx", c_vp), ("d_blob", c_vp),
@@ -181,6 +192,12 @@ SIGNATURES = {
     "dmnerf_surface_clusters": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_surface_clean_mark": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_surface_clean_compact": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_skip_grid_build": (c_int, [c_vp, c_int, c_int, c_int, c_float, c_int, c_vp, c_vp]),
+    "dmnerf_skip_select_work_ints": (c_i64, [c_i64]),
+    "dmnerf_skip_select": (c_int, [ctypes.POINTER(SkipGridArgs), c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_mlp_fwd_rays_sel": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_mlp_fwd_rays_density_sel": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_render_rays_fwd_fine_skip": (c_int, [ctypes.POINTER(RenderFineSkipArgs), c_vp]),
 }
 
 _lib = None

@@ -114,3 +114,68 @@ extern "C" int dmnerf_render_rays_fwd_fine(const dmnerf_render_fine_args* a, voi
                                    a->d_depth_fine, a->d_ins_fine, stream))) return rc;
     return DMNERF_OK;
 }
+
+int dmn_skip_set_int(int* d_p, int v, hipStream_t stream);      // skip.hip
+
+// dmnerf_render_rays_fwd_fine through an occupancy bit grid (csrc/skip.hip): the networks run on the marked samples only, the other
+// rows of sigma / raw_fine are zero.  A zero row is exactly neutral downstream -- alpha = 1 - exp(-0) = 0, weight 0, every term
+// 0 * x -- so the result is the dense render with those rows masked.  The sample counts never leave the device.
+extern "C" int dmnerf_render_rays_fwd_fine_skip(const dmnerf_render_fine_skip_args* k, void* stream) {
+    if (!k) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: null args");
+    const dmnerf_render_fine_args* a = &k->fine;
+    if (a->fused_heads != 0 && a->fused_heads != 1)
+        return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: fused_heads %d unsupported (no split-operand kernels over a selection)", a->fused_heads);
+    if (k->levels & ~(DMNERF_SKIP_LEVEL_COARSE | DMNERF_SKIP_LEVEL_FINE)) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: bad levels mask %d", k->levels);
+    const int64_t N = a->N;
+    const int S = a->S, SF = a->S + a->n_imp, C = a->ins_num + 1;
+    if (N < 0 || S < 3 || a->n_imp < 1) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: bad N=%lld S=%d n_imp=%d", (long long)N, S, a->n_imp);
+    if (N * SF >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: %lld samples do not fit the int32 selection", (long long)(N * SF));
+    if (!k->d_n_eval) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: null pointer in args");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (N == 0) {                                                        // an empty chunk: its buffers may be null
+        if ((rc = dmn_skip_set_int(k->d_n_eval, 0, st))) return rc;
+        return dmn_skip_set_int(k->d_n_eval + 1, 0, st);
+    }
+    if (!a->d_blob_coarse || !a->d_blob_fine || !a->d_rays_o || !a->d_rays_d || !a->d_z_in || !a->d_u || !a->d_z_coarse ||
+        !a->d_sigma_ws || !a->d_weights_ws || !a->d_z_fine || !a->d_raw_fine || !a->d_rgb_fine || !a->d_depth_fine || !a->d_ins_fine ||
+        !k->d_sel || !k->d_flag || !k->d_select_ws || !k->grid.d_bits)
+        return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: null pointer in args");
+    // stratified jitter (render.py:40-47) or pass-through copy of the coarse grid
+    if (a->d_t_rand) {
+        if ((rc = dmnerf_stratify(a->d_z_in, a->d_t_rand, N, S, a->d_z_coarse, stream))) return rc;
+    } else if (a->d_z_coarse != a->d_z_in) {
+        if (hipError_t e = hipMemcpyAsync(a->d_z_coarse, a->d_z_in, sizeof(float) * N * S, hipMemcpyDeviceToDevice, st); e != hipSuccess)
+            return dmn_fail_hip(e, "render_rays_fwd_fine_skip: z copy");
+    }
+    // coarse level: the density at the marked samples, 0 elsewhere (render.py:49-61), its weights (:6-20), resampling + merge (:66-70)
+    if (k->levels & DMNERF_SKIP_LEVEL_COARSE) {
+        if ((rc = dmnerf_skip_select(&k->grid, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, k->d_flag, k->d_sel, k->d_n_eval, k->d_select_ws, stream))) return rc;
+        if (hipError_t e = hipMemsetAsync(a->d_sigma_ws, 0, sizeof(float) * N * S, st); e != hipSuccess) return dmn_fail_hip(e, "render_rays_fwd_fine_skip: sigma fill");
+        if ((rc = dmnerf_mlp_fwd_rays_density_sel(a->d_blob_coarse, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, k->d_sel, k->d_n_eval,
+                                                  a->d_sigma_ws, stream))) return rc;
+    } else {
+        if ((rc = dmn_skip_set_int(k->d_n_eval, (int)(N * S), st))) return rc;
+        if ((rc = dmnerf_mlp_fwd_rays_density(a->d_blob_coarse, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, a->d_sigma_ws, stream))) return rc;
+    }
+    if ((rc = dmnerf_weights_from_sigma(a->d_sigma_ws, a->d_z_coarse, a->d_rays_d, N, S, a->d_weights_ws, stream))) return rc;
+    if ((rc = dmnerf_importance_resample(a->d_z_coarse, a->d_weights_ws, a->d_u, a->u_row_stride, N, S, a->n_imp, a->d_z_fine, nullptr, stream))) return rc;
+    // fine level (render.py:71-86)
+    if (k->levels & DMNERF_SKIP_LEVEL_FINE) {
+        if ((rc = dmnerf_skip_select(&k->grid, a->d_rays_o, a->d_rays_d, a->d_z_fine, N, SF, k->d_flag, k->d_sel, k->d_n_eval + 1, k->d_select_ws, stream))) return rc;
+        if (hipError_t e = hipMemsetAsync(a->d_raw_fine, 0, sizeof(float) * N * SF * (4 + C), st); e != hipSuccess) return dmn_fail_hip(e, "render_rays_fwd_fine_skip: raw fill");
+        if (a->ev_fine_mlp_begin) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_begin, st);
+        if ((rc = dmnerf_mlp_fwd_rays_sel(a->d_blob_fine, a->ins_num, a->fused_heads, a->d_rays_o, a->d_rays_d, a->d_z_fine, N, SF, k->d_sel, k->d_n_eval + 1,
+                                          a->d_raw_fine, stream))) return rc;
+        if (a->ev_fine_mlp_end) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_end, st);
+    } else {
+        if ((rc = dmn_skip_set_int(k->d_n_eval + 1, (int)(N * SF), st))) return rc;
+        auto mlp = a->fused_heads ? dmnerf_mlp_fwd_rays_fused : dmnerf_mlp_fwd_rays;
+        if (a->ev_fine_mlp_begin) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_begin, st);
+        if ((rc = mlp(a->d_blob_fine, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_fine, N, SF, a->d_raw_fine, stream))) return rc;
+        if (a->ev_fine_mlp_end) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_end, st);
+    }
+    if ((rc = dmnerf_composite_fwd(a->d_raw_fine, a->d_z_fine, a->d_rays_d, N, SF, C, a->d_rgb_fine, a->d_weights_ws,
+                                   a->d_depth_fine, a->d_ins_fine, stream))) return rc;
+    return DMNERF_OK;
+}

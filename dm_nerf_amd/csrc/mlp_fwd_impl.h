@@ -52,8 +52,12 @@ struct MlpArgs {
 #define DMN_STAMP(k) do {} while (0)
 #endif
 
-template <int OBI, bool EMBEDDED, bool SAVE, bool FUSED = false>
-__global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
+// The kernel body, shared by mlp_fwd_kernel (below) and the kernels over a selection (mlp_fwd_sparse.hip).  SEL: the batch is the
+// sample list a.sel[0 .. *a.count) -- a lane's sample is sel[blk * 32 + lane % 32], its ray sel[..] / S, its output row sel[..];
+// the batch size is read on the device and a workgroup beyond it leaves as a whole, before the DMA ring and the first barrier.
+// Without SEL every `if constexpr (SEL)` drops out and M is a.M: the dense kernels' code is what it was.
+template <int OBI, bool EMBEDDED, bool SAVE, bool FUSED, bool SEL, class Args>
+__device__ __forceinline__ void mlp_fwd_body(const Args& a) {
     // (FUSED && SAVE = the opt-in training forward on the fused-heads blob: the backward is in re-associated form anyway,
     // csrc/heads.hip, and needs exactly what this variant saves: pe, de, h_0..h_7, g1, g2 and the masks)
     extern __shared__ __attribute__((aligned(16))) float lds[];          // [ring 2 x 64 KiB][table 16 KiB][park 16 KiB]
@@ -65,7 +69,14 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
     // Every wave of the workgroup takes part in the DMA + barrier protocol; a wave beyond the end of
     // the batch (only in the last workgroup) is an exact duplicate of the last block's wave: it computes and
     // stores the same values to the same addresses.
-    const int64_t nblk = (a.M + 31) / 32;
+    int64_t M = a.M;
+    if constexpr (SEL) M = *a.count;                                      // wave-uniform: one scalar load
+    const int64_t nblk = (M + 31) / 32;
+    if constexpr (SEL) {
+        // blockIdx and the count are the same for all four waves, so the workgroup leaves as one: nobody is left waiting in the
+        // ring protocol.  count == 0: nblk == 0 and every workgroup leaves here.
+        if ((int64_t)blockIdx.x * 4 >= nblk) return;
+    }
     const int64_t blk_raw = (int64_t)blockIdx.x * 4 + wave;
     const bool wave_active = blk_raw < nblk;
     const int64_t blk = wave_active ? blk_raw : nblk - 1;
@@ -75,8 +86,11 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
     // computed where it is used instead of being hoisted to the top of the kernel and carried (spilled) across the network
     auto fresh = [](int x) -> int { asm volatile("" : "+v"(x)); return x; };
     auto sample_of_lane = [&]() -> int64_t { return blk * 32 + (fresh(lane) & 31); };
+    // output row of batch position j < M: j itself, or with SEL the selected sample (re-read where the row is written)
+    auto row_of = [&](int64_t j) -> int64_t { if constexpr (SEL) return a.sel[j]; else return j; };
     const int64_t m_in = blk * 32 + (lane & 31);
-    const int64_t m = m_in < a.M ? m_in : a.M - 1;                           // tail lanes recompute the last sample
+    int64_t m = m_in < M ? m_in : M - 1;                                     // tail lanes recompute the last sample
+    if constexpr (SEL) m = a.sel[m];                                         // (sel is never read at or beyond count)
     // The direction encoding (16 registers) is needed once, ~4400 MFMAs from here, by the rgb hidden layer: it is parked in
     // this wave's 4 KiB of the last 16 KiB of the CU's LDS instead of occupying VGPRs through the whole trunk (with it
     // resident the training variants spilled ~30 registers to scratch around the heads).
@@ -128,8 +142,8 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
         for (int k = 0; k < TAB_FLOATS / 1024; ++k) dst[k * 256] = tabv[k];
     }
 
-    const SaveLayout SL = make_save_layout(a.M);
-    const int64_t MP = save_row_len(a.M);          // padded row length of the training workspace
+    const SaveLayout SL = make_save_layout(M);
+    const int64_t MP = save_row_len(M);          // padded row length of the training workspace
     const int srows = 1;                           // (every wave stores: see mlp_common.h::RowIO)
     // ReLU bit masks for the backward pass (one 16-byte store per lane and layer instead of 128 row loads there)
     rsrc_t bits_rs;
@@ -296,8 +310,8 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
         gemm_quarter<0, 16, OBI, 0, false, NS3>(ws, hid, io, lane, st_3);   // ins_linear (:103); its fetch runs into the zero-filled landing zone
         const int64_t ms = sample_of_lane();
         const int hf = fresh(half);
-        float* __restrict__ out_row = a.raw + (ms < a.M ? ms : a.M - 1) * (4 + L.C);
-        if (ms < a.M) {
+        float* __restrict__ out_row = a.raw + row_of(ms < M ? ms : M - 1) * (4 + L.C);
+        if (ms < M) {
 #pragma unroll
             for (int b = 0; b < OBI; ++b) {
 #pragma unroll
@@ -311,14 +325,19 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
     DMN_STAMP(4);
     // cat[rgb, density, ins]  (dm_nerf.py:105)
     const int64_t ms = sample_of_lane();
-    float* __restrict__ out_row = a.raw + (ms < a.M ? ms : a.M - 1) * (4 + L.C);
-    if (ms < a.M && fresh(half) == 0) {
+    float* __restrict__ out_row = a.raw + row_of(ms < M ? ms : M - 1) * (4 + L.C);
+    if (ms < M && fresh(half) == 0) {
         out_row[0] = rgb_out[0];
         out_row[1] = rgb_out[1];
         out_row[2] = rgb_out[2];
         out_row[3] = sigma;
     }
     DMN_STAMP(5);
+}
+
+template <int OBI, bool EMBEDDED, bool SAVE, bool FUSED = false>
+__global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
+    mlp_fwd_body<OBI, EMBEDDED, SAVE, FUSED, false>(a);
 }
 
 template <bool EMBEDDED, bool SAVE, bool FUSED = false>

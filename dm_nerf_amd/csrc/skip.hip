@@ -1,0 +1,209 @@
+// skip.hip -- the occupancy bit grid that lets a render skip samples in empty space: build it, and mark + compact the samples of a
+// chunk of rays against it (the networks over the compacted list: mlp_fwd_sparse.hip; the render: api.hip).
+//
+// The grid is an axis-aligned box in world coordinates, dims = (dx, dy, dz) cells, one bit per cell in uint32 words: cell
+// g = (i * dy + j) * dz + k sits in word g >> 5 at bit g & 31; the unused high bits of the last word are 0.
+//
+//   dmnerf_skip_grid_build   bit(g) = any sigma in the (2 dilate + 1)^3 neighbourhood of g, clipped at the faces, is > threshold;
+//                            NaN counts as occupied (the test is !(sigma <= threshold)).
+//   dmnerf_skip_select       flag [N,S], the ascending list sel of the flagged samples, and its length, which stays on the device.
+//
+// No atomics anywhere: a word of the grid is written by the one lane that holds its ballot, and the compaction is three passes
+// (per-block counts, one scan of the counts, scatter by prefix sums), so the list is in ascending order and the same every run.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/dmnerf_hip.h"
+#include "common.h"
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr int MAX_DILATE = 4;
+
+// ---- build.  A block owns 256 consecutive cells [g0, g0 + 256) = 8 whole words.  The neighbour (i + di, j + dj, k + dk) of cell g,
+// where it exists, is cell g + (di * dy + dj) * dz + dk: for every (di, dj) the neighbours of the block's cells are again one
+// contiguous run of 256 + 2 dilate cells.  The LDS tile holds the occupancy predicate of these (2 dilate + 1)^2 runs (halo included);
+// whether a neighbour exists is decided per cell from its coordinates (the clipping at the faces), so a run's entries that belong
+// to a neighbouring row are never used by mistake.
+__global__ __launch_bounds__(BLOCK) void skip_grid_build_kernel(const float* __restrict__ sigma, int dx, int dy, int dz, float threshold,
+                                                                int d, uint32_t* __restrict__ bits) {
+    extern __shared__ unsigned char tile[];                    // [(2d+1)^2][256 + 2d]
+    const int D = 2 * d + 1, SEG = BLOCK + 2 * d;
+    const int64_t total = (int64_t)dx * dy * dz;
+    const int64_t g0 = (int64_t)blockIdx.x * BLOCK;
+    for (int idx = threadIdx.x; idx < D * D * SEG; idx += BLOCK) {
+        const int seg = idx / SEG, t = idx - seg * SEG;
+        const int di = seg / D - d, dj = seg % D - d;
+        const int64_t gl = g0 - d + t + ((int64_t)di * dy + dj) * dz;
+        unsigned char v = 0;
+        if (gl >= 0 && gl < total) v = !(sigma[gl] <= threshold);          // NaN: occupied
+        tile[idx] = v;
+    }
+    __syncthreads();
+    const int64_t g = g0 + threadIdx.x;
+    bool occ = false;
+    if (g < total) {
+        const int k = (int)(g % dz);
+        const int64_t r = g / dz;
+        const int j = (int)(r % dy), i = (int)(r / dy);
+        for (int di = -d; di <= d; ++di) {
+            if (i + di < 0 || i + di >= dx) continue;
+            for (int dj = -d; dj <= d; ++dj) {
+                if (j + dj < 0 || j + dj >= dy) continue;
+                const unsigned char* run = tile + ((di + d) * D + (dj + d)) * SEG + threadIdx.x + d;
+                for (int dk = -d; dk <= d; ++dk)
+                    if (k + dk >= 0 && k + dk < dz) occ |= run[dk] != 0;
+            }
+        }
+    }
+    const unsigned long long ballot = __ballot(occ);           // 64 cells = 2 words; lanes 0 and 32 each own one
+    const int lane = threadIdx.x & 63;
+    if ((lane & 31) == 0) {
+        const int64_t w = (g0 + (threadIdx.x & ~63)) / 32 + (lane >> 5);
+        if (w < (total + 31) / 32) bits[w] = (uint32_t)(ballot >> (lane & 32));
+    }
+}
+
+// ---- select, pass 1: the flag of every sample and the number of flagged samples of every block
+struct GridDev {
+    float lo[3], inv_cell[3];
+    int dims[3];
+    int outside_flag;          // the flag of a sample outside the box: 1 ("evaluate") or 0 ("empty")
+    const uint32_t* bits;
+};
+
+__device__ __forceinline__ int block_count_and_rank(bool f, int* rank_out) {
+    // -> the block's total; *rank_out = number of flagged threads before this one (thread order)
+    __shared__ int wave_n[BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(f);
+    if (lane == 0) wave_n[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; ++w) {
+        if (w < wave) before += wave_n[w];
+        total += wave_n[w];
+    }
+    *rank_out = before + __popcll(b & ((1ull << lane) - 1ull));
+    return total;
+}
+
+__global__ __launch_bounds__(BLOCK) void skip_flag_kernel(GridDev G, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                          const float* __restrict__ z, int64_t M, int S, uint8_t* __restrict__ flag,
+                                                          int* __restrict__ block_n) {
+    const int64_t m = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    bool f = false;
+    if (m < M) {
+        const int64_t n = m / S;
+        const float zv = z[m];
+        bool inside = true;
+        int64_t g = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            // p = o + d z: separate multiply and add, as the MLP prologue (render.py:49); then every operation rounded on its own
+            const float p = __fadd_rn(rays_o[n * 3 + a], __fmul_rn(rays_d[n * 3 + a], zv));
+            const float c = floorf(__fmul_rn(__fsub_rn(p, G.lo[a]), G.inv_cell[a]));
+            inside = inside && (c >= 0.f) && (c < (float)G.dims[a]);        // on the float: a NaN point is outside
+            g = g * G.dims[a] + (inside ? (int)c : 0);
+        }
+        f = inside ? ((G.bits[g >> 5] >> (g & 31)) & 1u) != 0 : G.outside_flag != 0;
+        flag[m] = f ? 1 : 0;
+    }
+    int rank;
+    const int total = block_count_and_rank(f, &rank);
+    if (threadIdx.x == 0) block_n[blockIdx.x] = total;
+}
+
+// ---- pass 2: exclusive scan of the block counts in place (one workgroup walks them, 1024 at a time) and the grand total
+__global__ __launch_bounds__(1024) void skip_scan_kernel(int* __restrict__ block_n, int64_t nb, int* __restrict__ count) {
+    __shared__ int buf[1024];
+    const int tid = threadIdx.x;
+    int carry = 0;                                             // the same in every thread
+    for (int64_t base = 0; base < nb; base += 1024) {
+        const int64_t i = base + tid;
+        const int v = i < nb ? block_n[i] : 0;
+        buf[tid] = v;
+        __syncthreads();
+        for (int off = 1; off < 1024; off <<= 1) {
+            const int t = tid >= off ? buf[tid - off] : 0;
+            __syncthreads();
+            buf[tid] += t;
+            __syncthreads();
+        }
+        if (i < nb) block_n[i] = carry + buf[tid] - v;
+        carry += buf[1023];
+        __syncthreads();
+    }
+    if (tid == 0) *count = carry;
+}
+
+// ---- pass 3: sample m goes to sel[block offset + rank within the block]
+__global__ __launch_bounds__(BLOCK) void skip_scatter_kernel(const uint8_t* __restrict__ flag, const int* __restrict__ block_off, int64_t M,
+                                                             int* __restrict__ sel) {
+    const int64_t m = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool f = m < M && flag[m] != 0;
+    int rank;
+    (void)block_count_and_rank(f, &rank);
+    if (f) sel[block_off[blockIdx.x] + rank] = (int)m;
+}
+
+__global__ void skip_set_int_kernel(int* p, int v) { *p = v; }
+
+}  // namespace
+
+// (api.hip: the sample count of a level that is rendered dense)
+int dmn_skip_set_int(int* d_p, int v, hipStream_t stream) {
+    hipLaunchKernelGGL(skip_set_int_kernel, dim3(1), dim3(1), 0, stream, d_p, v);
+    return dmn_check_launch("skip: set count");
+}
+
+extern "C" int dmnerf_skip_grid_build(const float* d_sigma, int dx, int dy, int dz, float threshold, int dilate, uint32_t* d_bits,
+                                      void* stream) {
+    if (dx < 1 || dy < 1 || dz < 1) return dmn_fail(DMNERF_E_ARG, "skip_grid_build: bad dims %d x %d x %d", dx, dy, dz);
+    if (dilate < 0 || dilate > MAX_DILATE) return dmn_fail(DMNERF_E_ARG, "skip_grid_build: dilate %d outside 0..%d", dilate, MAX_DILATE);
+    const int64_t total = (int64_t)dx * dy * dz;
+    if (total >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_grid_build: %lld cells do not fit int32", (long long)total);
+    if (!d_sigma || !d_bits) return dmn_fail(DMNERF_E_ARG, "skip_grid_build: null pointer");
+    const int D = 2 * dilate + 1;
+    const size_t lds = (size_t)D * D * (BLOCK + 2 * dilate);   // <= 81 * 264 B
+    hipLaunchKernelGGL(skip_grid_build_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), lds, (hipStream_t)stream,
+                       d_sigma, dx, dy, dz, threshold, dilate, d_bits);
+    return dmn_check_launch("skip_grid_build");
+}
+
+extern "C" int64_t dmnerf_skip_select_work_ints(int64_t M) {
+    if (M < 0 || M >= (1LL << 31)) return -1;
+    return (M + BLOCK - 1) / BLOCK + 1;
+}
+
+extern "C" int dmnerf_skip_select(const dmnerf_skip_grid* grid, const float* d_rays_o, const float* d_rays_d, const float* d_z,
+                                  int64_t N, int S, uint8_t* d_flag, int* d_sel, int* d_count, int* d_work, void* stream) {
+    if (!grid) return dmn_fail(DMNERF_E_ARG, "skip_select: null grid");
+    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "skip_select: bad N=%lld S=%d", (long long)N, S);
+    const int64_t M = N * S;
+    if (M >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_select: %lld samples do not fit the int32 selection", (long long)M);
+    if (grid->outside != DMNERF_SKIP_OUTSIDE_EVALUATE && grid->outside != DMNERF_SKIP_OUTSIDE_EMPTY)
+        return dmn_fail(DMNERF_E_ARG, "skip_select: outside policy %d unknown", grid->outside);
+    GridDev G;
+    int64_t cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (grid->dims[a] < 1) return dmn_fail(DMNERF_E_ARG, "skip_select: bad grid dims");
+        G.lo[a] = grid->lo[a]; G.inv_cell[a] = grid->inv_cell[a]; G.dims[a] = grid->dims[a];
+        cells *= grid->dims[a];
+    }
+    if (cells >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_select: %lld cells do not fit int32", (long long)cells);
+    G.outside_flag = grid->outside == DMNERF_SKIP_OUTSIDE_EVALUATE ? 1 : 0;
+    G.bits = grid->d_bits;
+    if (!d_count) return dmn_fail(DMNERF_E_ARG, "skip_select: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (M == 0) return dmn_skip_set_int(d_count, 0, st);
+    if (!grid->d_bits || !d_rays_o || !d_rays_d || !d_z || !d_flag || !d_sel || !d_work) return dmn_fail(DMNERF_E_ARG, "skip_select: null pointer");
+    const int64_t nb = (M + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(skip_flag_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, G, d_rays_o, d_rays_d, d_z, M, S, d_flag, d_work);
+    hipLaunchKernelGGL(skip_scan_kernel, dim3(1), dim3(1024), 0, st, d_work, nb, d_count);
+    hipLaunchKernelGGL(skip_scatter_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, d_flag, d_work, M, d_sel);
+    return dmn_check_launch("skip_select");
+}

@@ -361,6 +361,13 @@ def _default_render_chunk(rays_o, rays_d, z, models, args, events=None):
     return out['rgb_fine'], out['ins_fine'], out['depth_fine']
 
 
+def _skip_render_chunk(rays_o, rays_d, z, models, args, events=None, grid=None, levels=("coarse", "fine")):
+    from .networks import render
+    out = render.dm_nerf_fine_skip(torch.stack([rays_o, rays_d]), None, None, models[0], models[1], z, args, grid, levels=levels,
+                                   _events=events)
+    return out['rgb_fine'], out['ins_fine'], out['depth_fine']
+
+
 _compact_index_cache = {}
 
 
@@ -393,13 +400,20 @@ class FrameRenderer:
     ``render_frame`` is ``step`` over all chunks + ``gather``; bench.py drives the same object chunk by chunk."""
 
     def __init__(self, H, W, K, c2w, models, near, far, args, chunk=4096, n_samples=64,
-                 raygen=None, render_chunk=None, z_fn=None, labels_only=False, label_conf=None, ins_num=None, dtype=None):
+                 raygen=None, render_chunk=None, z_fn=None, labels_only=False, label_conf=None, ins_num=None, dtype=None,
+                 skip=None, skip_levels=("coarse", "fine")):
         self.rank, self.world = world_info()
         self.dtype = dtype                                         # band dtype (default f32, what every kernel writes)
         self.H, self.W, self.models, self.args, self.chunk = int(H), int(W), models, args, int(chunk)
         self.labels_only = bool(labels_only)
-        self.render_chunk = render_chunk or _default_render_chunk
         self._pass_events = render_chunk is None
+        if skip is not None:
+            # skip = a field.SkipGrid: the chunks go through render.dm_nerf_fine_skip (samples in empty cells are not evaluated)
+            if render_chunk is not None:
+                raise ValueError("FrameRenderer: skip= routes the chunks through dm_nerf_fine_skip; it cannot be combined with render_chunk=")
+            import functools
+            render_chunk = functools.partial(_skip_render_chunk, grid=skip, levels=skip_levels)
+        self.render_chunk = render_chunk or _default_render_chunk
         if z_fn is None:
             from .networks import helpers
             z_fn = lambda n, dev: helpers.z_val_sample(n, near, far, n_samples, device=dev)
@@ -473,7 +487,8 @@ class FrameRenderer:
 
 
 def render_frame(H, W, K, c2w, models, near, far, args, chunk=4096, n_samples=64,
-                 raygen=None, render_chunk=None, z_fn=None, labels_only=False, label_conf=None, ins_num=None):
+                 raygen=None, render_chunk=None, z_fn=None, labels_only=False, label_conf=None, ins_num=None,
+                 skip=None, skip_levels=("coarse", "fine")):
     """Full-frame render, rows sharded over ranks, ONE all-gather per frame (``FrameRenderer``).
 
     Mirrors the per-pose body of ``render_test`` (networks/tester.py:58-85): same chunking
@@ -482,9 +497,12 @@ def render_frame(H, W, K, c2w, models, near, far, args, chunk=4096, n_samples=64
     ``depth [H,W]`` on every rank (views of the one gathered buffer).  ``labels_only=True``: the object map is reduced on the
     device to what ``ins_eval`` consumes (evaluator.py:127-137) -- ``label [H,W]`` int64 = argmax, ``conf [H,W]`` = max --
     before the gather, and ``(rgb, label, conf, depth)`` is returned: 24 instead of 16 + 4*ins_num bytes per pixel cross the links.
+    ``skip=`` a ``field.SkipGrid``: every chunk is rendered by ``render.dm_nerf_fine_skip`` at ``skip_levels`` (opt-in; samples in
+    empty cells are not evaluated).  ``render_path(..., skip=grid)`` hands it through.
     """
     fr = FrameRenderer(H, W, K, c2w, models, near, far, args, chunk=chunk, n_samples=n_samples, raygen=raygen,
-                       render_chunk=render_chunk, z_fn=z_fn, labels_only=labels_only, label_conf=label_conf, ins_num=ins_num)
+                       render_chunk=render_chunk, z_fn=z_fn, labels_only=labels_only, label_conf=label_conf, ins_num=ins_num,
+                       skip=skip, skip_levels=skip_levels)
     for i in range(fr.n_chunks):
         fr.step(i)
     return fr.gather()

@@ -399,3 +399,135 @@ def write_ply(path, vertices, faces, normals=None, colors=None):
         fh.write(("\n".join(header) + "\n").encode("ascii"))
         fh.write(rows.tobytes())
         fh.write(tris.tobytes())
+
+
+# ---- the occupancy bit grid of a render that skips empty space (csrc/skip.hip; tests/_skip_restate.py states it in numpy)
+SKIP_OUTSIDE = {"evaluate": 0, "empty": 1}          # DMNERF_SKIP_OUTSIDE_* (include/dmnerf_hip.h)
+
+
+def _dims3(dims):
+    dims = (int(dims),) * 3 if np.ndim(dims) == 0 else tuple(int(d) for d in dims)
+    if len(dims) != 3 or min(dims) < 1:
+        raise ValueError(f"dims must be one or three positive integers, got {dims}")
+    if dims[0] * dims[1] * dims[2] >= 2 ** 31:
+        raise ValueError(f"{dims[0] * dims[1] * dims[2]} cells do not fit int32")
+    return dims
+
+
+class SkipGrid:
+    """An axis-aligned box ``[lo, hi)`` in world coordinates, ``dims = (dx, dy, dz)`` cells, one bit per cell: set = the cell may hold
+    density, clear = a sample in it is not worth a network evaluation (``render.dm_nerf_fine_skip``).
+
+    ``cell = float32(hi - lo) / float32(dims)`` and ``inv_cell = float32(1) / cell``, each rounded to f32 on its own; a point ``p`` is
+    in cell ``c_a = floor((p_a - lo_a) * inv_cell_a)`` (f32 ops, one rounding each) and inside the box iff ``0 <= c_a < dims_a`` on all
+    three axes.  ``bits``: uint32 words on the device, held as an int32 tensor ``[ceil(dx dy dz / 32)]`` (the same bits); cell
+    ``g = (i * dy + j) * dz + k`` is bit ``g & 31`` of word ``g >> 5``; the unused bits of the last word are 0.  ``outside``: what a
+    sample outside the box gets -- ``"evaluate"`` (default, conservative: the network runs there) or ``"empty"``.
+
+    The bits may be overwritten in place (``grid.bits.copy_(other.bits)``): a captured render sees the new grid on its next replay."""
+
+    def __init__(self, lo, hi, dims, bits, outside="evaluate"):
+        self.dims = _dims3(dims)
+        self.lo = np.asarray(lo, dtype=np.float32).reshape(3)
+        self.hi = np.asarray(hi, dtype=np.float32).reshape(3)
+        if not np.all(self.hi > self.lo):
+            raise ValueError("SkipGrid: hi must be > lo on every axis")
+        self.cell = (self.hi - self.lo) / np.asarray(self.dims, dtype=np.float32)
+        self.inv_cell = np.float32(1.0) / self.cell
+        if outside not in SKIP_OUTSIDE:
+            raise ValueError(f"SkipGrid: outside must be 'evaluate' or 'empty', got {outside!r}")
+        self.outside = outside
+        _lib.require_gpu(bits)
+        if bits.dtype != torch.int32 or bits.dim() != 1 or bits.shape[0] != self.n_words:
+            raise ValueError(f"SkipGrid: bits must be int32 [{self.n_words}], got {bits.dtype} {tuple(bits.shape)}")
+        self.bits = bits
+
+    @property
+    def n_cells(self):
+        return self.dims[0] * self.dims[1] * self.dims[2]
+
+    @property
+    def n_words(self):
+        return (self.n_cells + 31) // 32
+
+    def c_struct(self):
+        """The ``dmnerf_skip_grid`` of this grid (points into ``bits``)."""
+        g = _lib.SkipGridArgs()
+        for a in range(3):
+            g.lo[a], g.inv_cell[a], g.dims[a] = float(self.lo[a]), float(self.inv_cell[a]), self.dims[a]
+        g.outside = SKIP_OUTSIDE[self.outside]
+        g.d_bits = self.bits.data_ptr()
+        return g
+
+    @classmethod
+    def from_bits(cls, bits, lo, hi, dims, outside="evaluate", device="cuda"):
+        """From packed words: a numpy uint32 / int32 array or a tensor of ``ceil(cells / 32)`` words."""
+        if not torch.is_tensor(bits):
+            bits = torch.from_numpy(np.ascontiguousarray(np.asarray(bits)).astype(np.uint32).view(np.int32)).to(device)
+        return cls(lo, hi, dims, bits.contiguous(), outside)
+
+    @classmethod
+    def empty(cls, lo, hi, dims, outside="evaluate", device="cuda"):
+        """No cell set: the neutral element of ``|``; with ``outside="empty"`` nothing is evaluated at all."""
+        dims = _dims3(dims)
+        words = (dims[0] * dims[1] * dims[2] + 31) // 32
+        return cls(lo, hi, dims, torch.zeros(words, dtype=torch.int32, device=device), outside)
+
+    @classmethod
+    def full(cls, lo, hi, dims, outside="evaluate", device="cuda"):
+        """Every cell set: with ``outside="evaluate"`` the render equals the dense one."""
+        g = cls.empty(lo, hi, dims, outside, device)
+        g.bits.fill_(-1)
+        tail = g.n_cells & 31
+        if tail:
+            g.bits[-1] = (1 << tail) - 1
+        return g
+
+    @classmethod
+    def from_sigma(cls, sigma, lo, hi, threshold=0.0, dilate=1, outside="evaluate"):
+        """From densities ``sigma [dx, dy, dz]`` at the cells: a cell's bit is set iff any sigma in its ``(2 dilate + 1)^3``
+        neighbourhood, clipped at the faces, is ``> threshold``; NaN counts as occupied (``dmnerf_skip_grid_build``)."""
+        sigma = _lib.f32(sigma)
+        _lib.require_gpu(sigma)
+        if sigma.dim() != 3:
+            raise ValueError(f"SkipGrid.from_sigma expects sigma [dx, dy, dz], got {tuple(sigma.shape)}")
+        g = cls.empty(lo, hi, tuple(sigma.shape), outside, sigma.device)
+        dx, dy, dz = g.dims
+        _lib.check(_lib.load().dmnerf_skip_grid_build(_lib.ptr(sigma), dx, dy, dz, float(threshold), int(dilate), _lib.ptr(g.bits),
+                                                      _lib.stream()), "dmnerf_skip_grid_build")
+        return g
+
+    def cell_centres(self, i0=0, i1=None, device=None):
+        """The centres ``lo + (idx + 0.5) * cell`` of the cells of planes ``i0 .. i1 - 1`` -> ``[(i1 - i0) dy dz, 3]`` f32, in cell order
+        (f32 ops, one rounding each)."""
+        dx, dy, dz = self.dims
+        i1 = dx if i1 is None else int(i1)
+        dev = device or self.bits.device
+        ax = [(torch.arange(n0, n1, dtype=torch.float32, device=dev) + 0.5) * float(self.cell[a]) + float(self.lo[a])
+              for a, (n0, n1) in enumerate(((int(i0), i1), (0, dy), (0, dz)))]
+        ni = i1 - int(i0)
+        return torch.stack([ax[0][:, None, None].expand(ni, dy, dz), ax[1][None, :, None].expand(ni, dy, dz),
+                            ax[2][None, None, :].expand(ni, dy, dz)], dim=-1).reshape(-1, 3)
+
+    @classmethod
+    def from_model(cls, model_fine, lo, hi, dims=128, threshold=0.0, dilate=1, outside="evaluate", slab=1 << 20, fuse_heads=False,
+                   device="cuda"):
+        """From the network: sigma at the cell centres through ``query_density`` (the trunk-only kernel), in slabs of whole
+        i-planes of about ``slab`` points, then ``from_sigma``.  Nothing touches the host."""
+        g = cls.empty(lo, hi, dims, outside, device)
+        dx, dy, dz = g.dims
+        sigma = torch.empty(dx, dy, dz, dtype=torch.float32, device=g.bits.device)
+        step = max(1, int(slab) // (dy * dz))
+        for i0 in range(0, dx, step):
+            i1 = min(i0 + step, dx)
+            sigma[i0:i1] = query_density(model_fine, g.cell_centres(i0, i1), fuse_heads=fuse_heads).reshape(i1 - i0, dy, dz)
+        return cls.from_sigma(sigma, lo, hi, threshold=threshold, dilate=dilate, outside=outside)
+
+    def unpack(self):
+        """The bits as a bool tensor ``[dx, dy, dz]`` on the device."""
+        g = torch.arange(self.n_cells, device=self.bits.device)
+        return (((self.bits[g >> 5] >> (g & 31)) & 1) != 0).reshape(self.dims)
+
+    def occupancy(self):
+        """Fraction of set cells (a device scalar)."""
+        return self.unpack().float().mean()

@@ -184,18 +184,11 @@ def fine_eligible(model_coarse, model_fine, args):
             and int(args.N_importance) >= 1 and not weights.split_mode(args))
 
 
-def dm_nerf_fine(rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args,
-                 t_rand=None, u=None, _events=None):
-    """``dm_nerf`` for a caller that keeps the fine level only, as ``render_test`` does (networks/tester.py:71-77 reads
-    ``rgb_fine``, ``ins_fine``, ``depth_fine``): returns ``{'rgb_fine', 'ins_fine', 'depth_fine', 'z_vals_fine', 'raw_fine'}``,
-    each ``torch.equal`` to the same key of ``dm_nerf`` called with the same arguments and draws.
-
-    Of the coarse level only the compositing weights reach the fine one (render.py:66-70) and they depend on the density alone
-    (:6-20), so the coarse network is evaluated up to ``density_linear`` (``dmnerf_mlp_fwd_rays_density``): no heads, no
-    ``raw_coarse``, no coarse maps -- 29 % fewer MFMAs in that launch.  Arguments, validation and the order of the RNG draws are
-    ``dm_nerf``'s.  Only for calls that are ``fine_eligible``; anything else raises (there is no silent detour)."""
+def _fine_prepare(who, rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args, t_rand, u, _events):
+    """Validation, draws, outputs and the filled ``RenderFineArgs`` of one fine-only render -> ``(out, a, keep)``; ``keep`` holds the
+    tensors the struct points into."""
     if not fine_eligible(model_coarse, model_fine, args):
-        raise ValueError("dm_nerf_fine: inference with the 8 x 256 network, N_importance >= 1 and no args.mfma_split only -- use dm_nerf")
+        raise ValueError(f"{who}: inference with the 8 x 256 network, N_importance >= 1 and no args.mfma_split only -- use dm_nerf")
     for emb, want in ((position_embedder, model_fine.input_ch_pts), (view_embedder, model_fine.input_ch_views)):
         if getattr(emb, "out_dim", want) != want:
             raise ValueError("dm_nerf: the embedders' out_dim does not match the models' input channels")
@@ -234,7 +227,68 @@ def dm_nerf_fine(rays, position_embedder, view_embedder, model_coarse, model_fin
         for e in _events:
             e.record()               # torch creates the hipEvent_t lazily; the library re-records it in place
         a.ev_fine_mlp_begin, a.ev_fine_mlp_end = _events[0].cuda_event, _events[1].cuda_event
+    return out, a, (rays_o, rays_d, z_in, t_rand, u, z_c, sigma, ws)
+
+
+def dm_nerf_fine(rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args,
+                 t_rand=None, u=None, _events=None):
+    """``dm_nerf`` for a caller that keeps the fine level only, as ``render_test`` does (networks/tester.py:71-77 reads
+    ``rgb_fine``, ``ins_fine``, ``depth_fine``): returns ``{'rgb_fine', 'ins_fine', 'depth_fine', 'z_vals_fine', 'raw_fine'}``,
+    each ``torch.equal`` to the same key of ``dm_nerf`` called with the same arguments and draws.
+
+    Of the coarse level only the compositing weights reach the fine one (render.py:66-70) and they depend on the density alone
+    (:6-20), so the coarse network is evaluated up to ``density_linear`` (``dmnerf_mlp_fwd_rays_density``): no heads, no
+    ``raw_coarse``, no coarse maps -- 29 % fewer MFMAs in that launch.  Arguments, validation and the order of the RNG draws are
+    ``dm_nerf``'s.  Only for calls that are ``fine_eligible``; anything else raises (there is no silent detour)."""
+    out, a, _keep = _fine_prepare("dm_nerf_fine", rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args,
+                                  t_rand, u, _events)
     _lib.check(_lib.load().dmnerf_render_rays_fwd_fine(ctypes.byref(a), _lib.stream()), "dmnerf_render_rays_fwd_fine")
+    if getattr(args, "is_train", False) and getattr(args, "N_ins", None) is not None:
+        out['ins_fine'] = out['ins_fine'][-args.N_ins:]          # render.py:88-90
+    return out
+
+
+SKIP_LEVELS = {"coarse": 1, "fine": 2}          # DMNERF_SKIP_LEVEL_* (include/dmnerf_hip.h)
+
+
+def dm_nerf_fine_skip(rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args, grid,
+                      levels=("coarse", "fine"), t_rand=None, u=None, _events=None):
+    """``dm_nerf_fine`` that does not march through empty space: at the levels named in ``levels`` the network is evaluated only
+    at the samples whose cell of ``grid`` (a ``field.SkipGrid``) is set -- or that lie outside its box, with ``grid.outside ==
+    "evaluate"`` -- and the other rows of the density / of ``raw_fine`` are zero.  A zero row is exactly neutral to the compositing
+    ("Skipping empty space"), so every key equals the dense render with those rows masked; with ``SkipGrid.full`` it equals
+    ``dm_nerf_fine`` bit for bit.  Returns ``dm_nerf_fine``'s keys plus ``n_eval``: int32 ``[2]`` on the device, the samples evaluated
+    at the coarse and at the fine level.  The counts never reach the host, so the call can be captured in a graph and replayed after
+    the grid's bits were overwritten in place.
+
+    ``levels=("fine",)`` leaves the coarse pass dense: the grid comes from the FINE network's density, and masking the coarse
+    network by it is an approximation the caller opts into.  Eligibility, validation and the order of the RNG draws are
+    ``dm_nerf_fine``'s; anything else raises."""
+    from .. import field
+    if not isinstance(grid, field.SkipGrid):
+        raise TypeError("dm_nerf_fine_skip: grid must be a field.SkipGrid")
+    levels = (levels,) if isinstance(levels, str) else tuple(levels)
+    if not levels or any(l not in SKIP_LEVELS for l in levels):
+        raise ValueError(f"dm_nerf_fine_skip: levels must name 'coarse' and / or 'fine', got {levels}")
+    out, a, _keep = _fine_prepare("dm_nerf_fine_skip", rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse,
+                                  args, t_rand, u, _events)
+    dev = out['raw_fine'].device
+    if grid.bits.device != dev:
+        raise RuntimeError("dm_nerf_fine_skip: the grid lives on another device than the rays")
+    N, SF = out['z_vals_fine'].shape
+    if N * SF >= 2 ** 31:
+        raise ValueError(f"dm_nerf_fine_skip: {N * SF} samples do not fit the int32 selection; render in smaller chunks")
+    lib = _lib.load()
+    sel = torch.empty(max(N * SF, 1), dtype=torch.int32, device=dev)
+    flag = torch.empty(max(N * SF, 1), dtype=torch.uint8, device=dev)
+    work = torch.empty(int(lib.dmnerf_skip_select_work_ints(N * SF)), dtype=torch.int32, device=dev)
+    out['n_eval'] = torch.empty(2, dtype=torch.int32, device=dev)
+    k = _lib.RenderFineSkipArgs()
+    k.fine = a
+    k.grid = grid.c_struct()
+    k.d_sel, k.d_flag, k.d_select_ws, k.d_n_eval = sel.data_ptr(), flag.data_ptr(), work.data_ptr(), out['n_eval'].data_ptr()
+    k.levels = sum(SKIP_LEVELS[l] for l in set(levels))
+    _lib.check(lib.dmnerf_render_rays_fwd_fine_skip(ctypes.byref(k), _lib.stream()), "dmnerf_render_rays_fwd_fine_skip")
     if getattr(args, "is_train", False) and getattr(args, "N_ins", None) is not None:
         out['ins_fine'] = out['ins_fine'][-args.N_ins:]          # render.py:88-90
     return out

@@ -632,6 +632,59 @@ typedef struct {
 } dmnerf_render_fine_args;
 int dmnerf_render_rays_fwd_fine(const dmnerf_render_fine_args* args, void* stream);
 
+/* A render that does not march through empty space (opt-in; csrc/skip.hip, csrc/mlp_fwd_sparse.hip).  An occupancy bit grid marks
+ * the cells of an axis-aligned world box that hold density; a sample whose cell is clear is not evaluated and its row of raw /
+ * sigma is zero, which is exactly neutral to the compositing: alpha = 1 - exp(-0) = 0, so its weight is exactly 0, and its rgb,
+ * depth and object terms are 0 * x ("Skipping empty space").  Replaces the dense pts -> embed -> network evaluation of
+ * networks/render.py:49-61 (coarse) and :71-83 (fine) by one over the marked samples only.  Additive (the ABI version stays).
+ *   dmnerf_skip_grid: lo / inv_cell / dims of the box, one bit per cell: cell g = (i * dims[1] + j) * dims[2] + k is bit g & 31 of
+ *     word g >> 5 of d_bits [ceil(cells / 32)].  outside: the flag of a sample outside the box.
+ *   dmnerf_skip_grid_build: bit(g) = any d_sigma [dx,dy,dz] in the (2 dilate + 1)^3 neighbourhood of g, clipped at the faces, is
+ *     > threshold; NaN counts as occupied.  0 <= dilate <= 4; the unused bits of the last word are written 0.
+ *   dmnerf_skip_select: for sample m = n * S + s: p = o + d * z (separate multiply and add, as networks/render.py:49),
+ *     c_a = floorf((p_a - lo_a) * inv_cell_a) with each operation rounded to f32 on its own; inside iff 0 <= c_a < dims_a on the float
+ *     for all three axes (a NaN point is outside).  d_flag [N,S] = the cell's bit, or the outside policy; d_sel = the flagged m in
+ *     ascending order (prefix sums: the same list every run); d_count [1] = their number, on the device.  d_work: scratch of
+ *     dmnerf_skip_select_work_ints(N * S) int32.  N * S < 2^31.
+ *   dmnerf_mlp_fwd_rays_sel / dmnerf_mlp_fwd_rays_density_sel: dmnerf_mlp_fwd_rays (fused_heads = 1: dmnerf_mlp_fwd_rays_fused) /
+ *     dmnerf_mlp_fwd_rays_density on the samples d_sel [0, *d_count) only: those rows of d_raw [N*S, 4+C] / entries of d_sigma [N*S]
+ *     are written, bit-identical to the dense call's; every other row is left untouched (the caller zero-fills).  The batch size is
+ *     read on the device; d_sel is read below *d_count only; nothing synchronises, so the chain can be captured in a graph and
+ *     replayed with another grid.  N * S < 2^31.
+ *   dmnerf_render_rays_fwd_fine_skip: dmnerf_render_rays_fwd_fine with the levels in `levels` (bit 0 coarse, bit 1 fine) evaluated
+ *     through the grid: jitter, select on z_coarse, zero-fill of sigma_ws, sparse density network, weights, resample + merge, select
+ *     on z_fine, zero-fill of raw_fine, sparse full network, compositing.  A level whose bit is clear runs dense.
+ *     d_n_eval [2] = samples evaluated per level.  d_flag, d_sel: [N, S+n_imp]; d_select_ws: dmnerf_skip_select_work_ints(N * (S+n_imp)). */
+#define DMNERF_SKIP_OUTSIDE_EVALUATE 0
+#define DMNERF_SKIP_OUTSIDE_EMPTY 1
+#define DMNERF_SKIP_LEVEL_COARSE 1
+#define DMNERF_SKIP_LEVEL_FINE 2
+typedef struct {
+    float lo[3];
+    float inv_cell[3];
+    int dims[3];
+    int outside;                /* DMNERF_SKIP_OUTSIDE_* */
+    const uint32_t* d_bits;
+} dmnerf_skip_grid;
+int dmnerf_skip_grid_build(const float* d_sigma, int dx, int dy, int dz, float threshold, int dilate, uint32_t* d_bits, void* stream);
+int64_t dmnerf_skip_select_work_ints(int64_t M);
+int dmnerf_skip_select(const dmnerf_skip_grid* grid, const float* d_rays_o, const float* d_rays_d, const float* d_z, int64_t N, int S,
+                       uint8_t* d_flag, int* d_sel, int* d_count, int* d_work, void* stream);
+int dmnerf_mlp_fwd_rays_sel(const float* d_blob, int ins_num, int fused_heads, const float* d_rays_o, const float* d_rays_d,
+                            const float* d_z, int64_t N, int S, const int* d_sel, const int* d_count, float* d_raw, void* stream);
+int dmnerf_mlp_fwd_rays_density_sel(const float* d_blob, int ins_num, const float* d_rays_o, const float* d_rays_d, const float* d_z,
+                                    int64_t N, int S, const int* d_sel, const int* d_count, float* d_sigma, void* stream);
+typedef struct {
+    dmnerf_render_fine_args fine;
+    dmnerf_skip_grid grid;
+    int* d_sel;                 /* scratch [N, S+n_imp] */
+    int* d_n_eval;              /* out [2]: samples evaluated at the coarse / the fine level */
+    uint8_t* d_flag;            /* scratch [N, S+n_imp] */
+    int* d_select_ws;           /* scratch, dmnerf_skip_select_work_ints(N * (S+n_imp)) */
+    int levels;                 /* DMNERF_SKIP_LEVEL_* mask */
+} dmnerf_render_fine_skip_args;
+int dmnerf_render_rays_fwd_fine_skip(const dmnerf_render_fine_skip_args* args, void* stream);
+
 /* The density of the field off the rays: what mesh_main (tools/mesh_generator.py:12-143) asks the fine network for (csrc/mlp_fwd_points.hip).
  * Both entries run dmnerf_mlp_fwd_rays_density's body -- encoding, trunk, density_linear; no direction, no heads -- so sigma is
  * raw[..., 3] of the full network bit for bit, and both take the forward blob or the fused-heads blob.  Neither allocates nor

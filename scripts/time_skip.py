@@ -1,0 +1,97 @@
+"""Time the render that skips empty space (render.dm_nerf_fine_skip) against the dense fine-only render, by grid occupancy.
+
+    python scripts/time_skip.py [--out profiles/skip/timing.jsonl]
+
+One 640 x 480 frame, 64 + 128 samples, chunks of 4096 rays, ins_num 13, the benchmark's models and camera.  The grids are synthetic:
+a 128^3 box round the scene whose cells are set at random with probability 5, 10, 25, 50 and 100 %, ``outside="empty"`` so that the
+occupancy is the fraction of in-box samples that is evaluated.  The 100 % row is the overhead of select, zero-fill and the
+over-sized launch; the ``dense`` row is ``FrameRenderer`` without ``skip=`` in the same process.  Per row: HIP-event milliseconds
+of the whole frame, median and minimum of ``--iters`` runs after ``--warmup``, rays/s, and the samples evaluated per level.  The
+first line records the device and its clocks as ``rocm-smi --showclocks`` reports them (read-only).  One JSON object per line."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def clocks():
+    try:
+        r = subprocess.run(["rocm-smi", "--showclocks", "--json"], capture_output=True, text=True, timeout=30)
+        return json.loads(r.stdout) if r.returncode == 0 else {"error": r.stderr[-200:]}
+    except Exception as e:                                           # the tool is optional
+        return {"error": repr(e)}
+
+
+def time_frame(make, iters, warmup):
+    """``make()`` -> a FrameRenderer; -> (median ms, min ms) of rendering all its chunks."""
+    ms = []
+    for it in range(warmup + iters):
+        fr = make()
+        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        b.record()
+        for i in range(fr.n_chunks):
+            fr.step(i)
+        e.record()
+        torch.cuda.synchronize()
+        if it >= warmup:
+            ms.append(b.elapsed_time(e))
+    return float(np.median(ms)), float(np.min(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dims", type=int, default=128)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import types
+    import bench_common as C
+    from dm_nerf_amd import distributed as D, field as F
+    from dm_nerf_amd.networks import render as R
+    from oracle import ref_cpu as O
+    dev = torch.device("cuda")
+    _, _, mc, mf = C.build_models(dev)
+    H, W = 480, 640
+    K = O.dmsr_intrinsics(H, W)
+    c2w = O.pose_spherical(30.0, -65.0, 7.0).to(dev)
+    args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
+    lo, hi = (-8.0, -8.0, -8.0), (8.0, 8.0, 8.0)
+    lines = [{"leg": "device", "name": torch.cuda.get_device_name(0), "clocks": clocks(), "iters": a.iters, "warmup": a.warmup}]
+
+    def renderer(**kw):
+        return D.FrameRenderer(H, W, K, c2w, (mc, mf), 4.0, 15.0, args, chunk=4096, n_samples=64, **kw)
+
+    with torch.no_grad():
+        med, mn = time_frame(renderer, a.iters, a.warmup)
+        lines.append({"leg": "dense", "ms_median": med, "ms_min": mn, "rays_per_s": H * W / med * 1e3})
+        for pct in (5, 10, 25, 50, 100):
+            occ = np.random.RandomState(pct).rand(a.dims, a.dims, a.dims) < pct / 100.0
+            words = np.packbits(occ.reshape(-1), bitorder="little")
+            words = np.concatenate([words, np.zeros(-words.size % 4, np.uint8)]).view(np.uint32)
+            grid = F.SkipGrid.from_bits(words, lo, hi, a.dims, outside="empty")
+            med, mn = time_frame(lambda: renderer(skip=grid), a.iters, a.warmup)
+            fr = renderer()
+            n_eval = torch.zeros(2, dtype=torch.int64, device=dev)
+            for i in range(fr.n_chunks):
+                s, e = i * 4096, min((i + 1) * 4096, H * W)
+                out = R.dm_nerf_fine_skip(torch.stack([fr.rays_o[s:e], fr.rays_d[s:e]]), None, None, mc, mf, fr.z_full[:e - s], args, grid)
+                n_eval += out["n_eval"]
+            lines.append({"leg": "skip", "grid_occupancy": float(grid.occupancy()), "ms_median": med, "ms_min": mn,
+                          "rays_per_s": H * W / med * 1e3, "n_eval": n_eval.tolist(), "n_dense": [H * W * 64, H * W * 192]})
+    text = "\n".join(json.dumps(l) for l in lines)
+    print(text, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
