@@ -197,6 +197,11 @@ SIGNATURES = {
     "dmnerf_skip_select": (c_int, [ctypes.POINTER(SkipGridArgs), c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_mlp_fwd_rays_sel": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_mlp_fwd_rays_density_sel": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_blob_f16_density_words": (c_i64, [c_int]),
+    "dmnerf_blob_f16_density_from_f16": (c_int, [c_vp, c_int, c_vp, c_vp]),
+    "dmnerf_mlp_fwd_rays_density_f16": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
+    "dmnerf_mlp_fwd_rays_f16_sel": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_mlp_fwd_rays_density_f16_sel": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_render_rays_fwd_fine_skip": (c_int, [ctypes.POINTER(RenderFineSkipArgs), c_vp]),
 }
 

@@ -84,7 +84,7 @@ extern "C" int dmnerf_render_rays_fwd(const dmnerf_render_args* a, void* stream)
 // coarse maps.  Everything the fine level sees (the weights, hence z_vals_fine) is bit-identical to dmnerf_render_rays_fwd.
 extern "C" int dmnerf_render_rays_fwd_fine(const dmnerf_render_fine_args* a, void* stream) {
     if (!a) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine: null args");
-    if (a->fused_heads != 0 && a->fused_heads != 1)
+    if (a->fused_heads != 0 && a->fused_heads != 1 && a->fused_heads != 3)
         return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine: fused_heads %d unsupported (the split-operand blobs go through dmnerf_render_rays_fwd)", a->fused_heads);
     if (a->N == 0 && a->S >= 3 && a->n_imp >= 1) return DMNERF_OK;      // an empty chunk: its buffers may be null
     if (!a->d_blob_coarse || !a->d_blob_fine || !a->d_rays_o || !a->d_rays_d || !a->d_z_in || !a->d_u || !a->d_z_coarse ||
@@ -93,6 +93,10 @@ extern "C" int dmnerf_render_rays_fwd_fine(const dmnerf_render_fine_args* a, voi
     const int64_t N = a->N;
     const int S = a->S, SF = a->S + a->n_imp, C = a->ins_num + 1;
     if (N < 0 || S < 3 || a->n_imp < 1) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine: bad N=%lld S=%d n_imp=%d", (long long)N, S, a->n_imp);
+    // f16x2: the coarse blob is the f16 DENSITY blob, another format than the fine one -- one buffer cannot be both (a caller that
+    // passes the model's f16 blob twice would get the density of the wrong weight groups, silently)
+    if (a->fused_heads == 3 && a->d_blob_coarse == a->d_blob_fine)
+        return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine: fused_heads 3 wants the f16 density blob as d_blob_coarse, got d_blob_fine twice");
     int rc;
     // stratified jitter (render.py:40-47) or pass-through copy of the coarse grid
     if (a->d_t_rand) {
@@ -102,11 +106,14 @@ extern "C" int dmnerf_render_rays_fwd_fine(const dmnerf_render_fine_args* a, voi
             return dmn_check_launch("render_rays_fwd_fine: z copy");
     }
     // coarse network as far as the density (render.py:49-61), its weights (:6-20), resampling + merge (:66-70)
-    if ((rc = dmnerf_mlp_fwd_rays_density(a->d_blob_coarse, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, a->d_sigma_ws, stream))) return rc;
+    // (fused_heads == 3, f16x2: d_blob_coarse is the f16 density blob, d_blob_fine the f16 blob)
+    const bool f16 = a->fused_heads == 3;
+    auto density = f16 ? dmnerf_mlp_fwd_rays_density_f16 : dmnerf_mlp_fwd_rays_density;
+    if ((rc = density(a->d_blob_coarse, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, a->d_sigma_ws, stream))) return rc;
     if ((rc = dmnerf_weights_from_sigma(a->d_sigma_ws, a->d_z_coarse, a->d_rays_d, N, S, a->d_weights_ws, stream))) return rc;
     if ((rc = dmnerf_importance_resample(a->d_z_coarse, a->d_weights_ws, a->d_u, a->u_row_stride, N, S, a->n_imp, a->d_z_fine, nullptr, stream))) return rc;
     // fine network + compositing (render.py:71-86)
-    auto mlp = a->fused_heads ? dmnerf_mlp_fwd_rays_fused : dmnerf_mlp_fwd_rays;
+    auto mlp = f16 ? dmnerf_mlp_fwd_rays_f16 : a->fused_heads ? dmnerf_mlp_fwd_rays_fused : dmnerf_mlp_fwd_rays;
     if (a->ev_fine_mlp_begin) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_begin, (hipStream_t)stream);
     if ((rc = mlp(a->d_blob_fine, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_fine, N, SF, a->d_raw_fine, stream))) return rc;
     if (a->ev_fine_mlp_end) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_end, (hipStream_t)stream);
@@ -123,7 +130,7 @@ int dmn_skip_set_int(int* d_p, int v, hipStream_t stream);      // skip.hip
 extern "C" int dmnerf_render_rays_fwd_fine_skip(const dmnerf_render_fine_skip_args* k, void* stream) {
     if (!k) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: null args");
     const dmnerf_render_fine_args* a = &k->fine;
-    if (a->fused_heads != 0 && a->fused_heads != 1)
+    if (a->fused_heads != 0 && a->fused_heads != 1 && a->fused_heads != 3)
         return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: fused_heads %d unsupported (no split-operand kernels over a selection)", a->fused_heads);
     if (k->levels & ~(DMNERF_SKIP_LEVEL_COARSE | DMNERF_SKIP_LEVEL_FINE)) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: bad levels mask %d", k->levels);
     const int64_t N = a->N;
@@ -132,6 +139,7 @@ extern "C" int dmnerf_render_rays_fwd_fine_skip(const dmnerf_render_fine_skip_ar
     if (N * SF >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: %lld samples do not fit the int32 selection", (long long)(N * SF));
     if (!k->d_n_eval) return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: null pointer in args");
     hipStream_t st = (hipStream_t)stream;
+    const bool f16 = a->fused_heads == 3;                                // f16x2: d_blob_coarse is the f16 density blob, d_blob_fine the f16 blob
     int rc;
     if (N == 0) {                                                        // an empty chunk: its buffers may be null
         if ((rc = dmn_skip_set_int(k->d_n_eval, 0, st))) return rc;
@@ -141,6 +149,8 @@ extern "C" int dmnerf_render_rays_fwd_fine_skip(const dmnerf_render_fine_skip_ar
         !a->d_sigma_ws || !a->d_weights_ws || !a->d_z_fine || !a->d_raw_fine || !a->d_rgb_fine || !a->d_depth_fine || !a->d_ins_fine ||
         !k->d_sel || !k->d_flag || !k->d_select_ws || !k->grid.d_bits)
         return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: null pointer in args");
+    if (f16 && a->d_blob_coarse == a->d_blob_fine)                       // (as in dmnerf_render_rays_fwd_fine: two formats, one buffer)
+        return dmn_fail(DMNERF_E_ARG, "render_rays_fwd_fine_skip: fused_heads 3 wants the f16 density blob as d_blob_coarse, got d_blob_fine twice");
     // stratified jitter (render.py:40-47) or pass-through copy of the coarse grid
     if (a->d_t_rand) {
         if ((rc = dmnerf_stratify(a->d_z_in, a->d_t_rand, N, S, a->d_z_coarse, stream))) return rc;
@@ -152,11 +162,12 @@ extern "C" int dmnerf_render_rays_fwd_fine_skip(const dmnerf_render_fine_skip_ar
     if (k->levels & DMNERF_SKIP_LEVEL_COARSE) {
         if ((rc = dmnerf_skip_select(&k->grid, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, k->d_flag, k->d_sel, k->d_n_eval, k->d_select_ws, stream))) return rc;
         if (hipError_t e = hipMemsetAsync(a->d_sigma_ws, 0, sizeof(float) * N * S, st); e != hipSuccess) return dmn_fail_hip(e, "render_rays_fwd_fine_skip: sigma fill");
-        if ((rc = dmnerf_mlp_fwd_rays_density_sel(a->d_blob_coarse, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, k->d_sel, k->d_n_eval,
-                                                  a->d_sigma_ws, stream))) return rc;
+        auto density_sel = f16 ? dmnerf_mlp_fwd_rays_density_f16_sel : dmnerf_mlp_fwd_rays_density_sel;
+        if ((rc = density_sel(a->d_blob_coarse, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, k->d_sel, k->d_n_eval, a->d_sigma_ws, stream))) return rc;
     } else {
         if ((rc = dmn_skip_set_int(k->d_n_eval, (int)(N * S), st))) return rc;
-        if ((rc = dmnerf_mlp_fwd_rays_density(a->d_blob_coarse, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, a->d_sigma_ws, stream))) return rc;
+        auto density = f16 ? dmnerf_mlp_fwd_rays_density_f16 : dmnerf_mlp_fwd_rays_density;
+        if ((rc = density(a->d_blob_coarse, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_coarse, N, S, a->d_sigma_ws, stream))) return rc;
     }
     if ((rc = dmnerf_weights_from_sigma(a->d_sigma_ws, a->d_z_coarse, a->d_rays_d, N, S, a->d_weights_ws, stream))) return rc;
     if ((rc = dmnerf_importance_resample(a->d_z_coarse, a->d_weights_ws, a->d_u, a->u_row_stride, N, S, a->n_imp, a->d_z_fine, nullptr, stream))) return rc;
@@ -165,12 +176,16 @@ extern "C" int dmnerf_render_rays_fwd_fine_skip(const dmnerf_render_fine_skip_ar
         if ((rc = dmnerf_skip_select(&k->grid, a->d_rays_o, a->d_rays_d, a->d_z_fine, N, SF, k->d_flag, k->d_sel, k->d_n_eval + 1, k->d_select_ws, stream))) return rc;
         if (hipError_t e = hipMemsetAsync(a->d_raw_fine, 0, sizeof(float) * N * SF * (4 + C), st); e != hipSuccess) return dmn_fail_hip(e, "render_rays_fwd_fine_skip: raw fill");
         if (a->ev_fine_mlp_begin) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_begin, st);
-        if ((rc = dmnerf_mlp_fwd_rays_sel(a->d_blob_fine, a->ins_num, a->fused_heads, a->d_rays_o, a->d_rays_d, a->d_z_fine, N, SF, k->d_sel, k->d_n_eval + 1,
-                                          a->d_raw_fine, stream))) return rc;
+        if (f16)
+            rc = dmnerf_mlp_fwd_rays_f16_sel(a->d_blob_fine, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_fine, N, SF, k->d_sel, k->d_n_eval + 1, a->d_raw_fine, stream);
+        else
+            rc = dmnerf_mlp_fwd_rays_sel(a->d_blob_fine, a->ins_num, a->fused_heads, a->d_rays_o, a->d_rays_d, a->d_z_fine, N, SF, k->d_sel, k->d_n_eval + 1,
+                                         a->d_raw_fine, stream);
+        if (rc) return rc;
         if (a->ev_fine_mlp_end) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_end, st);
     } else {
         if ((rc = dmn_skip_set_int(k->d_n_eval + 1, (int)(N * SF), st))) return rc;
-        auto mlp = a->fused_heads ? dmnerf_mlp_fwd_rays_fused : dmnerf_mlp_fwd_rays;
+        auto mlp = f16 ? dmnerf_mlp_fwd_rays_f16 : a->fused_heads ? dmnerf_mlp_fwd_rays_fused : dmnerf_mlp_fwd_rays;
         if (a->ev_fine_mlp_begin) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_begin, st);
         if ((rc = mlp(a->d_blob_fine, a->ins_num, a->d_rays_o, a->d_rays_d, a->d_z_fine, N, SF, a->d_raw_fine, stream))) return rc;
         if (a->ev_fine_mlp_end) (void)hipEventRecord((hipEvent_t)a->ev_fine_mlp_end, st);

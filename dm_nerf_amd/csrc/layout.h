@@ -214,6 +214,20 @@ DMN_HD inline F16Layout make_f16_layout(int ins_num) {
     return S;
 }
 
+// Split-f16 DENSITY blob (mlp_f16_density.hip: the network cut off behind density_linear): the F16Layout table unchanged, then
+// the trunk groups and the two density groups of the forward stream, copied (dmnerf_blob_f16_density_from_f16), then the landing
+// groups -- what the linear fetch of the kernel meets when it leaves the heads out:
+//   mlps.0 .. mlps.7 (F16_TRUNK_GROUPS = 120, stream groups 0..119) | density (2 groups, stream groups 138, 139 behind
+//   9 rgb hidden', 8 ins hidden' and 1 rgb_linear group)                                               = 122 groups
+constexpr int F16_TRUNK_GROUPS = 4 + 4 * 16 + 20 + 2 * 16;
+constexpr int F16_DENSITY_GROUP0 = F16_TRUNK_GROUPS + 9 + 8 + 1, F16_DENSITY_GROUPS = 2;
+DMN_HD inline F16Layout make_f16_density_layout(int ins_num) {
+    F16Layout S = make_f16_layout(ins_num);
+    S.n_groups = F16_TRUNK_GROUPS + F16_DENSITY_GROUPS;
+    S.total = S.stream + (int64_t)(S.n_groups + F16_LA) * F16_GROUP_WORDS;
+    return S;
+}
+
 // Split-f16 blob of the OPT-IN data-gradient kernel (mlp_bwd_f16.hip): W^T groups in the F16Layout group format
 // (A tile rows = the layer's INPUTS 32 ob + (lane & 31), k = its OUTPUTS in accumulator order cfeat(8 kb + q, lane >> 5)):
 //   ins_linear^T (nob 4: the 128 g2 rows; 2 OBI k-blocks = OBI groups) | F^T (4 passes x 2 groups, nob 2: 8 k-blocks = dg1) |

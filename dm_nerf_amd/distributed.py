@@ -356,7 +356,7 @@ def _default_raygen(H, W, K, c2w, row0, nrows):
 def _default_render_chunk(rays_o, rays_d, z, models, args, events=None):
     from .networks import render
     # the frame keeps the fine level only (tester.py:71-77): where the density-only coarse pass exists, skip the coarse heads
-    fn = render.dm_nerf_fine if render.fine_eligible(models[0], models[1], args) else render.dm_nerf
+    fn = render.fine_renderer(models[0], models[1], args)
     out = fn(torch.stack([rays_o, rays_d]), None, None, models[0], models[1], z, args, _events=events)
     return out['rgb_fine'], out['ins_fine'], out['depth_fine']
 

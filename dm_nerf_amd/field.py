@@ -167,7 +167,7 @@ def label_points(vertices, normals, models, args, chunk=None):
     lib = _lib.load()
     z = None
     with torch.no_grad():
-        render = R.dm_nerf_fine if R.fine_eligible(model_coarse, model_fine, args) else R.dm_nerf
+        render = R.fine_renderer(model_coarse, model_fine, args)
         for s in range(0, V, chunk):
             e = min(s + chunk, V)
             if z is None or z.shape[0] != e - s:

@@ -173,6 +173,18 @@ class DM_NeRF(nn.Module):
             self._blob_h_key = key
         return self._blob_h
 
+    def blob_f16_density(self):
+        """Split-f16 DENSITY blob (``dmnerf_mlp_fwd_rays_density_f16``): the table, the trunk groups and the ``density_linear`` groups of
+        ``blob_f16()``, copied on the device; same refresh rule as ``blob_f16`` (it is re-made whenever that blob is re-packed)."""
+        src = self.blob_f16()
+        if getattr(self, "_blob_hd", None) is None or self._blob_hd_src is not src:
+            lib = _lib.load()
+            out = torch.empty(int(lib.dmnerf_blob_f16_density_words(self.ins_num)), dtype=torch.float32, device=src.device)
+            _lib.check(lib.dmnerf_blob_f16_density_from_f16(_lib.ptr(src), self.ins_num, _lib.ptr(out), _lib.stream()),
+                       "dmnerf_blob_f16_density_from_f16")
+            self._blob_hd, self._blob_hd_src = out, src
+        return self._blob_hd
+
     def blob_t_f16(self):
         """Split-f16 W^T blob of the opt-in data-gradient kernel (training with ``args.mfma_split = "f16x2"``)."""
         self._check_supported()

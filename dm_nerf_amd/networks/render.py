@@ -179,16 +179,27 @@ def _training(model_coarse, model_fine):
 
 def fine_eligible(model_coarse, model_fine, args):
     """Can ``dm_nerf_fine`` serve this call?  Inference, the shipped 8 x 256 network in both models, hierarchical sampling on,
-    and the f32 kernels (the split-operand modes have no density-only variant)."""
+    and the f32 kernels (f16x2 has a density-only variant of its own: ``fine_f16_eligible`` / ``dm_nerf_fine_f16``; bf16x3 has none)."""
     return (not _training(model_coarse, model_fine) and model_coarse._fused_ok() and model_fine._fused_ok()
             and int(args.N_importance) >= 1 and not weights.split_mode(args))
 
 
-def _fine_prepare(who, rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args, t_rand, u, _events):
+def fine_f16_eligible(model_coarse, model_fine, args):
+    """Can ``dm_nerf_fine_f16`` serve this call?  ``fine_eligible``'s conditions with ``args.mfma_split = "f16x2"`` instead of the f32
+    kernels (bf16x3 has no density-only variant)."""
+    return (not _training(model_coarse, model_fine) and model_coarse._fused_ok() and model_fine._fused_ok()
+            and int(args.N_importance) >= 1 and weights.split_mode(args) == "f16x2")
+
+
+def _fine_prepare(who, rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args, t_rand, u, _events,
+                  modes=("f32",)):
     """Validation, draws, outputs and the filled ``RenderFineArgs`` of one fine-only render -> ``(out, a, keep)``; ``keep`` holds the
-    tensors the struct points into."""
-    if not fine_eligible(model_coarse, model_fine, args):
-        raise ValueError(f"{who}: inference with the 8 x 256 network, N_importance >= 1 and no args.mfma_split only -- use dm_nerf")
+    tensors the struct points into.  ``modes``: which of the f32 kernels (``fine_eligible``) and the f16x2 kernels
+    (``fine_f16_eligible``) the caller serves."""
+    f16 = "f16x2" in modes and fine_f16_eligible(model_coarse, model_fine, args)
+    if not f16 and not ("f32" in modes and fine_eligible(model_coarse, model_fine, args)):
+        want = {("f32",): "no args.mfma_split", ("f16x2",): 'args.mfma_split = "f16x2"'}.get(tuple(modes), 'no args.mfma_split or "f16x2"')
+        raise ValueError(f"{who}: inference with the 8 x 256 network, N_importance >= 1 and {want} only -- use dm_nerf")
     for emb, want in ((position_embedder, model_fine.input_ch_pts), (view_embedder, model_fine.input_ch_views)):
         if getattr(emb, "out_dim", want) != want:
             raise ValueError("dm_nerf: the embedders' out_dim does not match the models' input channels")
@@ -211,9 +222,14 @@ def _fine_prepare(who, rays, position_embedder, view_embedder, model_coarse, mod
     fused = bool(getattr(args, "fuse_heads", False))
     pick = (lambda mdl: mdl.blob_fused()) if fused else (lambda mdl: mdl.blob())
     a = _lib.RenderFineArgs()
-    a.fused_heads = 1 if fused else 0
-    a.d_blob_coarse = pick(model_coarse).data_ptr()                  # (the trunk and its table entries are the same in both blobs)
-    a.d_blob_fine = pick(model_fine).data_ptr()
+    if f16:                                                          # the linear weight stream wants a density blob of its own
+        a.fused_heads = 3
+        a.d_blob_coarse = model_coarse.blob_f16_density().data_ptr()
+        a.d_blob_fine = model_fine.blob_f16().data_ptr()
+    else:
+        a.fused_heads = 1 if fused else 0
+        a.d_blob_coarse = pick(model_coarse).data_ptr()              # (the trunk and its table entries are the same in both blobs)
+        a.d_blob_fine = pick(model_fine).data_ptr()
     a.ins_num = ins_num
     a.d_rays_o, a.d_rays_d, a.d_z_in = rays_o.data_ptr(), rays_d.data_ptr(), z_in.data_ptr()
     a.d_t_rand = t_rand.data_ptr() if t_rand is not None else None
@@ -248,6 +264,41 @@ def dm_nerf_fine(rays, position_embedder, view_embedder, model_coarse, model_fin
     return out
 
 
+def _f16_probe(model_coarse, model_fine, args, keep, out):
+    """The opt-in f16 range probe of ``dm_nerf`` (DMNERF_CHECK_F16=1 / args.check_f16), on the same depths."""
+    from .. import autograd
+    if autograd.f16_check_enabled(args):
+        rays_o, rays_d, z_c = keep[0], keep[1], keep[5]
+        autograd.f16x2_probe(model_coarse, rays_o, rays_d, z_c)
+        autograd.f16x2_probe(model_fine, rays_o, rays_d, out['z_vals_fine'])
+        autograd.check_f16x2(rays_o.device)
+
+
+def dm_nerf_fine_f16(rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args,
+                     t_rand=None, u=None, _events=None):
+    """``dm_nerf_fine`` on the split-f16 kernels (``args.mfma_split = "f16x2"``): the coarse network runs as far as ``density_linear``
+    (``dmnerf_mlp_fwd_rays_density_f16``, 122 instead of 140 + OBX weight groups), the fine one is ``dmnerf_mlp_fwd_rays_f16``.  Each
+    returned key is ``torch.equal`` to the same key of ``dm_nerf`` called with the same f16x2 args and draws.  Signature, validation,
+    draw order and keys are ``dm_nerf_fine``'s; only for calls that are ``fine_f16_eligible``, anything else raises."""
+    out, a, keep = _fine_prepare("dm_nerf_fine_f16", rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse,
+                                 args, t_rand, u, _events, modes=("f16x2",))
+    _lib.check(_lib.load().dmnerf_render_rays_fwd_fine(ctypes.byref(a), _lib.stream()), "dmnerf_render_rays_fwd_fine")
+    _f16_probe(model_coarse, model_fine, args, keep, out)
+    if getattr(args, "is_train", False) and getattr(args, "N_ins", None) is not None:
+        out['ins_fine'] = out['ins_fine'][-args.N_ins:]          # render.py:88-90
+    return out
+
+
+def fine_renderer(model_coarse, model_fine, args):
+    """The chunk renderer of a caller that keeps the fine level only: ``dm_nerf_fine`` / ``dm_nerf_fine_f16`` where eligible, else
+    ``dm_nerf``."""
+    if fine_eligible(model_coarse, model_fine, args):
+        return dm_nerf_fine
+    if fine_f16_eligible(model_coarse, model_fine, args):
+        return dm_nerf_fine_f16
+    return dm_nerf
+
+
 SKIP_LEVELS = {"coarse": 1, "fine": 2}          # DMNERF_SKIP_LEVEL_* (include/dmnerf_hip.h)
 
 
@@ -262,8 +313,9 @@ def dm_nerf_fine_skip(rays, position_embedder, view_embedder, model_coarse, mode
     the grid's bits were overwritten in place.
 
     ``levels=("fine",)`` leaves the coarse pass dense: the grid comes from the FINE network's density, and masking the coarse
-    network by it is an approximation the caller opts into.  Eligibility, validation and the order of the RNG draws are
-    ``dm_nerf_fine``'s; anything else raises."""
+    network by it is an approximation the caller opts into.  Serves a call that is ``fine_eligible`` (the f32 kernels) or
+    ``fine_f16_eligible`` (``args.mfma_split = "f16x2"``: ``dmnerf_mlp_fwd_rays_density_f16_sel`` / ``.._f16_sel``, equal to
+    ``dm_nerf_fine_f16`` with ``SkipGrid.full``); validation and the order of the RNG draws are ``dm_nerf_fine``'s; anything else raises."""
     from .. import field
     if not isinstance(grid, field.SkipGrid):
         raise TypeError("dm_nerf_fine_skip: grid must be a field.SkipGrid")
@@ -271,7 +323,7 @@ def dm_nerf_fine_skip(rays, position_embedder, view_embedder, model_coarse, mode
     if not levels or any(l not in SKIP_LEVELS for l in levels):
         raise ValueError(f"dm_nerf_fine_skip: levels must name 'coarse' and / or 'fine', got {levels}")
     out, a, _keep = _fine_prepare("dm_nerf_fine_skip", rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse,
-                                  args, t_rand, u, _events)
+                                  args, t_rand, u, _events, modes=("f32", "f16x2"))
     dev = out['raw_fine'].device
     if grid.bits.device != dev:
         raise RuntimeError("dm_nerf_fine_skip: the grid lives on another device than the rays")
@@ -289,6 +341,8 @@ def dm_nerf_fine_skip(rays, position_embedder, view_embedder, model_coarse, mode
     k.d_sel, k.d_flag, k.d_select_ws, k.d_n_eval = sel.data_ptr(), flag.data_ptr(), work.data_ptr(), out['n_eval'].data_ptr()
     k.levels = sum(SKIP_LEVELS[l] for l in set(levels))
     _lib.check(lib.dmnerf_render_rays_fwd_fine_skip(ctypes.byref(k), _lib.stream()), "dmnerf_render_rays_fwd_fine_skip")
+    if a.fused_heads == 3:
+        _f16_probe(model_coarse, model_fine, args, _keep, out)
     if getattr(args, "is_train", False) and getattr(args, "N_ins", None) is not None:
         out['ins_fine'] = out['ins_fine'][-args.N_ins:]          # render.py:88-90
     return out

@@ -598,7 +598,7 @@ int dmnerf_render_rays_fwd(const dmnerf_render_args* args, void* stream);
  *   dmnerf_weights_from_sigma: the weights of render_train (render.py:6-20) from that row: weights [N,S] = what
  *     dmnerf_composite_fwd writes for raw[..., 3] = sigma.
  *   dmnerf_render_rays_fwd_fine: jitter / z copy, density-only coarse, weights, resample + merge (render.py:66-70), the full fine
- *     network and its compositing (render.py:71-86).  fused_heads: 0 or 1 (the f32 blobs; the split-operand blobs are refused).
+ *     network and its compositing (render.py:71-86).  fused_heads: 0 or 1 (the f32 blobs), or 3 (f16x2, see below; bf16x3 is refused).
  *     d_z_coarse may alias d_z_in when d_t_rand is NULL.  Scratch: d_sigma_ws [N,S], d_weights_ws [N,S+n_imp].              */
 int dmnerf_mlp_fwd_rays_density(const float* d_blob, int ins_num, const float* d_rays_o, const float* d_rays_d,
                                 const float* d_z, int64_t N, int S, float* d_sigma, void* stream);
@@ -628,7 +628,7 @@ typedef struct {
     float* d_ins_fine;          /* [N,C-1]      'ins_fine'     */
     void* ev_fine_mlp_begin;    /* as in dmnerf_render_args */
     void* ev_fine_mlp_end;
-    int fused_heads;            /* 0 / 1 */
+    int fused_heads;            /* 0 / 1; 3 = f16x2: d_blob_coarse is the f16 density blob */
 } dmnerf_render_fine_args;
 int dmnerf_render_rays_fwd_fine(const dmnerf_render_fine_args* args, void* stream);
 
@@ -684,6 +684,30 @@ typedef struct {
     int levels;                 /* DMNERF_SKIP_LEVEL_* mask */
 } dmnerf_render_fine_skip_args;
 int dmnerf_render_rays_fwd_fine_skip(const dmnerf_render_fine_skip_args* args, void* stream);
+
+/* The two renders above on the OPT-IN split-f16 ("f16x2") kernels (csrc/mlp_f16_density.hip, csrc/mlp_f16_sparse.hip; the body of
+ * csrc/mlp_f16_impl.h with template flags).  Additive (the ABI version stays).
+ *   f16 density blob: dmnerf_blob_f16_density_words 32-bit words = [the f16 blob's 4096-float bias table | its 120 trunk groups
+ *     (mlps.0 .. mlps.7) | its 2 density_linear groups | 6 landing groups]; dmnerf_blob_f16_density_from_f16 copies them out of
+ *     a packed f16 blob (dmnerf_pack_f16) on `stream`, device to device.  Re-make it whenever the f16 blob is re-packed.
+ *   dmnerf_mlp_fwd_rays_density_f16: render.py:49-61 + DM_NeRF.forward up to density_linear (networks/dm_nerf.py:80-88,101):
+ *     sigma [N,S] = raw[..., 3] of dmnerf_mlp_fwd_rays_f16, bit for bit (the same MFMAs on the same tiles in the same order).
+ *   dmnerf_mlp_fwd_rays_f16_sel / dmnerf_mlp_fwd_rays_density_f16_sel: dmnerf_mlp_fwd_rays_f16 (render.py:71-83) /
+ *     dmnerf_mlp_fwd_rays_density_f16 on the samples d_sel [0, *d_count) only, with the contract of dmnerf_mlp_fwd_rays_sel: those
+ *     rows of d_raw [N*S, 4+C] / entries of d_sigma [N*S] are written, bit-identical to the dense call's, every other row is left
+ *     untouched; the batch size is read on the device, d_sel below *d_count only; *d_count == 0 is legal.  N * S < 2^31.
+ *   dmnerf_render_rays_fwd_fine / .._fine_skip with fused_heads = 3: d_blob_coarse is the f16 DENSITY blob of the coarse model,
+ *     d_blob_fine the f16 blob of the fine model (two formats: d_blob_coarse == d_blob_fine is refused); the chains are otherwise
+ *     unchanged.  fused_heads = 2 (bf16x3) is refused. */
+int64_t dmnerf_blob_f16_density_words(int ins_num);
+int dmnerf_blob_f16_density_from_f16(const float* d_blob_f16, int ins_num, float* d_blob_f16_density, void* stream);
+int dmnerf_mlp_fwd_rays_density_f16(const float* d_blob_f16_density, int ins_num, const float* d_rays_o, const float* d_rays_d,
+                                    const float* d_z, int64_t N, int S, float* d_sigma, void* stream);
+int dmnerf_mlp_fwd_rays_f16_sel(const float* d_blob_f16, int ins_num, const float* d_rays_o, const float* d_rays_d, const float* d_z,
+                                int64_t N, int S, const int* d_sel, const int* d_count, float* d_raw, void* stream);
+int dmnerf_mlp_fwd_rays_density_f16_sel(const float* d_blob_f16_density, int ins_num, const float* d_rays_o, const float* d_rays_d,
+                                        const float* d_z, int64_t N, int S, const int* d_sel, const int* d_count, float* d_sigma,
+                                        void* stream);
 
 /* The density of the field off the rays: what mesh_main (tools/mesh_generator.py:12-143) asks the fine network for (csrc/mlp_fwd_points.hip).
  * Both entries run dmnerf_mlp_fwd_rays_density's body -- encoding, trunk, density_linear; no direction, no heads -- so sigma is

@@ -1,6 +1,7 @@
 """Time the render that skips empty space (render.dm_nerf_fine_skip) against the dense fine-only render, by grid occupancy.
 
     python scripts/time_skip.py [--out profiles/skip/timing.jsonl]
+    python scripts/time_skip.py --mfma-split f16x2 [--out profiles/skip_f16/timing.jsonl]      (the opt-in split-f16 kernels)
 
 One 640 x 480 frame, 64 + 128 samples, chunks of 4096 rays, ins_num 13, the benchmark's models and camera.  The grids are synthetic:
 a 128^3 box round the scene whose cells are set at random with probability 5, 10, 25, 50 and 100 %, ``outside="empty"`` so that the
@@ -49,6 +50,7 @@ def main():
     ap.add_argument("--iters", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dims", type=int, default=128)
+    ap.add_argument("--mfma-split", default=None, choices=["f16x2"], help="render with args.mfma_split (default: the f32 kernels)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import types
@@ -62,8 +64,13 @@ def main():
     K = O.dmsr_intrinsics(H, W)
     c2w = O.pose_spherical(30.0, -65.0, 7.0).to(dev)
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
+    if a.mfma_split:
+        args.mfma_split = a.mfma_split
     lo, hi = (-8.0, -8.0, -8.0), (8.0, 8.0, 8.0)
     lines = [{"leg": "device", "name": torch.cuda.get_device_name(0), "clocks": clocks(), "iters": a.iters, "warmup": a.warmup}]
+
+    if a.mfma_split:
+        lines[0]["mfma_split"] = a.mfma_split
 
     def renderer(**kw):
         return D.FrameRenderer(H, W, K, c2w, (mc, mf), 4.0, 15.0, args, chunk=4096, n_samples=64, **kw)
