@@ -195,6 +195,8 @@ SIGNATURES = {
     "dmnerf_skip_grid_build": (c_int, [c_vp, c_int, c_int, c_int, c_float, c_int, c_vp, c_vp]),
     "dmnerf_skip_select_work_ints": (c_i64, [c_i64]),
     "dmnerf_skip_select": (c_int, [ctypes.POINTER(SkipGridArgs), c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_skip_select_fill": (c_int, [ctypes.POINTER(SkipGridArgs), c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                        c_int, c_vp, c_vp]),
     "dmnerf_mlp_fwd_rays_sel": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_mlp_fwd_rays_density_sel": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_blob_f16_density_words": (c_i64, [c_int]),

@@ -7,6 +7,11 @@
 //   dmnerf_skip_grid_build   bit(g) = any sigma in the (2 dilate + 1)^3 neighbourhood of g, clipped at the faces, is > threshold;
 //                            NaN counts as occupied (the test is !(sigma <= threshold)).
 //   dmnerf_skip_select       flag [N,S], the ascending list sel of the flagged samples, and its length, which stays on the device.
+//   dmnerf_skip_select_fill  the same, and in the same pass every row of rows [N*S, width] whose flag is 0 becomes a copy of
+//                            fill_row [width]; flagged rows are left for the sparse network.  The manipulation render passes
+//                            the EMPTY ROW (0, 0, 0, 0 | 0, .., 0, 1): sigma 0 is exactly neutral to the compositing, and the
+//                            argmax over its C logits is C - 1, the label of empty space, never the label of a moved object
+//                            ("The empty row").
 //
 // No atomics anywhere: a word of the grid is written by the one lane that holds its ballot, and the compaction is three passes
 // (per-block counts, one scan of the counts, scatter by prefix sums), so the list is in ascending order and the same every run.
@@ -117,6 +122,51 @@ __global__ __launch_bounds__(BLOCK) void skip_flag_kernel(GridDev G, const float
     if (threadIdx.x == 0) block_n[blockIdx.x] = total;
 }
 
+// ---- select-and-fill, pass 1: skip_flag_kernel that also writes fill_row into the rows of the samples it does not flag.  The block's
+// samples are rows [m0, m0 + 256) of `rows`, one contiguous run of 256 * width floats.  width = 4 + C is rarely a multiple of 4 and a
+// row is not 16-byte aligned, so the run is written one float per lane: lane t takes floats t, t + 256, ... of the run (a wave stores
+// 256 consecutive bytes), looks the float's row up in the block's flags (LDS) and stores fill_row[column] where the flag is 0.
+// (row, column) advance by (256 / width, 256 % width) per step: no division in the loop.  The flag arithmetic is skip_flag_kernel's,
+// statement for statement; that kernel is left as it is so that dmnerf_skip_select runs the machine code it always ran.
+__global__ __launch_bounds__(BLOCK) void skip_flag_fill_kernel(GridDev G, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                               const float* __restrict__ z, int64_t M, int S, uint8_t* __restrict__ flag,
+                                                               int* __restrict__ block_n, float* __restrict__ rows,
+                                                               const float* __restrict__ fill_row, int width) {
+    __shared__ uint8_t block_flag[BLOCK];
+    const int64_t m0 = (int64_t)blockIdx.x * BLOCK;
+    const int64_t m = m0 + threadIdx.x;
+    bool f = false;
+    if (m < M) {
+        const int64_t n = m / S;
+        const float zv = z[m];
+        bool inside = true;
+        int64_t g = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float p = __fadd_rn(rays_o[n * 3 + a], __fmul_rn(rays_d[n * 3 + a], zv));
+            const float c = floorf(__fmul_rn(__fsub_rn(p, G.lo[a]), G.inv_cell[a]));
+            inside = inside && (c >= 0.f) && (c < (float)G.dims[a]);
+            g = g * G.dims[a] + (inside ? (int)c : 0);
+        }
+        f = inside ? ((G.bits[g >> 5] >> (g & 31)) & 1u) != 0 : G.outside_flag != 0;
+        flag[m] = f ? 1 : 0;
+    }
+    block_flag[threadIdx.x] = f ? 1 : 0;
+    int rank;
+    const int total = block_count_and_rank(f, &rank);            // (its barrier also publishes block_flag)
+    if (threadIdx.x == 0) block_n[blockIdx.x] = total;
+    const int nrows = (int)(M - m0 < BLOCK ? M - m0 : BLOCK);
+    const int run = nrows * width;                                 // <= 256 * width floats
+    float* out = rows + m0 * width;
+    const int dr = BLOCK / width, dc = BLOCK - dr * width;
+    int r = threadIdx.x / width, c = threadIdx.x - r * width;
+    for (int i = threadIdx.x; i < run; i += BLOCK) {
+        if (!block_flag[r]) out[i] = fill_row[c];
+        r += dr; c += dc;
+        if (c >= width) { c -= width; ++r; }
+    }
+}
+
 // ---- pass 2: exclusive scan of the block counts in place (one workgroup walks them, 1024 at a time) and the grand total
 __global__ __launch_bounds__(1024) void skip_scan_kernel(int* __restrict__ block_n, int64_t nb, int* __restrict__ count) {
     __shared__ int buf[1024];
@@ -152,6 +202,12 @@ __global__ __launch_bounds__(BLOCK) void skip_scatter_kernel(const uint8_t* __re
 
 __global__ void skip_set_int_kernel(int* p, int v) { *p = v; }
 
+// (select-and-fill: the running sums += (selected, M); one thread, a plain read-modify-write ordered by the stream)
+__global__ void skip_add_totals_kernel(const int* __restrict__ count, int64_t M, int64_t* __restrict__ totals) {
+    totals[0] += *count;
+    totals[1] += M;
+}
+
 }  // namespace
 
 // (api.hip: the sample count of a level that is rendered dense)
@@ -179,31 +235,57 @@ extern "C" int64_t dmnerf_skip_select_work_ints(int64_t M) {
     return (M + BLOCK - 1) / BLOCK + 1;
 }
 
-extern "C" int dmnerf_skip_select(const dmnerf_skip_grid* grid, const float* d_rays_o, const float* d_rays_d, const float* d_z,
-                                  int64_t N, int S, uint8_t* d_flag, int* d_sel, int* d_count, int* d_work, void* stream) {
-    if (!grid) return dmn_fail(DMNERF_E_ARG, "skip_select: null grid");
-    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "skip_select: bad N=%lld S=%d", (long long)N, S);
+static int skip_select_impl(const char* who, const dmnerf_skip_grid* grid, const float* d_rays_o, const float* d_rays_d, const float* d_z,
+                            int64_t N, int S, uint8_t* d_flag, int* d_sel, int* d_count, int* d_work, float* d_rows,
+                            const float* d_fill_row, int width, int64_t* d_totals, hipStream_t st) {
+    if (!grid) return dmn_fail(DMNERF_E_ARG, "%s: null grid", who);
+    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "%s: bad N=%lld S=%d", who, (long long)N, S);
     const int64_t M = N * S;
-    if (M >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_select: %lld samples do not fit the int32 selection", (long long)M);
+    if (M >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: %lld samples do not fit the int32 selection", who, (long long)M);
     if (grid->outside != DMNERF_SKIP_OUTSIDE_EVALUATE && grid->outside != DMNERF_SKIP_OUTSIDE_EMPTY)
-        return dmn_fail(DMNERF_E_ARG, "skip_select: outside policy %d unknown", grid->outside);
+        return dmn_fail(DMNERF_E_ARG, "%s: outside policy %d unknown", who, grid->outside);
     GridDev G;
     int64_t cells = 1;
     for (int a = 0; a < 3; ++a) {
-        if (grid->dims[a] < 1) return dmn_fail(DMNERF_E_ARG, "skip_select: bad grid dims");
+        if (grid->dims[a] < 1) return dmn_fail(DMNERF_E_ARG, "%s: bad grid dims", who);
         G.lo[a] = grid->lo[a]; G.inv_cell[a] = grid->inv_cell[a]; G.dims[a] = grid->dims[a];
         cells *= grid->dims[a];
     }
-    if (cells >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_select: %lld cells do not fit int32", (long long)cells);
+    if (cells >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: %lld cells do not fit int32", who, (long long)cells);
     G.outside_flag = grid->outside == DMNERF_SKIP_OUTSIDE_EVALUATE ? 1 : 0;
     G.bits = grid->d_bits;
-    if (!d_count) return dmn_fail(DMNERF_E_ARG, "skip_select: null pointer");
-    hipStream_t st = (hipStream_t)stream;
+    if (!d_count) return dmn_fail(DMNERF_E_ARG, "%s: null pointer", who);
+    if (d_rows && (!d_fill_row || width < 1 || width > (1 << 16)))
+        return dmn_fail(DMNERF_E_ARG, "%s: rows without a fill row, or bad width %d", who, width);
     if (M == 0) return dmn_skip_set_int(d_count, 0, st);
-    if (!grid->d_bits || !d_rays_o || !d_rays_d || !d_z || !d_flag || !d_sel || !d_work) return dmn_fail(DMNERF_E_ARG, "skip_select: null pointer");
+    if (!grid->d_bits || !d_rays_o || !d_rays_d || !d_z || !d_flag || !d_sel || !d_work) return dmn_fail(DMNERF_E_ARG, "%s: null pointer", who);
     const int64_t nb = (M + BLOCK - 1) / BLOCK;
-    hipLaunchKernelGGL(skip_flag_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, G, d_rays_o, d_rays_d, d_z, M, S, d_flag, d_work);
+    if (d_rows)
+        hipLaunchKernelGGL(skip_flag_fill_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, G, d_rays_o, d_rays_d, d_z, M, S, d_flag, d_work,
+                           d_rows, d_fill_row, width);
+    else                                                           // (dmnerf_skip_select: the three kernels it always launched)
+        hipLaunchKernelGGL(skip_flag_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, G, d_rays_o, d_rays_d, d_z, M, S, d_flag, d_work);
     hipLaunchKernelGGL(skip_scan_kernel, dim3(1), dim3(1024), 0, st, d_work, nb, d_count);
     hipLaunchKernelGGL(skip_scatter_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, d_flag, d_work, M, d_sel);
-    return dmn_check_launch("skip_select");
+    if (d_totals) hipLaunchKernelGGL(skip_add_totals_kernel, dim3(1), dim3(1), 0, st, d_count, M, d_totals);
+    return dmn_check_launch(who);
+}
+
+extern "C" int dmnerf_skip_select(const dmnerf_skip_grid* grid, const float* d_rays_o, const float* d_rays_d, const float* d_z,
+                                  int64_t N, int S, uint8_t* d_flag, int* d_sel, int* d_count, int* d_work, void* stream) {
+    return skip_select_impl("skip_select", grid, d_rays_o, d_rays_d, d_z, N, S, d_flag, d_sel, d_count, d_work, nullptr, nullptr, 0, nullptr,
+                            (hipStream_t)stream);
+}
+
+// dmnerf_skip_select with one more duty in its first pass: row m of d_rows [N*S, width] becomes d_fill_row [width] where flag m is 0
+// (flagged rows are left untouched: the sparse network writes them afterwards).  The manipulation render's fill row is the empty
+// row E = (0, 0, 0, 0 | 0, .., 0, 1): neutral to manipulator_render and labelled C - 1 by the exchanger.  d_rows == NULL: exactly
+// dmnerf_skip_select.  d_totals (may be NULL): [2] int64 on the device, += (*d_count, N * S) by a one-thread kernel behind the select:
+// a plain read-modify-write, so all calls that share one d_totals must be on one stream; N * S == 0 adds nothing.  Nothing reaches
+// the host.
+extern "C" int dmnerf_skip_select_fill(const dmnerf_skip_grid* grid, const float* d_rays_o, const float* d_rays_d, const float* d_z,
+                                       int64_t N, int S, uint8_t* d_flag, int* d_sel, int* d_count, int* d_work, float* d_rows,
+                                       const float* d_fill_row, int width, int64_t* d_totals, void* stream) {
+    return skip_select_impl("skip_select_fill", grid, d_rays_o, d_rays_d, d_z, N, S, d_flag, d_sel, d_count, d_work, d_rows, d_fill_row,
+                            width, d_totals, (hipStream_t)stream);
 }

@@ -650,6 +650,12 @@ def _default_manipulate_chunk(ori_rays, tar_rays, models, args, us):
                           keep_labels=getattr(args, "keep_labels", None))
 
 
+def _skip_manipulate_chunk(ori_rays, tar_rays, models, args, us, grid=None, levels=("coarse", "fine"), counts=None):
+    from .networks import manipulator as Mn
+    return Mn.manipulator(None, None, models[0], models[1], ori_rays, tar_rays, args, us=us, kinds=getattr(args, "edit_kinds", None),
+                          keep_labels=getattr(args, "keep_labels", None), skip=grid, skip_levels=levels, skip_counts=counts)
+
+
 def _default_draws(n, n_imp, count, device):
     return [torch.rand([n, n_imp], device=device) for _ in range(count)]
 
@@ -706,10 +712,17 @@ class ManipulationFrameRenderer:
     ``manipulate_chunk(ori_rays [2,n,3], tar_rays [T,2,n,3], models, args, us)``, ``raygen`` / ``draws`` and
     ``target_rays(H, W, K, poses, kinds, offsets [T,H] float64, row0, nrows) -> [T,2,n,3]`` are injectable
     (CPU / gloo tests of the sharding logic); ``rank=`` / ``world=`` override the process group's view for the band arithmetic
-    (a single process can then render band r of N, without collectives)."""
+    (a single process can then render band r of N, without collectives).
+
+    ``skip=`` a ``field.SkipGrid`` (opt-in): the default chunk function hands it to ``manipulator(skip=, skip_levels=)``, which does
+    not evaluate samples in empty cells and writes the empty row there.  The draws do not depend on the grid, so the assembled frame
+    stays bit-identical whatever the world size.  ``self.n_eval``: int64 ``[2]`` on the device, the samples evaluated and the samples
+    in all over the steps this rank rendered (zeros without ``skip=``); it never reaches the host.  ``skip=`` cannot be combined with
+    an injected ``manipulate_chunk=``."""
 
     def __init__(self, H, W, K, ori_pose, trans_list, models, args, chunk=None, raygen=None, manipulate_chunk=None, draws=None,
-                 ins_num=None, rank=None, world=None, dtype=torch.float32, target_rays=None, keep_labels=None):
+                 ins_num=None, rank=None, world=None, dtype=torch.float32, target_rays=None, keep_labels=None, skip=None,
+                 skip_levels=("coarse", "fine")):
         r_, w_ = world_info()
         self.rank, self.world = (r_ if rank is None else int(rank)), (w_ if world is None else int(world))
         self._collective = rank is None and world is None
@@ -720,6 +733,13 @@ class ManipulationFrameRenderer:
         if not hasattr(self.args, "target_labels"):                 # manipulator.py:229
             self.args.target_labels = [self.args.target_label] if len(trans_list) else []
         self.n_imp = int(self.args.N_importance)
+        if skip is not None and manipulate_chunk is not None:
+            raise ValueError("ManipulationFrameRenderer: skip= routes the chunks through manipulator(skip=); it cannot be combined "
+                             "with manipulate_chunk=")
+        self._skip = None
+        if skip is not None:
+            from .networks import render
+            self._skip = (skip, render.check_skip_levels("ManipulationFrameRenderer", skip_levels))
         self.manipulate_chunk = manipulate_chunk or _default_manipulate_chunk
         self.draws = draws or _default_draws
         from .editing import Copy, Deform, edit_kind
@@ -775,6 +795,10 @@ class ManipulationFrameRenderer:
             raise ValueError("ManipulationFrameRenderer: pass ins_num= (no model with .ins_num given)")
         self.C = int(ins_num) + 1
         self.band = torch.empty(max(max(self.sizes), 1), 2 * (3 + self.C), dtype=dtype, device=self.dev)
+        self.n_eval = torch.zeros(2, dtype=torch.int64, device=self.dev)
+        if self._skip is not None:
+            import functools
+            self.manipulate_chunk = functools.partial(_skip_manipulate_chunk, grid=self._skip[0], levels=self._skip[1], counts=self.n_eval)
 
     def owned(self, c):
         """Rows of the band that chunk ``c`` of the frame covers: (first, last + 1) in band coordinates; empty if first >= last."""

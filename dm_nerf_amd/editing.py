@@ -186,7 +186,7 @@ MAP_NAMES = ("rgb", "ins", "tar_rgb", "tar_ins")
 
 
 def manipulate_demo_path(view_poses, hwk, models, args, objs, objs_trans, ins_rgbs, color_dict, ins_map, keep_maps=False,
-                         products=None, keep_labels=None, **frame_kw):
+                         products=None, keep_labels=None, skip=None, skip_levels=("coarse", "fine"), **frame_kw):
     """The pose loop of ``manipulator_demo`` (networks/manipulator.py:384-488) without its file output: per view ``i`` every
     object of ``objs`` is edited at once -- ``obj['mani_mode'] == 'deform'``: ``Deform(obj['deform_func'], i)``, otherwise the
     rigid ``objs_trans[obj['obj_name']][i]['transformation']`` -- with ``target_labels = [obj['tar_id'] ...]`` (:395, :437), one
@@ -199,10 +199,13 @@ def manipulate_demo_path(view_poses, hwk, models, args, objs, objs_trans, ins_rg
     (injectable, for tests of the loop on the CPU): a stand-in for ``frame_products``.
 
     Extension: a ``'transformation'`` of ``objs_trans`` may be a ``Remove()`` or a ``Copy(matrix)``, and ``keep_labels`` shows
-    only the objects of that set (isolate); ``objs`` may then be empty."""
+    only the objects of that set (isolate); ``objs`` may then be empty.  ``skip=`` a ``field.SkipGrid`` / ``skip_levels=``: every
+    frame skips empty space (``ManipulationFrameRenderer(skip=)``); moves, ``Deform``, ``Remove``, ``Copy`` and ``keep_labels`` work with it."""
     H, W, K = hwk
     if keep_labels is not None:
         frame_kw = dict(frame_kw, keep_labels=keep_labels)
+    if skip is not None:
+        frame_kw = dict(frame_kw, skip=skip, skip_levels=skip_levels)
     products = products or frame_products
     a = copy.copy(args)
     a.target_labels = [obj["tar_id"] for obj in objs]
@@ -236,7 +239,7 @@ def _gt_colors(table, labels):
 
 
 def manipulate_eval_path(ori_poses, hwk, models, args, trans, gt_rgbs=None, gt_labels=None, ins_rgbs=None, color_dict=None,
-                         image_metrics=True, keep_maps=False, lpips=None, **frame_kw):
+                         image_metrics=True, keep_maps=False, lpips=None, skip=None, skip_levels=("coarse", "fine"), **frame_kw):
     """The pose loop of ``manipulator_eval`` (networks/manipulator.py:233-339) for one transformation ``trans`` (4 x 4, or a
     ``Deform``), without its file output: per pose one ``ManipulationFrameRenderer`` frame with ``target_labels =
     [args.target_label]`` (:231), then on the device
@@ -252,14 +255,16 @@ def manipulate_eval_path(ori_poses, hwk, models, args, trans, gt_rgbs=None, gt_l
       (``render_gt_label2img``, :327).  A gt label that ``color_dict`` does not hold is black (the reference raises ``KeyError``).
 
     ``keep_maps=True`` adds the float frames ``rgb, ins, tar_rgb, tar_ins``.  ``distributed.results_table`` takes the result as it
-    is (LPIPS from ``out["lpips"]``, ``nan`` without a model).  The frames are complete on every rank: every rank computes the same numbers."""
+    is (LPIPS from ``out["lpips"]``, ``nan`` without a model).  The frames are complete on every rank: every rank computes the same numbers.
+    ``skip=`` a ``field.SkipGrid`` / ``skip_levels=``: every frame skips empty space (``ManipulationFrameRenderer(skip=)``)."""
     H, W, K = hwk
+    render_kw = frame_kw if skip is None else dict(frame_kw, skip=skip, skip_levels=skip_levels)
     cols = {}
     table = None
     scored = image_metrics and gt_rgbs is not None
     perceptual = lpips is not None and gt_rgbs is not None
     for i, pose in enumerate(ori_poses):
-        rgb, ins, tar_rgb, tar_ins = _render(H, W, K, pose, [trans], models, args, frame_kw)
+        rgb, ins, tar_rgb, tar_ins = _render(H, W, K, pose, [trans], models, args, render_kw)
         cols.setdefault("rgb8", []).append(frame_products(rgb)[0])
         cols.setdefault("tar_rgb8", []).append(frame_products(tar_rgb)[0])
         if keep_maps or scored or perceptual:

@@ -10,7 +10,7 @@ import torch
 
 from .. import _lib
 from . import helpers
-from .render import run_network
+from .render import run_network, run_network_skip
 
 
 def exchanger(ori_raw, tar_raws, ori_raw_pred, tar_raw_preds, move_labels):
@@ -100,15 +100,39 @@ def manipulator_z(N_rays, near, far, N_samples, device=None):
     return z
 
 
-def manipulator_nerf(rays, position_embedder, view_embedder, model, N_samples=None, near=None, far=None, z_vals=None, split=None):
+def manipulator_nerf(rays, position_embedder, view_embedder, model, N_samples=None, near=None, far=None, z_vals=None, split=None,
+                     skip=None, counts=None):
     """``manipulator_nerf`` (networks/manipulator.py:108-134) -> (raw [N,S,4+C], z_vals).  ``split`` (extension): the opt-in
-    split-operand network kernels, ``weights.split_mode(args)``."""
+    split-operand network kernels, ``weights.split_mode(args)``.  ``skip`` (extension): a ``field.SkipGrid``; the network is then
+    evaluated at the samples in set cells only and every other row of ``raw`` is the empty row (``render.run_network_skip``, which
+    also explains ``counts``)."""
     rays_o, rays_d = rays
     if z_vals is None:
         z_vals = manipulator_z(rays_d.shape[0], near, far, N_samples, rays_d.device)
     with torch.no_grad():
-        raw = run_network(model, rays_o, rays_d, z_vals, split=split)
+        if skip is not None:
+            raw = run_network_skip(model, rays_o, rays_d, z_vals, skip, split=split, counts=counts)
+        else:
+            raw = run_network(model, rays_o, rays_d, z_vals, split=split)
     return raw, z_vals
+
+
+def _skip_plan(model_coarse, model_fine, split, skip, skip_levels):
+    """-> the ``manipulator_nerf`` keywords of the coarse and of the fine model's calls.  Everything ``skip=`` cannot serve is refused
+    here, before the first launch."""
+    if skip is None:
+        return {}, {}
+    from .. import field
+    from . import render
+    if not isinstance(skip, field.SkipGrid):
+        raise TypeError("manipulator: skip must be a field.SkipGrid")
+    levels = render.check_skip_levels("manipulator", skip_levels)
+    if split not in (None, "f16x2"):
+        raise ValueError(f"manipulator: skip= has no sparse network kernel for args.mfma_split = {split!r} (f32 and 'f16x2' only)")
+    for name, model in (("coarse", model_coarse), ("fine", model_fine)):
+        if name in levels and not model._fused_ok():
+            raise ValueError(f"manipulator: skip= needs the 8 x 256 network at the {name} level (the sparse kernels exist for it only)")
+    return tuple({"skip": skip} if name in levels else {} for name in ("coarse", "fine"))
 
 
 def sort_rows(x):
@@ -120,11 +144,14 @@ def sort_rows(x):
     return out
 
 
-def _manipulator_edit(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, kinds, keep_labels):
+def _manipulator_edit(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, kinds, keep_labels, skip=None,
+                      skip_levels=("coarse", "fine"), skip_counts=None):
     """``manipulator`` with edit kinds: the chain below with ``edit_exchanger`` in place of ``exchanger``, the target side run for
     the ``T_r`` entries that have rays (MOVE and COPY) only, and the original's fine network on the merged depths evaluated once."""
     from .. import weights
     split = weights.split_mode(args)
+    kc, kf = _skip_plan(model_coarse, model_fine, split or None, skip, skip_levels)
+    kc, kf = dict(kc, split=split, counts=skip_counts), dict(kf, split=split, counts=skip_counts)
     N_samples, N_importance, near, far = args.N_samples, args.N_importance, args.near, args.far
     labels = [int(v) for v in args.target_labels]
     kinds = [MOVE] * len(labels) if kinds is None else [int(k) for k in kinds]
@@ -141,19 +168,19 @@ def _manipulator_edit(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, 
     Nr = ori_rays.shape[1]
     us = list(us) if us is not None else None
     draw = lambda: _lib.f32(us.pop(0)) if us is not None else torch.rand([Nr, N_importance], device=dev)
-    ori_raw, ori_z = manipulator_nerf(ori_rays, None, None, model_coarse, N_samples, near, far, split=split)
+    ori_raw, ori_z = manipulator_nerf(ori_rays, None, None, model_coarse, N_samples, near, far, **kc)
     _, ori_w, _, _ = manipulator_render(ori_raw, ori_z, ori_rays[1])
     ori_z_full = helpers.importance_resample(ori_z, ori_w, N_importance, u=draw())
-    ori_raw_full, _ = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z_full, split=split)
+    ori_raw_full, _ = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z_full, **kf)
     _, _, _, ori_ins_accum = manipulator_render(ori_raw_full, ori_z_full, ori_rays[1])
     tar_raws, f_tar_z, f_tar_zs, tar_ins_accums = [], [], [], []
     tar_rgb = tar_ins_accum = None
     for tar_rays in f_tar_rays:
-        tar_raw, tar_z = manipulator_nerf(tar_rays, None, None, model_coarse, N_samples, near, far, split=split)
+        tar_raw, tar_z = manipulator_nerf(tar_rays, None, None, model_coarse, N_samples, near, far, **kc)
         tar_raws.append(tar_raw); f_tar_z.append(tar_z)
         tar_rgb, tar_w, _, _ = manipulator_render(tar_raw, tar_z, tar_rays[1])
         tar_z_full, tar_zs = helpers.importance_resample(tar_z, tar_w, N_importance, u=draw(), return_samples=True)
-        tar_raw_full, _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z_full, split=split)
+        tar_raw_full, _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z_full, **kf)
         _, _, _, tar_ins_accum = manipulator_render(tar_raw_full, tar_z_full, tar_rays[1])
         f_tar_zs.append(tar_zs); tar_ins_accums.append(tar_ins_accum)
 
@@ -165,10 +192,10 @@ def _manipulator_edit(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, 
     _, ori_w, _, _ = manipulator_render(ori_raw, ori_z, ori_rays[1])
     _, ori_zs = helpers.importance_resample(ori_z, ori_w, N_importance, u=draw(), return_samples=True)
     ori_z = sort_rows(torch.cat([ori_z, ori_zs] + f_tar_zs, dim=-1))
-    ori_raw, _ = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z, split=split)
+    ori_raw, _ = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z, **kf)
     for idx, tar_rays in enumerate(f_tar_rays):
         tar_z = sort_rows(torch.cat([f_tar_z[idx], ori_zs] + f_tar_zs, dim=-1))
-        tar_raws[idx], _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z, split=split)
+        tar_raws[idx], _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z, **kf)
     ori_raw, _ = edit_exchanger(ori_raw, per_edit(tar_raws), ori_ins_accum, accs, labels, kinds, keep_labels, want_label=False)
     final_rgb, _, _, final_ins = manipulator_render(ori_raw, ori_z, ori_rays[1])
     if not f_tar_rays:
@@ -177,7 +204,7 @@ def _manipulator_edit(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, 
 
 
 def manipulator(position_embedder, view_embedder, model_coarse, model_fine, ori_rays, f_tar_rays, args, us=None, kinds=None,
-                keep_labels=None):
+                keep_labels=None, skip=None, skip_levels=("coarse", "fine"), skip_counts=None):
     """``manipulator`` (networks/manipulator.py:137-205) -> (final_rgb, final_ins, tar_rgb, tar_ins_accum).
 
     ``kinds`` / ``keep_labels`` (extension; both ``None``: the reference's chain below, unchanged): ``kinds[e]`` in ``MOVE``,
@@ -189,31 +216,45 @@ def manipulator(position_embedder, view_embedder, model_coarse, model_fine, ori_
     RNG: the reference calls ``sample_pdf(..., det=False)`` even at evaluation (:148,:170,:187): ``2 + T`` draws
     of ``torch.rand([N, N_importance])`` in the order original, each target, original again; the same draws are
     made here on the rays' device, or pass them as ``us`` (extension used by the tests).  ``args.mfma_split`` (extension, default
-    off) evaluates the 3 + 4 T network launches on the opt-in split-operand kernels, as in ``dm_nerf``.
+    off) evaluates the 2 + 4 T network launches on the opt-in split-operand kernels, as in ``dm_nerf``.
+
+    ``skip`` (extension, default off: the chain is then untouched): a ``field.SkipGrid`` in the world frame of the trained scene.
+    Target rays are the original rays carried back into that frame, so one grid serves both ray sets.  Every network call on
+    ``model_coarse`` / ``model_fine`` named in ``skip_levels`` ("coarse", "fine") evaluates only the samples whose cell is set (or
+    that lie outside the box with ``grid.outside == "evaluate"``); every other row of its output is the EMPTY ROW
+    ``(0, 0, 0, 0 | 0, .., 0, 1)``: sigma 0, so its compositing weight is exactly 0, and per-sample label ``C - 1`` -- never a move
+    label -- so the exchanger does not take a skipped sample for the moved object, as it would an all-zero row (label 0).  The result
+    is the dense chain with exactly those rows of every network output replaced, bit for bit; with ``SkipGrid.full`` it is the dense
+    result.  Draws, their order, shapes, ``kinds`` and ``keep_labels`` are unchanged.  ``args.mfma_split = "bf16x3"`` and a network
+    shape other than 8 x 256 at a named level raise ``ValueError`` (no dense detour).  ``skip_counts``: optional int64 ``[2]`` device
+    tensor, += (samples evaluated, samples) over the calls that went through the grid.
     """
     if kinds is not None or keep_labels is not None:
-        return _manipulator_edit(model_coarse, model_fine, ori_rays, list(f_tar_rays), args, us, kinds, keep_labels)
+        return _manipulator_edit(model_coarse, model_fine, ori_rays, list(f_tar_rays), args, us, kinds, keep_labels, skip=skip,
+                                 skip_levels=skip_levels, skip_counts=skip_counts)
     from .. import weights
     split = weights.split_mode(args)
+    kc, kf = _skip_plan(model_coarse, model_fine, split or None, skip, skip_levels)
+    kc, kf = dict(kc, split=split, counts=skip_counts), dict(kf, split=split, counts=skip_counts)
     N_samples, N_importance, near, far = args.N_samples, args.N_importance, args.near, args.far
     dev = ori_rays.device
     Nr = ori_rays.shape[1]
     us = list(us) if us is not None else None
     draw = lambda: _lib.f32(us.pop(0)) if us is not None else torch.rand([Nr, N_importance], device=dev)
     pe, ve = position_embedder, view_embedder
-    ori_raw, ori_z = manipulator_nerf(ori_rays, pe, ve, model_coarse, N_samples, near, far, split=split)
+    ori_raw, ori_z = manipulator_nerf(ori_rays, pe, ve, model_coarse, N_samples, near, far, **kc)
     _, ori_w, _, _ = manipulator_render(ori_raw, ori_z, ori_rays[1])
     ori_z_full = helpers.importance_resample(ori_z, ori_w, N_importance, u=draw())
-    ori_raw_full, _ = manipulator_nerf(ori_rays, pe, ve, model_fine, z_vals=ori_z_full, split=split)
+    ori_raw_full, _ = manipulator_nerf(ori_rays, pe, ve, model_fine, z_vals=ori_z_full, **kf)
     _, _, _, ori_ins_accum = manipulator_render(ori_raw_full, ori_z_full, ori_rays[1])
     tar_raws, f_tar_z, f_tar_zs, tar_ins_accums = [], [], [], []
     tar_rgb = tar_ins_accum = None
     for tar_rays in f_tar_rays:
-        tar_raw, tar_z = manipulator_nerf(tar_rays, pe, ve, model_coarse, N_samples, near, far, split=split)
+        tar_raw, tar_z = manipulator_nerf(tar_rays, pe, ve, model_coarse, N_samples, near, far, **kc)
         tar_raws.append(tar_raw); f_tar_z.append(tar_z)
         tar_rgb, tar_w, _, _ = manipulator_render(tar_raw, tar_z, tar_rays[1])
         tar_z_full, tar_zs = helpers.importance_resample(tar_z, tar_w, N_importance, u=draw(), return_samples=True)
-        tar_raw_full, _ = manipulator_nerf(tar_rays, pe, ve, model_fine, z_vals=tar_z_full, split=split)
+        tar_raw_full, _ = manipulator_nerf(tar_rays, pe, ve, model_fine, z_vals=tar_z_full, **kf)
         _, _, _, tar_ins_accum = manipulator_render(tar_raw_full, tar_z_full, tar_rays[1])
         f_tar_zs.append(tar_zs); tar_ins_accums.append(tar_ins_accum)
     ori_raw, _, _, _ = exchanger(ori_raw, tar_raws, ori_ins_accum, tar_ins_accums, args.target_labels)
@@ -223,9 +264,9 @@ def manipulator(position_embedder, view_embedder, model_coarse, model_fine, ori_
     f_tar_zs = torch.cat(f_tar_zs, dim=-1)
     ori_z = sort_rows(torch.cat([ori_z, ori_zs, f_tar_zs], dim=-1))
     for idx, tar_rays in enumerate(f_tar_rays):
-        ori_raw, ori_z = manipulator_nerf(ori_rays, pe, ve, model_fine, z_vals=ori_z, split=split)
+        ori_raw, ori_z = manipulator_nerf(ori_rays, pe, ve, model_fine, z_vals=ori_z, **kf)
         tar_z = sort_rows(torch.cat([f_tar_z[idx], ori_zs, f_tar_zs], dim=-1))
-        tar_raws[idx], _ = manipulator_nerf(tar_rays, pe, ve, model_fine, z_vals=tar_z, split=split)
+        tar_raws[idx], _ = manipulator_nerf(tar_rays, pe, ve, model_fine, z_vals=tar_z, **kf)
     ori_raw, _, _, _ = exchanger(ori_raw, tar_raws, ori_ins_accum, tar_ins_accums, args.target_labels)
     final_rgb, _, _, final_ins = manipulator_render(ori_raw, ori_z, ori_rays[1])
     return final_rgb, final_ins, tar_rgb, tar_ins_accum

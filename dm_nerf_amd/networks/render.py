@@ -47,6 +47,85 @@ def run_network(model, rays_o, rays_d, z_vals, split=None):
     return raw
 
 
+_empty_rows = {}
+
+
+def empty_row(C, device):
+    """The EMPTY ROW ``E = (0, 0, 0, 0 | 0, .., 0, 1)`` of width ``4 + C`` on ``device``: sigma, rgb and the object logits 0, the last
+    ("empty") logit 1.  Its weight in ``manipulator_render`` is exactly 0 and the argmax over its C logits is ``C - 1``.
+    Built on the device (no host copy) and kept per width and device; as with the weight blobs, make one call outside a graph capture
+    first, so that the kept tensor does not come from the capture's memory pool."""
+    key = (int(C), str(device))
+    if key not in _empty_rows:
+        row = torch.zeros(4 + int(C), dtype=torch.float32, device=device)
+        row[-1:].fill_(1.0)
+        _empty_rows[key] = row
+    return _empty_rows[key]
+
+
+def check_skip_levels(who, levels):
+    """``levels`` as a tuple of ``SKIP_LEVELS`` names, validated as ``dm_nerf_fine_skip`` validates it."""
+    levels = (levels,) if isinstance(levels, str) else tuple(levels)
+    if not levels or any(l not in SKIP_LEVELS for l in levels):
+        raise ValueError(f"{who}: levels must name 'coarse' and / or 'fine', got {levels}")
+    return levels
+
+
+def run_network_skip(model, rays_o, rays_d, z_vals, grid, split=None, counts=None):
+    """``run_network`` that does not evaluate empty space: ``raw [N,S,4+C]`` whose rows are the dense call's, bit for bit, where the
+    sample's cell of ``grid`` (a ``field.SkipGrid``) is set -- or the sample lies outside its box and ``grid.outside == "evaluate"`` --
+    and the empty row ``E = (0, 0, 0, 0 | 0, .., 0, 1)`` everywhere else (``empty_row``).  One ``dmnerf_skip_select_fill`` (flags, the
+    ascending selection, its device-side length, and E into the clear rows: there is no separate fill of the buffer), then
+    ``dmnerf_mlp_fwd_rays_sel`` (``split`` None) or ``dmnerf_mlp_fwd_rays_f16_sel`` (``"f16x2"``) over the selection.
+
+    There is no dense detour: ``split == "bf16x3"`` (no sparse kernel) and a network shape other than the 8 x 256 one raise
+    ``ValueError``, a grid on another device raises ``RuntimeError``, ``N S >= 2^31`` raises ``ValueError``.  ``counts``: optional
+    int64 ``[2]`` device tensor; the number of samples evaluated and the number of samples are ADDED to it on the device (nothing
+    reaches the host, so the call can be captured after one warm-up call: ``empty_row``).  Calls that share one ``counts`` must be on
+    one stream (the sums are a plain read-modify-write on the device)."""
+    from .. import field
+    if not isinstance(grid, field.SkipGrid):
+        raise TypeError("run_network_skip: grid must be a field.SkipGrid")
+    split = split or None
+    if split not in (None, "f16x2"):
+        raise ValueError(f"run_network_skip: no sparse network kernel for args.mfma_split = {split!r} (f32 and 'f16x2' only)")
+    if not model._fused_ok():
+        raise ValueError("run_network_skip: the sparse network kernels exist for the 8 x 256 network only")
+    N, S = z_vals.shape
+    if N * S >= 2 ** 31:
+        raise ValueError(f"run_network_skip: {N * S} samples do not fit the int32 selection; render in smaller chunks")
+    rays_o, rays_d, z = _lib.f32(rays_o.reshape(-1, 3)), _lib.f32(rays_d.reshape(-1, 3)), _lib.f32(z_vals)
+    _lib.require_gpu(rays_o, rays_d, z)
+    dev = z.device
+    if grid.bits.device != dev:
+        raise RuntimeError("run_network_skip: the grid lives on another device than the rays")
+    if counts is not None:
+        _lib.require_gpu(counts)
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (2,) or counts.device != dev or not counts.is_contiguous():
+            raise ValueError("run_network_skip: counts must be a contiguous int64 [2] tensor on the rays' device")
+    C = model.ins_num + 1
+    raw = torch.empty(N, S, 4 + C, dtype=torch.float32, device=dev)
+    if N * S == 0:
+        return raw
+    lib = _lib.load()
+    sel = torch.empty(N * S, dtype=torch.int32, device=dev)
+    flag = torch.empty(N * S, dtype=torch.uint8, device=dev)
+    work = torch.empty(int(lib.dmnerf_skip_select_work_ints(N * S)), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    g = grid.c_struct()
+    st = _lib.stream()
+    _lib.check(lib.dmnerf_skip_select_fill(ctypes.byref(g), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z), N, S, _lib.ptr(flag),
+                                           _lib.ptr(sel), _lib.ptr(count), _lib.ptr(work), _lib.ptr(raw), _lib.ptr(empty_row(C, dev)),
+                                           4 + C, _lib.ptr(counts), st), "dmnerf_skip_select_fill")
+    if split == "f16x2":
+        _lib.check(lib.dmnerf_mlp_fwd_rays_f16_sel(_lib.ptr(model.blob_f16()), model.ins_num, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z),
+                                                   N, S, _lib.ptr(sel), _lib.ptr(count), _lib.ptr(raw), st), "dmnerf_mlp_fwd_rays_f16_sel")
+    else:
+        _lib.check(lib.dmnerf_mlp_fwd_rays_sel(_lib.ptr(model.blob()), model.ins_num, 0, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z),
+                                               N, S, _lib.ptr(sel), _lib.ptr(count), _lib.ptr(raw), st), "dmnerf_mlp_fwd_rays_sel")
+    return raw
+
+
 def check_draws(t_rand, u, N, S, n_imp, perturb, dev):
     """The two random tensors of one ``dm_nerf`` call, validated before raw pointers reach the kernels.
     ``perturb > 0``: ``t_rand [N,S]`` (render.py:46) then ``u [N,n_imp]`` (helpers.py:135), drawn here in the reference's
@@ -319,9 +398,7 @@ def dm_nerf_fine_skip(rays, position_embedder, view_embedder, model_coarse, mode
     from .. import field
     if not isinstance(grid, field.SkipGrid):
         raise TypeError("dm_nerf_fine_skip: grid must be a field.SkipGrid")
-    levels = (levels,) if isinstance(levels, str) else tuple(levels)
-    if not levels or any(l not in SKIP_LEVELS for l in levels):
-        raise ValueError(f"dm_nerf_fine_skip: levels must name 'coarse' and / or 'fine', got {levels}")
+    levels = check_skip_levels("dm_nerf_fine_skip", levels)
     out, a, _keep = _fine_prepare("dm_nerf_fine_skip", rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse,
                                   args, t_rand, u, _events, modes=("f32", "f16x2"))
     dev = out['raw_fine'].device

@@ -646,6 +646,17 @@ int dmnerf_render_rays_fwd_fine(const dmnerf_render_fine_args* args, void* strea
  *     for all three axes (a NaN point is outside).  d_flag [N,S] = the cell's bit, or the outside policy; d_sel = the flagged m in
  *     ascending order (prefix sums: the same list every run); d_count [1] = their number, on the device.  d_work: scratch of
  *     dmnerf_skip_select_work_ints(N * S) int32.  N * S < 2^31.
+ *   dmnerf_skip_select_fill: dmnerf_skip_select (same cell arithmetic, flags, ascending d_sel, device-side d_count, same argument
+ *     checks) that in the same pass over the samples writes d_fill_row [width] into row m of d_rows [N*S, width] for every sample
+ *     whose flag is 0; flagged rows are left untouched (the sparse network writes them afterwards), so no separate fill of the
+ *     buffer is needed.  Rows need no alignment (width = 4 + C is rarely a multiple of 4): the stores are one float per lane over
+ *     the block's contiguous run of rows.  No atomics.  d_rows == NULL: exactly dmnerf_skip_select (which launches the kernels it
+ *     always launched).  d_totals (may be NULL): [2] int64 running sums on the device, += (*d_count, N * S), by a one-thread kernel
+ *     behind the select: a plain read-modify-write, so every call that shares one d_totals must be on the same stream; with
+ *     N * S == 0 nothing is added.
+ *     The manipulation render (networks/manipulator.py) fills with the EMPTY ROW E = (0, 0, 0, 0 | 0, .., 0, 1): sigma 0 makes the
+ *     sample's weight exactly 0 in manipulator_render, and the argmax over its C logits is C - 1 -- the label the field gives empty
+ *     space, which is never a move label -- where an all-zero row would read as object 0 to the exchanger.
  *   dmnerf_mlp_fwd_rays_sel / dmnerf_mlp_fwd_rays_density_sel: dmnerf_mlp_fwd_rays (fused_heads = 1: dmnerf_mlp_fwd_rays_fused) /
  *     dmnerf_mlp_fwd_rays_density on the samples d_sel [0, *d_count) only: those rows of d_raw [N*S, 4+C] / entries of d_sigma [N*S]
  *     are written, bit-identical to the dense call's; every other row is left untouched (the caller zero-fills).  The batch size is
@@ -670,6 +681,9 @@ int dmnerf_skip_grid_build(const float* d_sigma, int dx, int dy, int dz, float t
 int64_t dmnerf_skip_select_work_ints(int64_t M);
 int dmnerf_skip_select(const dmnerf_skip_grid* grid, const float* d_rays_o, const float* d_rays_d, const float* d_z, int64_t N, int S,
                        uint8_t* d_flag, int* d_sel, int* d_count, int* d_work, void* stream);
+int dmnerf_skip_select_fill(const dmnerf_skip_grid* grid, const float* d_rays_o, const float* d_rays_d, const float* d_z, int64_t N, int S,
+                            uint8_t* d_flag, int* d_sel, int* d_count, int* d_work, float* d_rows, const float* d_fill_row, int width,
+                            int64_t* d_totals, void* stream);
 int dmnerf_mlp_fwd_rays_sel(const float* d_blob, int ins_num, int fused_heads, const float* d_rays_o, const float* d_rays_d,
                             const float* d_z, int64_t N, int S, const int* d_sel, const int* d_count, float* d_raw, void* stream);
 int dmnerf_mlp_fwd_rays_density_sel(const float* d_blob, int ins_num, const float* d_rays_o, const float* d_rays_d, const float* d_z,
