@@ -824,6 +824,9 @@ int dmnerf_ray_embed(const float* d_rays_o, const float* d_rays_d, const float* 
  *     weight-gradient kernels wrote), first and second moments -- applying torch.optim.Adam's update (amsgrad off, no weight
  *     decay) operation for operation, each rounded to f32 on its own, scalar factors formed in double:
  *       m <- m + (1-b1)(g - m);  v <- v b2;  v <- v + (1-b2)(g g);  p <- p + (-(lr / (1 - b1^t))) (m / (sqrt(v) / sqrt(1 - b2^t) + eps))
+ *     The second-moment product is g * g FIRST, then scaled by (1-b2) (torch's multi-tensor form, _foreach_addcmul_): g * g is inf
+ *     in f32 for |g| beyond about 1.8e19, v becomes inf and stays inf, m / inf = 0 -- that element's parameter stops moving from
+ *     that step on, exactly as under torch.optim.Adam(foreach=True); single-tensor Adam forms (value * g) * g and stays finite.
  *     t = d_state2[0] + 1 is read on the device and stored back by the last workgroup to finish (d_state2[1] is its ticket
  *     counter; both start at 0): no host synchronisation, HIP-graph capturable.  d_lr (nullable): a device f32 scalar that
  *     overrides lr (a captured graph changes the learning rate by writing it).
