@@ -310,10 +310,7 @@ __global__ void conv3x3_pack_kernel(const float* __restrict__ w, int cout, int c
 template <int NBB>
 int launch_cv(const CvArgs& a, int tiles_n, hipStream_t stream) {
     constexpr int lds_bytes = CvRing<NBB>::D * CvRing<NBB>::BUF + CV_STAGE_BYTES;
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)conv3x3_kernel<NBB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); });
-        e != hipSuccess)
-        return dmn_fail_hip(e, "conv3x3: hipFuncSetAttribute");
+    if (int rc = dmn_allow_lds<conv3x3_kernel<NBB>, lds_bytes>("conv3x3")) return rc;
     int dev = 0, cus = 0;
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return dmn_fail_hip(e, "conv3x3: hipGetDevice");
     if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess || cus < 1)

@@ -347,12 +347,8 @@ static int cr_forward(const CrPair& pr, int levels, const int32_t* d_labels, int
     const CrLayout w = cr_layout(N, ins_num);
     if (work_bytes < w.total) return dmn_fail(DMNERF_E_ARG, "ins_criterion: work buffer too small (%lld < %lld bytes)", (long long)work_bytes, (long long)w.total);
     const size_t lds = (size_t)(2 * w.L * ins_num + w.L) * sizeof(float);
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)cr_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                2 * (CR_MAXC + 1) * CR_MAXC * 4 + (CR_MAXC + 1) * 4); });
-        e != hipSuccess)
-        return dmn_fail_hip(e, "ins_criterion: hipFuncSetAttribute");
     // (no memset: V, U and the flags word are written afresh by cr_solve_kernel; the chunks report through plain stores)
+    if (int rc = dmn_allow_lds<cr_partial_kernel, 2 * (CR_MAXC + 1) * CR_MAXC * 4 + (CR_MAXC + 1) * 4>("ins_criterion")) return rc;
     hipLaunchKernelGGL(cr_partial_kernel, dim3((unsigned)w.nch, (unsigned)levels), dim3(CR_MAXC), lds, (hipStream_t)stream, pr, (const int*)d_labels, N, ins_num);
     int rc = dmn_check_launch("ins_criterion: partial sums");
     if (rc) return rc;

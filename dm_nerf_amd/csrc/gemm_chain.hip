@@ -372,10 +372,7 @@ __global__ __launch_bounds__(256) void chain_kernel(const ChainArgs a) {
 template <int NBB, int D>
 int launch_chain(const ChainArgs& a, hipStream_t stream) {
     const int lds_bytes = CH_LDS_BUDGET;
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)chain_kernel<NBB, D>, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS_BUDGET); });
-        e != hipSuccess)
-        return dmn_fail_hip(e, "mlp_chain: hipFuncSetAttribute");
+    if (int rc = dmn_allow_lds<chain_kernel<NBB, D>, CH_LDS_BUDGET>("mlp_chain")) return rc;
     int dev = 0, cus = 0;
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return dmn_fail_hip(e, "mlp_chain: hipGetDevice");
     if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess || cus < 1)

@@ -500,10 +500,7 @@ __global__ void copy_cols_pad_kernel(const float* __restrict__ src, int64_t lds_
 template <int NBB>
 int launch_nt(const NtArgs& a, int tiles_n, hipStream_t stream) {
     constexpr int lds_bytes = NtRing<NBB>::D * NtRing<NBB>::BUF + NtRing<NBB>::STAGE;
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)gemm_nt_kernel<NBB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); });
-        e != hipSuccess)
-        return dmn_fail_hip(e, "gemm_nt: hipFuncSetAttribute");
+    if (int rc = dmn_allow_lds<gemm_nt_kernel<NBB>, lds_bytes>("gemm_nt")) return rc;
     // persistent grid: one workgroup per CU slot (nt_occupancy per CU), each walking the sample tiles with stride gridDim.x
     int dev = 0, cus = 0;
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return dmn_fail_hip(e, "gemm_nt: hipGetDevice");
@@ -609,12 +606,7 @@ extern "C" int dmnerf_ray_embed(const float* d_rays_o, const float* d_rays_d, co
     if (blocks > 0x7fffffffLL) return dmn_fail(DMNERF_E_ARG, "ray_embed: too many samples");
     const int lds_bytes = RE_ROWS * (ldp + 4 + ldv + 4) * 4;
     if (lds_bytes > 163840) return dmn_fail(DMNERF_E_ARG, "ray_embed: rows of %d + %d floats do not fit the staging tile", ldp, ldv);
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)ray_embed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 163840); });
-        e != hipSuccess)
-        return dmn_fail_hip(e, "ray_embed: hipFuncSetAttribute");
     const int vec = ldp % 4 == 0 && ldv % 4 == 0 && !((uintptr_t)d_x_pos & 15) && !((uintptr_t)d_x_dir & 15);
-    hipLaunchKernelGGL(ray_embed_kernel, dim3((unsigned)blocks), dim3(256), lds_bytes, (hipStream_t)stream, d_rays_o, d_rays_d, d_z, N, S, Lp, Lv,
-                       d_x_pos, ldp, d_x_dir, ldv, vec);
-    return dmn_check_launch("ray_embed");
+    return dmn_launch_lds<ray_embed_kernel, 163840>("ray_embed", (unsigned)blocks, 256, lds_bytes, (hipStream_t)stream,
+                                                    d_rays_o, d_rays_d, d_z, N, S, Lp, Lv, d_x_pos, ldp, d_x_dir, ldv, vec);
 }

@@ -294,12 +294,8 @@ int launch_tn_occ(const TnArgs& a, int blocks, hipStream_t stream) {
     constexpr int NL = SA * WA + SB * WB;
     constexpr int D = TN_LDS_BUDGET / OCC / (NL * 4096) < 4 ? TN_LDS_BUDGET / OCC / (NL * 4096) : 4;
     constexpr int lds_bytes = D * NL * 4096;
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)gemm_tn_kernel<SA, SB, WA, WB, OCC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); });
-        e != hipSuccess)
-        return dmn_fail_hip(e, "gemm_tn: hipFuncSetAttribute");
-    hipLaunchKernelGGL((gemm_tn_kernel<SA, SB, WA, WB, OCC>), dim3((unsigned)blocks), dim3(256), lds_bytes, stream, a);
-    return dmn_check_launch("gemm_tn");
+    return dmn_launch_lds<gemm_tn_kernel<SA, SB, WA, WB, OCC>, lds_bytes>("gemm_tn", (unsigned)blocks, 256, lds_bytes,
+                                                                           stream, a);
 }
 template <int SA, int SB, int WA, int WB>
 int launch_tn(const TnArgs& a, int blocks, int occ, hipStream_t stream) {

@@ -110,14 +110,14 @@ __global__ void head_unfuse_kernel(const float* __restrict__ flat, const Params 
 }  // namespace
 
 extern "C" int dmnerf_head_product(const float* d_flat, int ins_num, float* d_F, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "head_product: ins_num %d unsupported", ins_num);
+    if (int rc = dmn_check_ins_num("head_product", ins_num)) return rc;
     if (!d_flat || !d_F) return dmn_fail(DMNERF_E_ARG, "head_product: null pointer");
     hipLaunchKernelGGL(head_product_kernel, dim3((HW * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_flat, make_params(ins_num), d_F);
     return dmn_check_launch("head_product");
 }
 
 extern "C" int dmnerf_fuse_heads(const float* d_flat, int ins_num, float* d_flat_fused, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "fuse_heads: ins_num %d unsupported", ins_num);
+    if (int rc = dmn_check_ins_num("fuse_heads", ins_num)) return rc;
     if (!d_flat || !d_flat_fused || d_flat == d_flat_fused) return dmn_fail(DMNERF_E_ARG, "fuse_heads: null or aliased pointer");
     const Params P = make_params(ins_num);
     hipLaunchKernelGGL(head_fuse_params_kernel, dim3((unsigned)((P.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_flat, P, d_flat_fused);

@@ -435,16 +435,9 @@ extern "C" int dmnerf_ins_eval_prep(const float* d_pred_ins, int64_t pred_row_st
     const IeLayout w = ie_layout(N, ins_num);
     if (work_bytes < w.total)
         return dmn_fail(DMNERF_E_ARG, "ins_eval_prep: work buffer too small (%lld < %lld bytes)", (long long)work_bytes, (long long)w.total);
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] {
-            if (hipError_t e1 = hipFuncSetAttribute((const void*)ie_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    (IE_MAXC + 1) * (IE_MAXC + 1) * 4);
-                e1 != hipSuccess)
-                return e1;
-            return hipFuncSetAttribute((const void*)ie_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * IE_MAXC * IE_BINS * 4);
-        });
-        e != hipSuccess)
-        return dmn_fail_hip(e, "ins_eval_prep: hipFuncSetAttribute");
+    // (ie_hist_kernel too: dmnerf_ins_eval, which launches it, works on what this entry prepared and so follows it)
+    if (int rc = dmn_allow_lds<ie_prep_kernel, (IE_MAXC + 1) * (IE_MAXC + 1) * 4>("ins_eval_prep")) return rc;
+    if (int rc = dmn_allow_lds<ie_hist_kernel, 2 * IE_MAXC * IE_BINS * 4>("ins_eval_prep")) return rc;
     const int64_t nz = w.zero_bytes / 4;
     hipLaunchKernelGGL(ie_zero_kernel, dim3((unsigned)((nz + IE_THREADS - 1) / IE_THREADS < 512 ? (nz + IE_THREADS - 1) / IE_THREADS : 512)),
                        dim3(IE_THREADS), 0, (hipStream_t)stream, (int*)d_work, nz);

@@ -191,31 +191,22 @@ __global__ __launch_bounds__(256) void mlp_bwd_split_kernel(const BwdSArgs a) {
 
 extern "C" int dmnerf_mlp_bwd_data_split(const float* d_blob_t_split, int ins_num, const float* d_save, const float* d_graw, int64_t M,
                                          float* d_dsave, float* d_graw_t, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "mlp_bwd_data_split: ins_num %d unsupported", ins_num);
+    if (int rc = dmn_check_ins_num("mlp_bwd_data_split", ins_num)) return rc;
     if (M < 0 || M > DMNERF_MAX_TRAIN_SAMPLES) return dmn_fail(DMNERF_E_ARG, "mlp_bwd_data_split: M=%lld outside [0,%lld]", (long long)M, (long long)DMNERF_MAX_TRAIN_SAMPLES);
     if (M == 0) return DMNERF_OK;
     if (!d_blob_t_split || !d_save || !d_graw || !d_dsave) return dmn_fail(DMNERF_E_ARG, "mlp_bwd_data_split: null pointer");
     BwdSArgs a{};
     a.blob = d_blob_t_split; a.L = make_layout(ins_num); a.LT = make_layout_t(ins_num); a.S = make_split_layout_t(ins_num);
     a.save = d_save; a.graw = d_graw; a.dsave = d_dsave; a.graw_t = d_graw_t; a.M = M;
-    const int64_t nblk = (M + 31) / 32;
-    dim3 g((unsigned)((nblk + 3) / 4)), b(256);
-    constexpr size_t lds_bytes = (size_t)(SP_RING_FLOATS + TAB_T_FLOATS) * sizeof(float);
-#define DMN_LAUNCH(OBI_)                                                                                          \
-    {                                                                                                            \
-        static DmnOncePerDevice once;                                                                                 \
-        if (hipError_t e_ = once.run([] { return hipFuncSetAttribute((const void*)mlp_bwd_split_kernel<OBI_>,              \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }); e_ != hipSuccess) \
-            return dmn_fail_hip(e_, "mlp_bwd_data_split: hipFuncSetAttribute");                                       \
-        hipLaunchKernelGGL(mlp_bwd_split_kernel<OBI_>, g, b, lds_bytes, (hipStream_t)stream, a);                        \
-    }
+    unsigned grid;
+    if (int rc = dmn_mlp_grid("mlp_bwd_data_split", M, &grid)) return rc;
+    constexpr int LDS = (SP_RING_FLOATS + TAB_T_FLOATS) * sizeof(float);
+    const char* what = "mlp_bwd_data_split";
     switch (a.L.OBI) {
-        case 1: DMN_LAUNCH(1) break;
-        case 2: DMN_LAUNCH(2) break;
-        case 3: DMN_LAUNCH(3) break;
-        case 4: DMN_LAUNCH(4) break;
+        case 1: return dmn_launch_lds<mlp_bwd_split_kernel<1>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
+        case 2: return dmn_launch_lds<mlp_bwd_split_kernel<2>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
+        case 3: return dmn_launch_lds<mlp_bwd_split_kernel<3>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
+        case 4: return dmn_launch_lds<mlp_bwd_split_kernel<4>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
         default: return dmn_fail(DMNERF_E_ARG, "mlp_bwd_data_split: unsupported logit count C=%d", a.L.C);
     }
-#undef DMN_LAUNCH
-    return dmn_check_launch("mlp_bwd_data_split");
 }

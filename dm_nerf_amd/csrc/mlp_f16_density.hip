@@ -17,34 +17,23 @@ __global__ __launch_bounds__(256) void mlp_f16_density_kernel(const F16Args a) {
 #include "mlp_f16_body.inc"
 }
 
-int check_args(const char* who, int ins_num, int64_t N, int S, bool sel) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "%s: ins_num %d unsupported", who, ins_num);
-    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "%s: bad N=%lld S=%d", who, (long long)N, S);
-    if (sel && N * S >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: %lld samples do not fit the int32 selection", who, (long long)(N * S));
-    return DMNERF_OK;
-}
-
 void fill_args(F16Args& a, const float* d_blob, int ins_num, const float* d_rays_o, const float* d_rays_d, const float* d_z, int64_t N, int S,
                float* d_sigma) {
     a.blob = d_blob; a.S = make_f16_density_layout(ins_num);
     a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z; a.raw = d_sigma; a.M = N * S; a.Sr = S;
-#ifdef DMN_F16_TRACE
-    a.trace = nullptr;
-#endif
 }
 
-constexpr size_t LDS_BYTES = (size_t)F16_LDS_FLOATS * sizeof(float);
+constexpr int LDS_BYTES = F16_LDS_FLOATS * sizeof(float);
 
 }  // namespace
 
 extern "C" int64_t dmnerf_blob_f16_density_words(int ins_num) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return -1;
-    return make_f16_density_layout(ins_num).total;
+    return dmn_ins_num_ok(ins_num) ? make_f16_density_layout(ins_num).total : -1;
 }
 
 // table + trunk groups | density groups | zeroed landing groups, all on `stream`
 extern "C" int dmnerf_blob_f16_density_from_f16(const float* d_blob_f16, int ins_num, float* d_blob_density, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "blob_f16_density_from_f16: ins_num %d unsupported", ins_num);
+    if (int rc = dmn_check_ins_num("blob_f16_density_from_f16", ins_num)) return rc;
     if (!d_blob_f16 || !d_blob_density) return dmn_fail(DMNERF_E_ARG, "blob_f16_density_from_f16: null pointer");
     const F16Layout F = make_f16_layout(ins_num), D = make_f16_density_layout(ins_num);
     static_assert(F16_DENSITY_GROUP0 + F16_DENSITY_GROUPS <= 4 + 4 * 16 + 20 + 2 * 16 + 9 + 8 + 2 + 1, "density groups inside the forward stream");
@@ -61,36 +50,27 @@ extern "C" int dmnerf_blob_f16_density_from_f16(const float* d_blob_f16, int ins
 
 extern "C" int dmnerf_mlp_fwd_rays_density_f16(const float* d_blob_f16_density, int ins_num, const float* d_rays_o, const float* d_rays_d,
                                                const float* d_z, int64_t N, int S, float* d_sigma, void* stream) {
-    if (int rc = check_args("mlp_fwd_rays_density_f16", ins_num, N, S, false)) return rc;
+    if (int rc = dmn_check_rays("mlp_fwd_rays_density_f16", ins_num, N, S)) return rc;
     if (N == 0) return DMNERF_OK;
     if (!d_blob_f16_density || !d_rays_o || !d_rays_d || !d_z || !d_sigma) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density_f16: null pointer");
     F16Args a{};
     fill_args(a, d_blob_f16_density, ins_num, d_rays_o, d_rays_d, d_z, N, S, d_sigma);
-    const int64_t grid = ((a.M + 31) / 32 + 3) / 4;
-    if (grid > 0x7fffffffLL) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density_f16: too many samples");
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)mlp_f16_density_kernel<false>,
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES); }); e != hipSuccess)
-        return dmn_fail_hip(e, "mlp_fwd_rays_density_f16: hipFuncSetAttribute");
-    hipLaunchKernelGGL(mlp_f16_density_kernel<false>, dim3((unsigned)grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
-    return dmn_check_launch("mlp_fwd_rays_density_f16");
+    unsigned grid;
+    if (int rc = dmn_mlp_grid("mlp_fwd_rays_density_f16", a.M, &grid, true)) return rc;
+    return dmn_launch_lds<mlp_f16_density_kernel<false>, LDS_BYTES>("mlp_fwd_rays_density_f16", grid, 256, LDS_BYTES, (hipStream_t)stream, a);
 }
 
 extern "C" int dmnerf_mlp_fwd_rays_density_f16_sel(const float* d_blob_f16_density, int ins_num, const float* d_rays_o,
                                                    const float* d_rays_d, const float* d_z, int64_t N, int S, const int* d_sel,
                                                    const int* d_count, float* d_sigma, void* stream) {
-    if (int rc = check_args("mlp_fwd_rays_density_f16_sel", ins_num, N, S, true)) return rc;
+    if (int rc = dmn_check_rays("mlp_fwd_rays_density_f16_sel", ins_num, N, S, true)) return rc;
     if (N == 0) return DMNERF_OK;
     if (!d_blob_f16_density || !d_rays_o || !d_rays_d || !d_z || !d_sel || !d_count || !d_sigma)
         return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density_f16_sel: null pointer");
     F16Args a{};
     fill_args(a, d_blob_f16_density, ins_num, d_rays_o, d_rays_d, d_z, N, S, d_sigma);
     a.sel = d_sel; a.count = d_count;
-    const int64_t grid = ((a.M + 31) / 32 + 3) / 4;                        // the worst case count == N * S
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)mlp_f16_density_kernel<true>,
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES); }); e != hipSuccess)
-        return dmn_fail_hip(e, "mlp_fwd_rays_density_f16_sel: hipFuncSetAttribute");
-    hipLaunchKernelGGL(mlp_f16_density_kernel<true>, dim3((unsigned)grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
-    return dmn_check_launch("mlp_fwd_rays_density_f16_sel");
+    unsigned grid;                                                          // the worst case count == N * S
+    if (int rc = dmn_mlp_grid("mlp_fwd_rays_density_f16_sel", a.M, &grid)) return rc;
+    return dmn_launch_lds<mlp_f16_density_kernel<true>, LDS_BYTES>("mlp_fwd_rays_density_f16_sel", grid, 256, LDS_BYTES, (hipStream_t)stream, a);
 }

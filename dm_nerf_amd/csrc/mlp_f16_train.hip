@@ -14,8 +14,7 @@ extern "C" void dmnerf_f16_train_set_trace(long long* d_trace) { g_f16_train_tra
 
 extern "C" int dmnerf_mlp_fwd_rays_train_f16(const float* d_blob_f16, int ins_num, const float* d_rays_o, const float* d_rays_d,
                                              const float* d_z, int64_t N, int S, float* d_raw, float* d_save, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_train_f16: ins_num %d unsupported", ins_num);
-    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_train_f16: bad N=%lld S=%d", (long long)N, S);
+    if (int rc = dmn_check_rays("mlp_fwd_rays_train_f16", ins_num, N, S)) return rc;
     if (N == 0) return DMNERF_OK;
     if (!d_blob_f16 || !d_rays_o || !d_rays_d || !d_z || !d_raw || !d_save) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_train_f16: null pointer");
     F16Args a{};
@@ -26,23 +25,14 @@ extern "C" int dmnerf_mlp_fwd_rays_train_f16(const float* d_blob_f16, int ins_nu
 #endif
     if (a.M > DMNERF_MAX_TRAIN_SAMPLES)
         return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_train_f16: %lld samples per launch exceed %lld; split the batch", (long long)a.M, (long long)DMNERF_MAX_TRAIN_SAMPLES);
-    const int64_t nblk = (a.M + 31) / 32;
-    const int64_t grid = (nblk + 3) / 4;
-    constexpr size_t lds_bytes = (size_t)F16_LDS_FLOATS * sizeof(float);
-#define DMN_LAUNCH(OBX_)                                                                                                   \
-    {                                                                                                                     \
-        static DmnOncePerDevice once;                                                                                 \
-        if (hipError_t e_ = once.run([] { return hipFuncSetAttribute((const void*)mlp_f16_kernel<OBX_, true>,              \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }); e_ != hipSuccess) \
-            return dmn_fail_hip(e_, "mlp_fwd_rays_train_f16: hipFuncSetAttribute");                                       \
-        hipLaunchKernelGGL((mlp_f16_kernel<OBX_, true>), dim3((unsigned)grid), dim3(256), lds_bytes, (hipStream_t)stream, a);    \
-    }
+    unsigned grid;
+    if (int rc = dmn_mlp_grid("mlp_fwd_rays_train_f16", a.M, &grid)) return rc;
+    constexpr int LDS = F16_LDS_FLOATS * sizeof(float);
+    const char* what = "mlp_fwd_rays_train_f16";
     switch (a.S.OBX) {
-        case 1: DMN_LAUNCH(1) break;
-        case 2: DMN_LAUNCH(2) break;
-        case 4: DMN_LAUNCH(4) break;
+        case 1: return dmn_launch_lds<mlp_f16_kernel<1, true>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
+        case 2: return dmn_launch_lds<mlp_f16_kernel<2, true>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
+        case 4: return dmn_launch_lds<mlp_f16_kernel<4, true>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
         default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_train_f16: unsupported logit count C=%d", a.S.C);
     }
-#undef DMN_LAUNCH
-    return dmn_check_launch("mlp_fwd_rays_train_f16");
 }

@@ -10,8 +10,7 @@ extern "C" int dmnerf_debug_fwd_trace(long long* p) { g_dmn_fwd_trace = p; retur
 extern "C" int dmnerf_mlp_fwd_rays(const float* d_blob, int ins_num, const float* d_rays_o,
                                    const float* d_rays_d, const float* d_z, int64_t N, int S,
                                    float* d_raw, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays: ins_num %d unsupported", ins_num);
-    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays: bad N=%lld S=%d", (long long)N, S);
+    if (int rc = dmn_check_rays("mlp_fwd_rays", ins_num, N, S)) return rc;
     if (N == 0) return DMNERF_OK;
     if (!d_blob || !d_rays_o || !d_rays_d || !d_z || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays: null pointer");
     MlpArgs a{};

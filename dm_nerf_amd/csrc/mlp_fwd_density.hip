@@ -38,21 +38,15 @@ __global__ __launch_bounds__(256) void mlp_fwd_density_kernel(const DensityArgs 
 extern "C" int dmnerf_mlp_fwd_rays_density(const float* d_blob, int ins_num, const float* d_rays_o,
                                            const float* d_rays_d, const float* d_z, int64_t N, int S,
                                            float* d_sigma, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density: ins_num %d unsupported", ins_num);
-    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density: bad N=%lld S=%d", (long long)N, S);
+    if (int rc = dmn_check_rays("mlp_fwd_rays_density", ins_num, N, S)) return rc;
     if (N == 0) return DMNERF_OK;
     if (!d_blob || !d_rays_o || !d_rays_d || !d_z || !d_sigma) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density: null pointer");
     DensityArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
     a.sigma = d_sigma; a.M = N * S; a.S = S;
-    const int64_t nblk = (a.M + 31) / 32;
-    const int64_t grid = (nblk + 3) / 4;
-    if (grid > 0x7fffffffLL) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density: %lld samples is too many for one launch", (long long)a.M);
-    constexpr size_t lds_bytes = (size_t)LDS_FLOATS * sizeof(float);     // 147 456 B: one workgroup per CU, as the full kernel
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)mlp_fwd_density_kernel,
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }); e != hipSuccess)
-        return dmn_fail_hip(e, "mlp_fwd_rays_density: hipFuncSetAttribute");
-    hipLaunchKernelGGL(mlp_fwd_density_kernel, dim3((unsigned)grid), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    return dmn_check_launch("mlp_fwd_rays_density");
+    unsigned grid;
+    if (int rc = dmn_mlp_grid("mlp_fwd_rays_density", a.M, &grid)) return rc;
+    constexpr int LDS = LDS_FLOATS * sizeof(float);                      // 147 456 B: one workgroup per CU, as the full kernel
+    return dmn_launch_lds<mlp_fwd_density_kernel, LDS>("mlp_fwd_rays_density", grid, 256, LDS,
+                                                       (hipStream_t)stream, a);
 }

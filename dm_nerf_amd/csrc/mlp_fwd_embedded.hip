@@ -4,7 +4,7 @@
 
 extern "C" int dmnerf_mlp_fwd_embedded(const float* d_blob, int ins_num, const float* d_x, int64_t M,
                                        float* d_raw, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_embedded: ins_num %d unsupported", ins_num);
+    if (int rc = dmn_check_ins_num("mlp_fwd_embedded", ins_num)) return rc;
     if (M < 0) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_embedded: M < 0");
     if (M == 0) return DMNERF_OK;      // an empty batch is legal (and has null data pointers)
     if (!d_blob || !d_x || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_embedded: null pointer");

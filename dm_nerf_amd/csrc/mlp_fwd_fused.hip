@@ -5,15 +5,11 @@
 extern "C" int dmnerf_mlp_fwd_rays_fused(const float* d_blob_fused, int ins_num, const float* d_rays_o,
                                          const float* d_rays_d, const float* d_z, int64_t N, int S,
                                          float* d_raw, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_fused: ins_num %d unsupported", ins_num);
-    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_fused: bad N=%lld S=%d", (long long)N, S);
+    if (int rc = dmn_check_rays("mlp_fwd_rays_fused", ins_num, N, S)) return rc;
     if (N == 0) return DMNERF_OK;
     if (!d_blob_fused || !d_rays_o || !d_rays_d || !d_z || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_fused: null pointer");
     MlpArgs a{};
     a.blob = d_blob_fused; a.L = make_layout(ins_num, true); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
     a.raw = d_raw; a.M = N * S; a.S = S;
-#ifdef DMN_FWD_TRACE
-    a.trace = nullptr;
-#endif
     return launch<false, false, true>(a, (hipStream_t)stream);
 }

@@ -342,31 +342,20 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
 
 template <bool EMBEDDED, bool SAVE, bool FUSED = false>
 int launch(const MlpArgs& a, hipStream_t stream) {
-    const int64_t nblk = (a.M + 31) / 32;
-    const int64_t grid = (nblk + 3) / 4;
-    if (grid > 0x7fffffffLL) return dmn_fail(DMNERF_E_ARG, "mlp_fwd: %lld samples is too many for one launch", (long long)a.M);
+    unsigned grid;
+    if (int rc = dmn_mlp_grid("mlp_fwd", a.M, &grid)) return rc;
     if (SAVE && a.M > DMNERF_MAX_TRAIN_SAMPLES)
         return dmn_fail(DMNERF_E_ARG, "mlp_fwd_train: %lld samples per launch exceed %lld (32-bit row offsets); split the batch",
                         (long long)a.M, (long long)DMNERF_MAX_TRAIN_SAMPLES);
-    dim3 g((unsigned)grid), b(256);
-    constexpr size_t lds_bytes = (size_t)(LDS_FLOATS + PARK_FLOATS) * sizeof(float);   // 163 840 B = the CU's whole LDS: one workgroup per CU
-#define DMN_LAUNCH(OBI_)                                                                                              \
-    {                                                                                                                \
-        static DmnOncePerDevice once;                                                                                 \
-        if (hipError_t e_ = once.run([] { return hipFuncSetAttribute((const void*)(mlp_fwd_kernel<OBI_, EMBEDDED, SAVE, FUSED>),              \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }); e_ != hipSuccess) \
-            return dmn_fail_hip(e_, "mlp_fwd: hipFuncSetAttribute");                                       \
-        hipLaunchKernelGGL((mlp_fwd_kernel<OBI_, EMBEDDED, SAVE, FUSED>), g, b, lds_bytes, stream, a);                       \
-    }
+    constexpr int LDS = (LDS_FLOATS + PARK_FLOATS) * sizeof(float);   // 163 840 B = the CU's whole LDS: one workgroup per CU
+    const char* what = "mlp_fwd";
     switch (a.L.OBI) {
-        case 1: DMN_LAUNCH(1) break;
-        case 2: DMN_LAUNCH(2) break;
-        case 3: DMN_LAUNCH(3) break;
-        case 4: DMN_LAUNCH(4) break;
+        case 1: return dmn_launch_lds<mlp_fwd_kernel<1, EMBEDDED, SAVE, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
+        case 2: return dmn_launch_lds<mlp_fwd_kernel<2, EMBEDDED, SAVE, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
+        case 3: return dmn_launch_lds<mlp_fwd_kernel<3, EMBEDDED, SAVE, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
+        case 4: return dmn_launch_lds<mlp_fwd_kernel<4, EMBEDDED, SAVE, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
         default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd: unsupported logit count C=%d", a.L.C);
     }
-#undef DMN_LAUNCH
-    return dmn_check_launch("mlp_fwd");
 }
 
 }  // namespace

@@ -156,15 +156,11 @@ __global__ __launch_bounds__(256) void mlp_fwd_points_kernel(const PointsArgs a)
 
 template <bool GRID, bool OCC>
 int launch(const PointsArgs& a, const char* what, void* stream) {
-    const int64_t nblk = (a.M + 31) / 32;
-    const int64_t grid = (nblk + 3) / 4;
-    if (grid > 0x7fffffffLL) return dmn_fail(DMNERF_E_ARG, "%s: %lld samples is too many for one launch", what, (long long)a.M);
-    constexpr size_t lds_bytes = (size_t)LDS_FLOATS * sizeof(float);     // 147 456 B: one workgroup per CU, as the full kernel
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)mlp_fwd_points_kernel<GRID, OCC>,
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }); e != hipSuccess)
-        return dmn_fail_hip(e, what);
-    hipLaunchKernelGGL((mlp_fwd_points_kernel<GRID, OCC>), dim3((unsigned)grid), dim3(256), lds_bytes, (hipStream_t)stream, a);
+    unsigned grid;
+    if (int rc = dmn_mlp_grid(what, a.M, &grid)) return rc;
+    constexpr int LDS = LDS_FLOATS * sizeof(float);                      // 147 456 B: one workgroup per CU, as the full kernel
+    if (int rc = dmn_allow_lds<mlp_fwd_points_kernel<GRID, OCC>, LDS>(what, "")) return rc;
+    hipLaunchKernelGGL((mlp_fwd_points_kernel<GRID, OCC>), dim3(grid), dim3(256), LDS, (hipStream_t)stream, a);
     return dmn_check_launch(what);
 }
 
@@ -173,7 +169,7 @@ int launch(const PointsArgs& a, const char* what, void* stream) {
 extern "C" int dmnerf_mlp_fwd_points_density(const float* d_blob, int ins_num, const float* d_pts, int64_t M, float* d_out,
                                              float voxel, void* stream) {
     const char* what = "mlp_fwd_points_density";
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "%s: ins_num %d unsupported", what, ins_num);
+    if (int rc = dmn_check_ins_num(what, ins_num)) return rc;
     if (M < 0 || voxel != voxel) return dmn_fail(DMNERF_E_ARG, "%s: bad M=%lld voxel=%g", what, (long long)M, (double)voxel);
     if (M == 0) return DMNERF_OK;
     if (!d_blob || !d_pts || !d_out) return dmn_fail(DMNERF_E_ARG, "%s: null pointer", what);
@@ -185,7 +181,7 @@ extern "C" int dmnerf_mlp_fwd_points_density(const float* d_blob, int ins_num, c
 extern "C" int dmnerf_occupancy_slab(const float* d_blob, int ins_num, const float* d_t, int dim, const float* scale,
                                      const float* transform, int64_t m0, int64_t M, float* d_out, float voxel, void* stream) {
     const char* what = "occupancy_slab";
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "%s: ins_num %d unsupported", what, ins_num);
+    if (int rc = dmn_check_ins_num(what, ins_num)) return rc;
     if (dim < 1 || dim > GRID_DIM_MAX) return dmn_fail(DMNERF_E_ARG, "%s: dim %d outside 1 .. %d", what, dim, GRID_DIM_MAX);
     const int64_t total = (int64_t)dim * dim * dim;
     if (m0 < 0 || M < 0 || m0 > total || M > total - m0)

@@ -18,26 +18,17 @@ __global__ __launch_bounds__(256) void mlp_fwd_sel_kernel(const MlpSelArgs a) {
 
 template <bool FUSED>
 int launch_sel(const MlpSelArgs& a, hipStream_t stream) {
-    const int64_t grid = ((a.M + 31) / 32 + 3) / 4;
-    dim3 g((unsigned)grid), b(256);
-    constexpr size_t lds_bytes = (size_t)(LDS_FLOATS + PARK_FLOATS) * sizeof(float);
-#define DMN_LAUNCH_SEL(OBI_)                                                                                                     \
-    {                                                                                                                            \
-        static DmnOncePerDevice once;                                                                                            \
-        if (hipError_t e_ = once.run([] { return hipFuncSetAttribute((const void*)(mlp_fwd_sel_kernel<OBI_, FUSED>),             \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }); e_ != hipSuccess) \
-            return dmn_fail_hip(e_, "mlp_fwd_rays_sel: hipFuncSetAttribute");                                                    \
-        hipLaunchKernelGGL((mlp_fwd_sel_kernel<OBI_, FUSED>), g, b, lds_bytes, stream, a);                                       \
-    }
+    unsigned grid;                                                       // the worst case count == M (< 2^31 samples: fits)
+    if (int rc = dmn_mlp_grid("mlp_fwd_rays_sel", a.M, &grid)) return rc;
+    constexpr int LDS = (LDS_FLOATS + PARK_FLOATS) * sizeof(float);
+    const char* what = "mlp_fwd_rays_sel";
     switch (a.L.OBI) {
-        case 1: DMN_LAUNCH_SEL(1) break;
-        case 2: DMN_LAUNCH_SEL(2) break;
-        case 3: DMN_LAUNCH_SEL(3) break;
-        case 4: DMN_LAUNCH_SEL(4) break;
+        case 1: return dmn_launch_lds<mlp_fwd_sel_kernel<1, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
+        case 2: return dmn_launch_lds<mlp_fwd_sel_kernel<2, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
+        case 3: return dmn_launch_lds<mlp_fwd_sel_kernel<3, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
+        case 4: return dmn_launch_lds<mlp_fwd_sel_kernel<4, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
         default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_sel: unsupported logit count C=%d", a.L.C);
     }
-#undef DMN_LAUNCH_SEL
-    return dmn_check_launch("mlp_fwd_rays_sel");
 }
 
 }  // namespace

@@ -35,19 +35,12 @@ __global__ __launch_bounds__(256) void mlp_fwd_density_sel_kernel(const DensityS
     mlp_fwd_density_body<true>(a);
 }
 
-int check_sel(const char* who, int ins_num, int64_t N, int S) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "%s: ins_num %d unsupported", who, ins_num);
-    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "%s: bad N=%lld S=%d", who, (long long)N, S);
-    if (N * S >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: %lld samples do not fit the int32 selection", who, (long long)(N * S));
-    return DMNERF_OK;
-}
-
 }  // namespace
 
 extern "C" int dmnerf_mlp_fwd_rays_sel(const float* d_blob, int ins_num, int fused_heads, const float* d_rays_o,
                                        const float* d_rays_d, const float* d_z, int64_t N, int S,
                                        const int* d_sel, const int* d_count, float* d_raw, void* stream) {
-    if (int rc = check_sel("mlp_fwd_rays_sel", ins_num, N, S)) return rc;
+    if (int rc = dmn_check_rays("mlp_fwd_rays_sel", ins_num, N, S, true)) return rc;
     if (fused_heads != 0 && fused_heads != 1) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_sel: fused_heads %d unsupported", fused_heads);
     if (N == 0) return DMNERF_OK;
     if (!d_blob || !d_rays_o || !d_rays_d || !d_z || !d_sel || !d_count || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_sel: null pointer");
@@ -55,27 +48,21 @@ extern "C" int dmnerf_mlp_fwd_rays_sel(const float* d_blob, int ins_num, int fus
     MlpSelArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
     a.raw = d_raw; a.M = N * S; a.S = S; a.sel = d_sel; a.count = d_count;
-#ifdef DMN_FWD_TRACE
-    a.trace = nullptr;
-#endif
     return launch_sel<false>(a, (hipStream_t)stream);
 }
 
 extern "C" int dmnerf_mlp_fwd_rays_density_sel(const float* d_blob, int ins_num, const float* d_rays_o,
                                                const float* d_rays_d, const float* d_z, int64_t N, int S,
                                                const int* d_sel, const int* d_count, float* d_sigma, void* stream) {
-    if (int rc = check_sel("mlp_fwd_rays_density_sel", ins_num, N, S)) return rc;
+    if (int rc = dmn_check_rays("mlp_fwd_rays_density_sel", ins_num, N, S, true)) return rc;
     if (N == 0) return DMNERF_OK;
     if (!d_blob || !d_rays_o || !d_rays_d || !d_z || !d_sel || !d_count || !d_sigma) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density_sel: null pointer");
     DensitySelArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
     a.sigma = d_sigma; a.M = N * S; a.S = S; a.sel = d_sel; a.count = d_count;
-    const int64_t grid = ((a.M + 31) / 32 + 3) / 4;
-    constexpr size_t lds_bytes = (size_t)LDS_FLOATS * sizeof(float);
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)mlp_fwd_density_sel_kernel,
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }); e != hipSuccess)
-        return dmn_fail_hip(e, "mlp_fwd_rays_density_sel: hipFuncSetAttribute");
-    hipLaunchKernelGGL(mlp_fwd_density_sel_kernel, dim3((unsigned)grid), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    return dmn_check_launch("mlp_fwd_rays_density_sel");
+    unsigned grid;
+    if (int rc = dmn_mlp_grid("mlp_fwd_rays_density_sel", a.M, &grid)) return rc;
+    constexpr int LDS = LDS_FLOATS * sizeof(float);
+    return dmn_launch_lds<mlp_fwd_density_sel_kernel, LDS>("mlp_fwd_rays_density_sel", grid, 256,
+                                                           LDS, (hipStream_t)stream, a);
 }

@@ -7,8 +7,5 @@ int dmn_mlp_fwd_rays_sel_fused(const float* d_blob, int ins_num, const float* d_
     MlpSelArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num, true); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
     a.raw = d_raw; a.M = N * S; a.S = S; a.sel = d_sel; a.count = d_count;
-#ifdef DMN_FWD_TRACE
-    a.trace = nullptr;
-#endif
     return launch_sel<true>(a, stream);
 }

@@ -38,31 +38,20 @@ extern "C" int dmnerf_pack_split(const float* d_flat, const int32_t* d_idx, floa
 
 extern "C" int dmnerf_mlp_fwd_rays_split(const float* d_blob_split, int ins_num, const float* d_rays_o, const float* d_rays_d,
                                          const float* d_z, int64_t N, int S, float* d_raw, void* stream) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_split: ins_num %d unsupported", ins_num);
-    if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_split: bad N=%lld S=%d", (long long)N, S);
+    if (int rc = dmn_check_rays("mlp_fwd_rays_split", ins_num, N, S)) return rc;
     if (N == 0) return DMNERF_OK;
     if (!d_blob_split || !d_rays_o || !d_rays_d || !d_z || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_split: null pointer");
     SplitArgs a{};
     a.blob = d_blob_split; a.L = make_layout(ins_num, true); a.S = make_split_layout(ins_num);
     a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z; a.raw = d_raw; a.M = N * S; a.Sr = S;
-    const int64_t nblk = (a.M + 31) / 32;
-    const int64_t grid = (nblk + 3) / 4;
-    if (grid > 0x7fffffffLL) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_split: too many samples");
-    constexpr size_t lds_bytes = (size_t)SP_LDS_FLOATS * sizeof(float);
-#define DMN_LAUNCH(OBX_)                                                                                                   \
-    {                                                                                                                     \
-        static DmnOncePerDevice once;                                                                                 \
-        if (hipError_t e_ = once.run([] { return hipFuncSetAttribute((const void*)mlp_split_kernel<OBX_>,              \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }); e_ != hipSuccess) \
-            return dmn_fail_hip(e_, "mlp_fwd_rays_split: hipFuncSetAttribute");                                       \
-        hipLaunchKernelGGL(mlp_split_kernel<OBX_>, dim3((unsigned)grid), dim3(256), lds_bytes, (hipStream_t)stream, a);    \
-    }
+    unsigned grid;
+    if (int rc = dmn_mlp_grid("mlp_fwd_rays_split", a.M, &grid, true)) return rc;
+    constexpr int LDS = SP_LDS_FLOATS * sizeof(float);
+    const char* what = "mlp_fwd_rays_split";
     switch (a.S.OBX) {
-        case 1: DMN_LAUNCH(1) break;
-        case 2: DMN_LAUNCH(2) break;
-        case 4: DMN_LAUNCH(4) break;
+        case 1: return dmn_launch_lds<mlp_split_kernel<1>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
+        case 2: return dmn_launch_lds<mlp_split_kernel<2>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
+        case 4: return dmn_launch_lds<mlp_split_kernel<4>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
         default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_split: unsupported logit count C=%d", a.S.C);
     }
-#undef DMN_LAUNCH
-    return dmn_check_launch("mlp_fwd_rays_split");
 }

@@ -176,7 +176,7 @@ extern "C" int dmnerf_repack_train(const dmnerf_repack_model* models, int n_mode
     int64_t most = 0;
     for (int i = 0; i < n_models; ++i) {
         const dmnerf_repack_model& s = models[i];
-        if (s.ins_num < 1 || s.ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "repack_train: ins_num %d unsupported", s.ins_num);
+        if (int rc = dmn_check_ins_num("repack_train", s.ins_num)) return rc;
         if (!s.d_params_flat || !s.d_idx || !s.d_blob || !s.d_idx_t || !s.d_blob_t) return dmn_fail(DMNERF_E_ARG, "repack_train: null pointer");
         if (s.d_flat_copy == s.d_params_flat) return dmn_fail(DMNERF_E_ARG, "repack_train: d_flat_copy aliases d_params_flat");
         RepackModel& m = a.m[i];

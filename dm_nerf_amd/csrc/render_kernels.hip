@@ -155,7 +155,7 @@ __host__ __device__ inline int ray_row_len(int S, int C) {
 }
 __device__ __forceinline__ float* ray_row(float* base, int k, int wv, int SP) { return base + ((size_t)k * RAYS_PER_BLOCK + wv) * SP; }
 inline size_t ray_lds_bytes(int rows, int S, int C) { return (size_t)rows * RAYS_PER_BLOCK * ray_row_len(S, C) * sizeof(float); }
-constexpr size_t RAY_LDS_MAX = (size_t)4 * RAYS_PER_BLOCK * MAX_S * sizeof(float);      // 80 KiB: four rows at MAX_S
+constexpr int RAY_LDS_MAX = 4 * RAYS_PER_BLOCK * MAX_S * sizeof(float);                 // 80 KiB: four rows at MAX_S
 
 // The compositing weights of one ray (render.py:6-20), one wave per ray: alpha from the density channel, the exclusive product
 // scan in double, w = alpha T.  sig[s * sig_stride] = the density of sample s (raw rows: stride 4 + C; a compact sigma row: 1).
@@ -841,13 +841,10 @@ __global__ void gather_kernel(const float* __restrict__ flat, const int32_t* __r
 
 inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
-// dynamic LDS of the wave-per-ray kernels may exceed the 64 KiB default at large S: raise the kernel's limit once per device
-template <class K>
-int ray_lds_allow(K kernel, DmnOncePerDevice& once, const char* what) {
-    if (hipError_t e = once.run([&] { return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RAY_LDS_MAX); });
-        e != hipSuccess)
-        return dmn_fail_hip(e, what);
-    return DMNERF_OK;
+// One wave per ray.  The rows' dynamic LDS may exceed the 64 KiB default at large S: every launch allows RAY_LDS_MAX (common.h).
+template <auto Kernel, class... Args>
+int ray_launch(const char* what, int64_t N, size_t lds_bytes, void* stream, const Args&... args) {
+    return dmn_launch_lds<Kernel, RAY_LDS_MAX>(what, blocks_for(N, RAYS_PER_BLOCK), WAVE * RAYS_PER_BLOCK, lds_bytes, (hipStream_t)stream, args...);
 }
 
 }  // namespace
@@ -908,11 +905,8 @@ extern "C" int dmnerf_composite_fwd(const float* d_raw, const float* d_z, const 
     // (C = 1: the object-code map has C - 1 = 0 columns, and an empty tensor has no storage; the kernel never touches it)
     if (!d_raw || !d_z || !d_rays_d || !d_rgb_map || !d_weights || !d_depth_map || (C > 1 && !d_ins_map))
         return dmn_fail(DMNERF_E_ARG, "composite_fwd: null pointer");
-    static DmnOncePerDevice once;
-    if (int rc = ray_lds_allow(composite_kernel, once, "composite_fwd: hipFuncSetAttribute")) return rc;
-    hipLaunchKernelGGL(composite_kernel, dim3(blocks_for(N, RAYS_PER_BLOCK)), dim3(WAVE * RAYS_PER_BLOCK), ray_lds_bytes(1, S, C), (hipStream_t)stream,
-                       d_raw, d_z, d_rays_d, N, S, C, C - 1, d_rgb_map, d_weights, d_depth_map, d_ins_map);
-    return dmn_check_launch("composite_fwd");
+    return ray_launch<composite_kernel>("composite_fwd", N, ray_lds_bytes(1, S, C), stream,
+                                        d_raw, d_z, d_rays_d, N, S, C, C - 1, d_rgb_map, d_weights, d_depth_map, d_ins_map);
 }
 
 extern "C" int dmnerf_weights_from_sigma(const float* d_sigma, const float* d_z, const float* d_rays_d, int64_t N, int S,
@@ -932,11 +926,8 @@ extern "C" int dmnerf_manipulator_render(const float* d_raw, const float* d_z, c
     if (N == 0) return DMNERF_OK;
     if (!d_raw || !d_z || !d_rays_d || !d_rgb_map || !d_weights || !d_depth_map || !d_ins_map)
         return dmn_fail(DMNERF_E_ARG, "manipulator_render: null pointer");
-    static DmnOncePerDevice once;
-    if (int rc = ray_lds_allow(composite_kernel, once, "manipulator_render: hipFuncSetAttribute")) return rc;
-    hipLaunchKernelGGL(composite_kernel, dim3(blocks_for(N, RAYS_PER_BLOCK)), dim3(WAVE * RAYS_PER_BLOCK), ray_lds_bytes(1, S, C), (hipStream_t)stream,
-                       d_raw, d_z, d_rays_d, N, S, C, C, d_rgb_map, d_weights, d_depth_map, d_ins_map);
-    return dmn_check_launch("manipulator_render");
+    return ray_launch<composite_kernel>("manipulator_render", N, ray_lds_bytes(1, S, C), stream,
+                                        d_raw, d_z, d_rays_d, N, S, C, C, d_rgb_map, d_weights, d_depth_map, d_ins_map);
 }
 
 extern "C" int dmnerf_sample_pdf(const float* d_bins, const float* d_weights, const float* d_u, int64_t u_row_stride,
@@ -985,11 +976,8 @@ extern "C" int dmnerf_composite_bwd(const float* d_raw, const float* d_z, const 
     if (N == 0) return DMNERF_OK;
     if (!d_raw || !d_z || !d_rays_d || !d_g_rgb || !d_grad_raw || (C > 1 && (!d_ins_map || !d_g_ins)))      // (C = 1: see composite_fwd)
         return dmn_fail(DMNERF_E_ARG, "composite_bwd: null pointer");
-    static DmnOncePerDevice once;
-    if (int rc = ray_lds_allow(composite_bwd_kernel<false>, once, "composite_bwd: hipFuncSetAttribute")) return rc;
-    hipLaunchKernelGGL(composite_bwd_kernel<false>, dim3(blocks_for(N, RAYS_PER_BLOCK)), dim3(WAVE * RAYS_PER_BLOCK), ray_lds_bytes(3, S, C), (hipStream_t)stream,
-                       d_raw, d_z, d_rays_d, d_ins_map, d_g_rgb, d_g_ins, d_g_depth, d_g_weights, N, S, C, d_grad_raw, PenBwd{});
-    return dmn_check_launch("composite_bwd");
+    return ray_launch<composite_bwd_kernel<false>>("composite_bwd", N, ray_lds_bytes(3, S, C), stream,
+                                                   d_raw, d_z, d_rays_d, d_ins_map, d_g_rgb, d_g_ins, d_g_depth, d_g_weights, N, S, C, d_grad_raw, PenBwd{});
 }
 
 extern "C" int dmnerf_composite_pen_fwd(const float* d_raw, const float* d_z, const float* d_rays_d, int64_t N, int S, int C,
@@ -1002,11 +990,8 @@ extern "C" int dmnerf_composite_pen_fwd(const float* d_raw, const float* d_z, co
     PenArgs a{};
     a.raw = d_raw; a.z = d_z; a.depth = d_depth_map; a.rays_d = d_rays_d; a.N = N; a.S = S; a.C = C;
     a.tol = tolerance; a.k2w = two_deta_w_sq; a.kh = gauss_norm; a.out4 = d_partials;
-    static DmnOncePerDevice once;
-    if (int rc = ray_lds_allow(composite_pen_kernel, once, "composite_pen_fwd: hipFuncSetAttribute")) return rc;
-    hipLaunchKernelGGL(composite_pen_kernel, dim3(blocks_for(N, RAYS_PER_BLOCK)), dim3(WAVE * RAYS_PER_BLOCK), ray_lds_bytes(3, S, C), (hipStream_t)stream,
-                       a, d_rgb_map, d_weights, d_depth_map, d_ins_map);
-    return dmn_check_launch("composite_pen_fwd");
+    return ray_launch<composite_pen_kernel>("composite_pen_fwd", N, ray_lds_bytes(3, S, C), stream,
+                                            a, d_rgb_map, d_weights, d_depth_map, d_ins_map);
 }
 
 extern "C" int dmnerf_composite_pen_bwd(const float* d_raw, const float* d_z, const float* d_rays_d, const float* d_ins_map,
@@ -1019,11 +1004,8 @@ extern "C" int dmnerf_composite_pen_bwd(const float* d_raw, const float* d_z, co
         return dmn_fail(DMNERF_E_ARG, "composite_pen_bwd: null pointer");
     PenBwd pen{};
     pen.depth = d_depth_map; pen.g_part = d_g_partials; pen.tol = tolerance; pen.k2w = two_deta_w_sq; pen.kh = gauss_norm;
-    static DmnOncePerDevice once;
-    if (int rc = ray_lds_allow(composite_bwd_kernel<true>, once, "composite_pen_bwd: hipFuncSetAttribute")) return rc;
-    hipLaunchKernelGGL(composite_bwd_kernel<true>, dim3(blocks_for(N, RAYS_PER_BLOCK)), dim3(WAVE * RAYS_PER_BLOCK), ray_lds_bytes(4, S, C), (hipStream_t)stream,
-                       d_raw, d_z, d_rays_d, d_ins_map, d_g_rgb, d_g_ins, d_g_depth, d_g_weights, N, S, C, d_grad_raw, pen);
-    return dmn_check_launch("composite_pen_bwd");
+    return ray_launch<composite_bwd_kernel<true>>("composite_pen_bwd", N, ray_lds_bytes(4, S, C), stream,
+                                                  d_raw, d_z, d_rays_d, d_ins_map, d_g_rgb, d_g_ins, d_g_depth, d_g_weights, N, S, C, d_grad_raw, pen);
 }
 
 extern "C" int dmnerf_penalizer_fwd(const float* d_raw, const float* d_z, const float* d_depth, const float* d_rays_d,
@@ -1035,10 +1017,7 @@ extern "C" int dmnerf_penalizer_fwd(const float* d_raw, const float* d_z, const 
     PenArgs a{};
     a.raw = d_raw; a.z = d_z; a.depth = d_depth; a.rays_d = d_rays_d; a.N = N; a.S = S; a.C = C;
     a.tol = tolerance; a.k2w = two_deta_w_sq; a.kh = gauss_norm; a.out4 = d_partials;
-    static DmnOncePerDevice once;
-    if (int rc = ray_lds_allow(penalizer_kernel<0>, once, "penalizer_fwd: hipFuncSetAttribute")) return rc;
-    hipLaunchKernelGGL(penalizer_kernel<0>, dim3(blocks_for(N, RAYS_PER_BLOCK)), dim3(WAVE * RAYS_PER_BLOCK), ray_lds_bytes(2, S, C), (hipStream_t)stream, a);
-    return dmn_check_launch("penalizer_fwd");
+    return ray_launch<penalizer_kernel<0>>("penalizer_fwd", N, ray_lds_bytes(2, S, C), stream, a);
 }
 
 extern "C" int dmnerf_penalizer_bwd(const float* d_raw, const float* d_z, const float* d_depth, const float* d_rays_d,
@@ -1050,10 +1029,7 @@ extern "C" int dmnerf_penalizer_bwd(const float* d_raw, const float* d_z, const 
     PenArgs a{};
     a.raw = d_raw; a.z = d_z; a.depth = d_depth; a.rays_d = d_rays_d; a.N = N; a.S = S; a.C = C;
     a.tol = tolerance; a.k2w = two_deta_w_sq; a.kh = gauss_norm; a.scales = d_scales; a.d_raw = d_grad_raw;
-    static DmnOncePerDevice once;
-    if (int rc = ray_lds_allow(penalizer_kernel<1>, once, "penalizer_bwd: hipFuncSetAttribute")) return rc;
-    hipLaunchKernelGGL(penalizer_kernel<1>, dim3(blocks_for(N, RAYS_PER_BLOCK)), dim3(WAVE * RAYS_PER_BLOCK), ray_lds_bytes(2, S, C), (hipStream_t)stream, a);
-    return dmn_check_launch("penalizer_bwd");
+    return ray_launch<penalizer_kernel<1>>("penalizer_bwd", N, ray_lds_bytes(2, S, C), stream, a);
 }
 
 // The scalar tail of emptiness_penalizer (penalizer.py:44-55) on the device: the per-ray partials -> 4 sums (one block, fixed

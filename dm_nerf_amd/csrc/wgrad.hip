@@ -423,7 +423,7 @@ Plan make_plan(int ins_num, int64_t M, int max_wgs, int mode = 0) {
 
 static int plan_sizes(int mode, int ins_num, int64_t M, int max_wgs, int64_t* n_job_bytes, int64_t* n_out_bytes,
                       int64_t* part_floats, int* n_jobs, int* n_outs) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS || M < 1 || max_wgs < 32) return dmn_fail(DMNERF_E_ARG, "wgrad_plan: bad argument");
+    if (!dmn_ins_num_ok(ins_num) || M < 1 || max_wgs < 32) return dmn_fail(DMNERF_E_ARG, "wgrad_plan: bad argument");
     const Plan P = make_plan(ins_num, M, max_wgs, mode);
     if (n_job_bytes) *n_job_bytes = (int64_t)(P.jobs.size() * sizeof(WgJob));
     if (n_out_bytes) *n_out_bytes = (int64_t)(P.outs.size() * sizeof(WgOut));
@@ -434,7 +434,7 @@ static int plan_sizes(int mode, int ins_num, int64_t M, int max_wgs, int64_t* n_
 }
 
 static int plan_fill(int mode, int ins_num, int64_t M, int max_wgs, void* h_jobs, int64_t job_bytes, void* h_outs, int64_t out_bytes) {
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS || M < 1 || max_wgs < 32 || !h_jobs || !h_outs) return dmn_fail(DMNERF_E_ARG, "wgrad_plan: bad argument");
+    if (!dmn_ins_num_ok(ins_num) || M < 1 || max_wgs < 32 || !h_jobs || !h_outs) return dmn_fail(DMNERF_E_ARG, "wgrad_plan: bad argument");
     const Plan P = make_plan(ins_num, M, max_wgs, mode);
     if (job_bytes != (int64_t)(P.jobs.size() * sizeof(WgJob)) || out_bytes != (int64_t)(P.outs.size() * sizeof(WgOut)))
         return dmn_fail(DMNERF_E_ARG, "wgrad_plan: buffer sizes do not match dmnerf_wgrad_plan_sizes");
@@ -478,18 +478,13 @@ extern "C" int dmnerf_mlp_bwd_weights(const float* d_save, const float* d_dsave,
                                       const float* d_params_flat, int ins_num, float* d_part, float* d_grad_flat, void* stream) {
     if (!d_save || !d_dsave || !d_graw_t || !d_jobs || !d_outs || !d_params_flat || !d_part || !d_grad_flat || M < 1 || n_jobs < 1 || n_outs < 1)
         return dmn_fail(DMNERF_E_ARG, "mlp_bwd_weights: bad argument");
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "mlp_bwd_weights: ins_num %d unsupported", ins_num);
+    if (int rc = dmn_check_ins_num("mlp_bwd_weights", ins_num)) return rc;
     WgArgs a{};
     a.src[0] = d_save; a.src[1] = d_dsave; a.src[2] = d_graw_t;
     a.part = d_part; a.jobs = (const WgJob*)d_jobs; a.Mp = save_row_len(M); a.trace = g_dmn_wgrad_trace;
-    const size_t lds_bytes = WG_LDS_BYTES;
-    static DmnOncePerDevice once;
-    if (hipError_t e = once.run([&] { return hipFuncSetAttribute((const void*)wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); });
-        e != hipSuccess)
-        return dmn_fail_hip(e, "mlp_bwd_weights: hipFuncSetAttribute");
-    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)n_jobs), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    int rc = dmn_check_launch("mlp_bwd_weights");
-    if (rc) return rc;
+    if (int rc = dmn_launch_lds<wgrad_kernel, WG_LDS_BYTES>("mlp_bwd_weights", (unsigned)n_jobs, 256,
+                                                            WG_LDS_BYTES, (hipStream_t)stream, a))
+        return rc;
     return dmn_wgrad_finish(d_outs, n_outs, d_params_flat, ins_num, d_part, d_grad_flat, (hipStream_t)stream);
 }
 

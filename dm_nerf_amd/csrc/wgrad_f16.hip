@@ -43,8 +43,7 @@ __global__ __launch_bounds__(256) void wgrad_f16_kernel(const WgArgs a) { wgrad_
 extern "C" int dmnerf_mlp_bwd_weights_f16(const float* d_save, const float* d_dsave, const float* d_graw_t, int64_t M,
                                           const void* d_jobs, int n_jobs, const void* d_outs, int n_outs,
                                           const float* d_params_flat, int ins_num, float* d_part, float* d_grad_flat, const float* d_scale, void* stream) {
-    static DmnOncePerDevice once;
     // the dy operands carry the factor 2^s of dmnerf_grad_scale: the second stage multiplies by d_scale[1] = 2^-s
-    return wgrad_split_launch(wgrad_f16_kernel, once, "mlp_bwd_weights_f16", d_save, d_dsave, d_graw_t, M, d_jobs, n_jobs, d_outs, n_outs, d_params_flat, ins_num,
+    return wgrad_split_launch<wgrad_f16_kernel>("mlp_bwd_weights_f16", d_save, d_dsave, d_graw_t, M, d_jobs, n_jobs, d_outs, n_outs, d_params_flat, ins_num,
                                          d_part, d_grad_flat, d_scale ? d_scale + 1 : nullptr, stream);
 }

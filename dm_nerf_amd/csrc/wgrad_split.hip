@@ -45,7 +45,6 @@ __global__ __launch_bounds__(256) void wgrad_split_kernel(const WgArgs a) { wgra
 extern "C" int dmnerf_mlp_bwd_weights_split(const float* d_save, const float* d_dsave, const float* d_graw_t, int64_t M,
                                             const void* d_jobs, int n_jobs, const void* d_outs, int n_outs,
                                             const float* d_params_flat, int ins_num, float* d_part, float* d_grad_flat, void* stream) {
-    static DmnOncePerDevice once;
-    return wgrad_split_launch(wgrad_split_kernel, once, "mlp_bwd_weights_split", d_save, d_dsave, d_graw_t, M, d_jobs, n_jobs, d_outs, n_outs, d_params_flat, ins_num,
+    return wgrad_split_launch<wgrad_split_kernel>("mlp_bwd_weights_split", d_save, d_dsave, d_graw_t, M, d_jobs, n_jobs, d_outs, n_outs, d_params_flat, ins_num,
                                           d_part, d_grad_flat, nullptr, stream);
 }

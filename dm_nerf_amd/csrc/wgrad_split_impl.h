@@ -314,23 +314,19 @@ __device__ __forceinline__ void wgrad_split_body(const WgArgs& a) {
 }
 
 // Launch + second stage; d_unscale: null, or the factor the dy operands must lose again (f16x2: 2^-s of dmnerf_grad_scale).
-template <class Kernel>
-int wgrad_split_launch(Kernel kernel, DmnOncePerDevice& once, const char* what, const float* d_save, const float* d_dsave, const float* d_graw_t, int64_t M, const void* d_jobs, int n_jobs,
+template <auto Kernel>
+int wgrad_split_launch(const char* what, const float* d_save, const float* d_dsave, const float* d_graw_t, int64_t M, const void* d_jobs, int n_jobs,
                        const void* d_outs, int n_outs, const float* d_params_flat, int ins_num, float* d_part, float* d_grad_flat,
                        const float* d_unscale, void* stream) {
     if (!d_save || !d_dsave || !d_graw_t || !d_jobs || !d_outs || !d_params_flat || !d_part || !d_grad_flat || M < 1 || n_jobs < 1 || n_outs < 1)
         return dmn_fail(DMNERF_E_ARG, "%s: bad argument", what);
-    if (ins_num < 1 || ins_num + 1 > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "%s: ins_num %d unsupported", what, ins_num);
+    if (int rc = dmn_check_ins_num(what, ins_num)) return rc;
     WgArgs a{};
     a.src[0] = d_save; a.src[1] = d_dsave; a.src[2] = d_graw_t;
     a.part = d_part; a.jobs = (const WgJob*)d_jobs; a.Mp = save_row_len(M); a.trace = g_dmn_wgrad_trace;
-    const size_t lds_bytes = WG_LDS_BYTES;
-    if (hipError_t e = once.run([&] { return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); });
-        e != hipSuccess)
-        return dmn_fail_hip(e, what);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)n_jobs), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    const int rc = dmn_check_launch(what);
-    if (rc) return rc;
+    if (int rc = dmn_allow_lds<Kernel, WG_LDS_BYTES>(what, "")) return rc;
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)n_jobs), dim3(256), WG_LDS_BYTES, (hipStream_t)stream, a);
+    if (int rc = dmn_check_launch(what)) return rc;
     return dmn_wgrad_finish(d_outs, n_outs, d_params_flat, ins_num, d_part, d_grad_flat, (hipStream_t)stream, d_unscale);
 }
 
