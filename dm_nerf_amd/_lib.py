@@ -205,6 +205,8 @@ SIGNATURES = {
     "dmnerf_mlp_fwd_rays_f16_sel": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_mlp_fwd_rays_density_f16_sel": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_render_rays_fwd_fine_skip": (c_int, [ctypes.POINTER(RenderFineSkipArgs), c_vp]),
+    "dmnerf_skip_grid_mark": (c_int, [ctypes.POINTER(SkipGridArgs), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_float, c_vp]),
+    "dmnerf_skip_grid_dilate": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
 }
 
 _lib = None

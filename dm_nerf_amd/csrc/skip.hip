@@ -13,8 +13,16 @@
 //                            argmax over its C logits is C - 1, the label of empty space, never the label of a moved object
 //                            ("The empty row").
 //
-// No atomics anywhere: a word of the grid is written by the one lane that holds its ballot, and the compaction is three passes
-// (per-block counts, one scan of the counts, scatter by prefix sums), so the list is in ascending order and the same every run.
+//   dmnerf_skip_grid_mark    the grid from rendered views: the cell of every sample whose compositing weight is > threshold (NaN
+//                            counts) gets its bit OR-ed in; bits are only ever set.
+//   dmnerf_skip_grid_dilate  out(g) = OR of in over the (2 dilate + 1)^3 neighbourhood of g, clipped at the faces: the build's
+//                            dilation with a set bit as the predicate.
+//
+// No atomics, with one exception: in build and dilate a word of the grid is written by the one lane that holds its ballot, and the
+// select's compaction is three passes (per-block counts, one scan of the counts, scatter by prefix sums), so the list is in ascending
+// order and the same every run.  The exception is skip_mark_kernel: samples of many rays fall into one word, so a lane ORs its bit in
+// with atomicOr -- after reading the word, and only where the bit still reads clear, so once the bits have saturated the kernel
+// only loads.  OR is commutative and associative: whatever the order of the lanes, the words are the same every run.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -167,6 +175,90 @@ __global__ __launch_bounds__(BLOCK) void skip_flag_fill_kernel(GridDev G, const 
     }
 }
 
+// ---- mark.  The cell of sample (ray n, depth zv): skip_flag_kernel's arithmetic, operation for operation (separate multiply and add
+// for p = o + d z, render.py:49; subtract, multiply, floorf, each rounded on its own; the inside test on the float, so a NaN point is
+// outside).  -> inside; *g_out = the cell's index where inside.  skip_flag_kernel and skip_flag_fill_kernel keep their own copies
+// of these statements so that they run the machine code they always ran.
+struct CellDev {
+    float lo[3], inv_cell[3];
+    int dims[3];
+};
+
+__device__ __forceinline__ bool skip_cell_of(const CellDev& G, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                             int64_t n, float zv, int64_t* g_out) {
+    bool inside = true;
+    int64_t g = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float p = __fadd_rn(rays_o[n * 3 + a], __fmul_rn(rays_d[n * 3 + a], zv));
+        const float c = floorf(__fmul_rn(__fsub_rn(p, G.lo[a]), G.inv_cell[a]));
+        inside = inside && (c >= 0.f) && (c < (float)G.dims[a]);
+        g = g * G.dims[a] + (inside ? (int)c : 0);
+    }
+    *g_out = g;
+    return inside;
+}
+
+// One sample per lane: consecutive lanes read consecutive z and w.  A sample marks iff it is inside the box and !(w <= threshold)
+// (NaN marks).  The word is read first (a relaxed atomic load: other lanes may be OR-ing into it) and the atomicOr is issued only
+// where the bit reads clear; a stale read costs one redundant OR, never a lost bit.  inside => 0 <= g < cells, so the word exists
+// and the unused bits of the last word are never touched.
+__global__ __launch_bounds__(BLOCK) void skip_mark_kernel(CellDev G, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                          const float* __restrict__ z, const float* __restrict__ w, int64_t M, int S,
+                                                          float threshold, uint32_t* bits) {
+    const int64_t m = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (m >= M) return;
+    const float wv = w[m], zv = z[m];
+    if (wv <= threshold) return;
+    int64_t g;
+    if (!skip_cell_of(G, rays_o, rays_d, m / S, zv, &g)) return;
+    uint32_t* word = bits + (g >> 5);
+    const uint32_t bit = 1u << (g & 31);
+    if ((__atomic_load_n(word, __ATOMIC_RELAXED) & bit) == 0) atomicOr(word, bit);
+}
+
+// ---- dilate.  skip_grid_build_kernel's tiling (a block owns 256 consecutive cells = 8 whole words; the LDS tile holds the predicate of
+// the (2 d + 1)^2 runs of 256 + 2 d cells; the clipping at the faces is decided per cell from its coordinates) with bit gl of `in`
+// as the predicate instead of sigma[gl] > threshold.  A kernel of its own: the build kernel is left as it is.
+__global__ __launch_bounds__(BLOCK) void skip_grid_dilate_kernel(const uint32_t* __restrict__ in, int dx, int dy, int dz, int d,
+                                                                 uint32_t* __restrict__ bits) {
+    extern __shared__ unsigned char tile[];                    // [(2d+1)^2][256 + 2d]
+    const int D = 2 * d + 1, SEG = BLOCK + 2 * d;
+    const int64_t total = (int64_t)dx * dy * dz;
+    const int64_t g0 = (int64_t)blockIdx.x * BLOCK;
+    for (int idx = threadIdx.x; idx < D * D * SEG; idx += BLOCK) {
+        const int seg = idx / SEG, t = idx - seg * SEG;
+        const int di = seg / D - d, dj = seg % D - d;
+        const int64_t gl = g0 - d + t + ((int64_t)di * dy + dj) * dz;
+        unsigned char v = 0;
+        if (gl >= 0 && gl < total) v = (in[gl >> 5] >> (gl & 31)) & 1u;
+        tile[idx] = v;
+    }
+    __syncthreads();
+    const int64_t g = g0 + threadIdx.x;
+    bool occ = false;
+    if (g < total) {
+        const int k = (int)(g % dz);
+        const int64_t r = g / dz;
+        const int j = (int)(r % dy), i = (int)(r / dy);
+        for (int di = -d; di <= d; ++di) {
+            if (i + di < 0 || i + di >= dx) continue;
+            for (int dj = -d; dj <= d; ++dj) {
+                if (j + dj < 0 || j + dj >= dy) continue;
+                const unsigned char* run = tile + ((di + d) * D + (dj + d)) * SEG + threadIdx.x + d;
+                for (int dk = -d; dk <= d; ++dk)
+                    if (k + dk >= 0 && k + dk < dz) occ |= run[dk] != 0;
+            }
+        }
+    }
+    const unsigned long long ballot = __ballot(occ);           // 64 cells = 2 words; lanes 0 and 32 each own one
+    const int lane = threadIdx.x & 63;
+    if ((lane & 31) == 0) {
+        const int64_t w = (g0 + (threadIdx.x & ~63)) / 32 + (lane >> 5);
+        if (w < (total + 31) / 32) bits[w] = (uint32_t)(ballot >> (lane & 32));
+    }
+}
+
 // ---- pass 2: exclusive scan of the block counts in place (one workgroup walks them, 1024 at a time) and the grand total
 __global__ __launch_bounds__(1024) void skip_scan_kernel(int* __restrict__ block_n, int64_t nb, int* __restrict__ count) {
     __shared__ int buf[1024];
@@ -288,4 +380,42 @@ extern "C" int dmnerf_skip_select_fill(const dmnerf_skip_grid* grid, const float
                                        const float* d_fill_row, int width, int64_t* d_totals, void* stream) {
     return skip_select_impl("skip_select_fill", grid, d_rays_o, d_rays_d, d_z, N, S, d_flag, d_sel, d_count, d_work, d_rows, d_fill_row,
                             width, d_totals, (hipStream_t)stream);
+}
+
+// The grid from rendered views: OR the bit of every sample's cell whose weight is > threshold (NaN counts) into d_bits.  Reads lo /
+// inv_cell / dims of `grid` only.  No allocation, no synchronisation.
+extern "C" int dmnerf_skip_grid_mark(const dmnerf_skip_grid* grid, uint32_t* d_bits, const float* d_rays_o, const float* d_rays_d,
+                                     const float* d_z, const float* d_weights, int64_t N, int S, float threshold, void* stream) {
+    if (!grid) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: null grid");
+    if (int rc = dmn_check_rays("skip_grid_mark", 1, N, S, true)) return rc;          // (no network here: ins_num 1 always passes)
+    if (!(threshold >= 0.f)) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: threshold %g must be >= 0", (double)threshold);
+    CellDev G;
+    int64_t cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (grid->dims[a] < 1) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: bad grid dims");
+        G.lo[a] = grid->lo[a]; G.inv_cell[a] = grid->inv_cell[a]; G.dims[a] = grid->dims[a];
+        cells *= grid->dims[a];
+        if (cells >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: the cells do not fit int32");
+    }
+    if (!d_bits || !d_rays_o || !d_rays_d || !d_z || !d_weights) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: null pointer");
+    if (N == 0) return DMNERF_OK;
+    const int64_t M = N * S;
+    hipLaunchKernelGGL(skip_mark_kernel, dim3((unsigned)((M + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, G, d_rays_o,
+                       d_rays_d, d_z, d_weights, M, S, threshold, d_bits);
+    return dmn_check_launch("skip_grid_mark");
+}
+
+extern "C" int dmnerf_skip_grid_dilate(const uint32_t* d_bits_in, int dx, int dy, int dz, int dilate, uint32_t* d_bits_out,
+                                       void* stream) {
+    if (dx < 1 || dy < 1 || dz < 1) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: bad dims %d x %d x %d", dx, dy, dz);
+    if (dilate < 0 || dilate > MAX_DILATE) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: dilate %d outside 0..%d", dilate, MAX_DILATE);
+    const int64_t total = (int64_t)dx * dy * dz;
+    if (total >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: %lld cells do not fit int32", (long long)total);
+    if (!d_bits_in || !d_bits_out) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: null pointer");
+    if (d_bits_in == d_bits_out) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: in and out must be different buffers");
+    const int D = 2 * dilate + 1;
+    const size_t lds = (size_t)D * D * (BLOCK + 2 * dilate);   // <= 81 * 264 B
+    hipLaunchKernelGGL(skip_grid_dilate_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), lds, (hipStream_t)stream,
+                       d_bits_in, dx, dy, dz, dilate, d_bits_out);
+    return dmn_check_launch("skip_grid_dilate");
 }

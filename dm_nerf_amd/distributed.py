@@ -368,6 +368,13 @@ def _skip_render_chunk(rays_o, rays_d, z, models, args, events=None, grid=None, 
     return out['rgb_fine'], out['ins_fine'], out['depth_fine']
 
 
+def _mark_render_chunk(rays_o, rays_d, z, models, args, events=None, grid=None, threshold=0.0, levels=("coarse", "fine")):
+    from .networks import render
+    out = render.dm_nerf_fine_mark(torch.stack([rays_o, rays_d]), None, None, models[0], models[1], z, args, grid, threshold=threshold,
+                                   levels=levels, _events=events)
+    return out['rgb_fine'], out['ins_fine'], out['depth_fine']
+
+
 _compact_index_cache = {}
 
 
@@ -401,7 +408,7 @@ class FrameRenderer:
 
     def __init__(self, H, W, K, c2w, models, near, far, args, chunk=4096, n_samples=64,
                  raygen=None, render_chunk=None, z_fn=None, labels_only=False, label_conf=None, ins_num=None, dtype=None,
-                 skip=None, skip_levels=("coarse", "fine")):
+                 skip=None, skip_levels=("coarse", "fine"), mark=None, mark_threshold=0.0, mark_levels=("coarse", "fine")):
         self.rank, self.world = world_info()
         self.dtype = dtype                                         # band dtype (default f32, what every kernel writes)
         self.H, self.W, self.models, self.args, self.chunk = int(H), int(W), models, args, int(chunk)
@@ -413,6 +420,15 @@ class FrameRenderer:
                 raise ValueError("FrameRenderer: skip= routes the chunks through dm_nerf_fine_skip; it cannot be combined with render_chunk=")
             import functools
             render_chunk = functools.partial(_skip_render_chunk, grid=skip, levels=skip_levels)
+        if mark is not None:
+            # mark = a field.SkipGrid: the chunks go through render.dm_nerf_fine_mark -- the dense render, which also sets in the grid
+            # the cells of the samples it gave a weight > mark_threshold.  This rank marks the rows of its own band.
+            if skip is not None:
+                raise ValueError("FrameRenderer: mark= records what a DENSE render uses; it cannot be combined with skip=")
+            if render_chunk is not None:
+                raise ValueError("FrameRenderer: mark= routes the chunks through dm_nerf_fine_mark; it cannot be combined with render_chunk=")
+            import functools
+            render_chunk = functools.partial(_mark_render_chunk, grid=mark, threshold=mark_threshold, levels=mark_levels)
         self.render_chunk = render_chunk or _default_render_chunk
         if z_fn is None:
             from .networks import helpers
@@ -488,7 +504,7 @@ class FrameRenderer:
 
 def render_frame(H, W, K, c2w, models, near, far, args, chunk=4096, n_samples=64,
                  raygen=None, render_chunk=None, z_fn=None, labels_only=False, label_conf=None, ins_num=None,
-                 skip=None, skip_levels=("coarse", "fine")):
+                 skip=None, skip_levels=("coarse", "fine"), mark=None, mark_threshold=0.0, mark_levels=("coarse", "fine")):
     """Full-frame render, rows sharded over ranks, ONE all-gather per frame (``FrameRenderer``).
 
     Mirrors the per-pose body of ``render_test`` (networks/tester.py:58-85): same chunking
@@ -499,10 +515,14 @@ def render_frame(H, W, K, c2w, models, near, far, args, chunk=4096, n_samples=64
     before the gather, and ``(rgb, label, conf, depth)`` is returned: 24 instead of 16 + 4*ins_num bytes per pixel cross the links.
     ``skip=`` a ``field.SkipGrid``: every chunk is rendered by ``render.dm_nerf_fine_skip`` at ``skip_levels`` (opt-in; samples in
     empty cells are not evaluated).  ``render_path(..., skip=grid)`` hands it through.
+    ``mark=`` a ``field.SkipGrid``: every chunk is rendered by ``render.dm_nerf_fine_mark`` -- the frame is the dense one, bit for bit
+    -- and the cells of the samples whose weight is ``> mark_threshold`` at ``mark_levels`` are set in the grid, in place; each rank
+    marks the rows of its own band (``field.SkipGrid.from_views`` combines the ranks).  Not with ``skip=`` or ``render_chunk=``
+    (``ValueError``).  ``render_path(..., mark=grid)`` hands it through.
     """
     fr = FrameRenderer(H, W, K, c2w, models, near, far, args, chunk=chunk, n_samples=n_samples, raygen=raygen,
                        render_chunk=render_chunk, z_fn=z_fn, labels_only=labels_only, label_conf=label_conf, ins_num=ins_num,
-                       skip=skip, skip_levels=skip_levels)
+                       skip=skip, skip_levels=skip_levels, mark=mark, mark_threshold=mark_threshold, mark_levels=mark_levels)
     for i in range(fr.n_chunks):
         fr.step(i)
     return fr.gather()

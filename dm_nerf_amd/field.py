@@ -414,6 +414,20 @@ def _dims3(dims):
     return dims
 
 
+def or_gathered_words(gathered, world):
+    """The bitwise OR over ranks of ``gathered [world * n_words]`` (the ranks' packed words, concatenated as
+    ``distributed.all_gather_cat`` returns them) -> ``[n_words]``, same dtype and device.  Plain torch ops: the collective library
+    offers no bitwise reduction, so the reduction is local; a 128^3 grid is 256 KB per rank."""
+    world = int(world)
+    if world < 1 or gathered.dim() != 1 or gathered.shape[0] % world:
+        raise ValueError(f"or_gathered_words: {tuple(gathered.shape)} words do not split over {world} ranks")
+    parts = gathered.reshape(world, -1)
+    out = parts[0].clone()
+    for r in range(1, world):
+        out |= parts[r]
+    return out
+
+
 class SkipGrid:
     """An axis-aligned box ``[lo, hi)`` in world coordinates, ``dims = (dx, dy, dz)`` cells, one bit per cell: set = the cell may hold
     density, clear = a sample in it is not worth a network evaluation (``render.dm_nerf_fine_skip``).
@@ -522,6 +536,87 @@ class SkipGrid:
             i1 = min(i0 + step, dx)
             sigma[i0:i1] = query_density(model_fine, g.cell_centres(i0, i1), fuse_heads=fuse_heads).reshape(i1 - i0, dy, dz)
         return cls.from_sigma(sigma, lo, hi, threshold=threshold, dilate=dilate, outside=outside)
+
+    # ---- the grid from rendered views (dmnerf_skip_grid_mark / dmnerf_skip_grid_dilate; tests/_mark_restate.py states them in numpy)
+    def _check_same(self, other, who):
+        if not isinstance(other, SkipGrid):
+            raise TypeError(f"SkipGrid.{who}: the other operand must be a SkipGrid")
+        if (self.dims != other.dims or not np.array_equal(self.lo, other.lo) or not np.array_equal(self.hi, other.hi)
+                or self.outside != other.outside):
+            raise ValueError(f"SkipGrid.{who}: the two grids must have the same box, dims and outside policy")
+        if self.bits.device != other.bits.device:
+            raise RuntimeError(f"SkipGrid.{who}: the two grids live on different devices")
+
+    def copy(self):
+        """A grid with the same box, dims and policy and its own copy of the bits."""
+        return SkipGrid(self.lo, self.hi, self.dims, self.bits.clone(), self.outside)
+
+    def __or__(self, other):
+        """Cells set in either grid (same box, dims and ``outside`` required, else ``ValueError``); ``empty`` is neutral."""
+        self._check_same(other, "__or__")
+        return SkipGrid(self.lo, self.hi, self.dims, self.bits | other.bits, self.outside)
+
+    def __ior__(self, other):
+        self._check_same(other, "__ior__")
+        self.bits |= other.bits                      # in place: a captured render sees the new bits on its next replay
+        return self
+
+    def mark(self, rays_o, rays_d, z, weights, threshold=0.0):
+        """Sets, in place, the cell of every sample ``p = o + d z`` that lies inside the box and whose compositing weight is
+        ``> threshold`` (NaN counts); returns ``self``.  ``rays_o``, ``rays_d`` ``[N, 3]``, ``z`` and ``weights`` ``[N, S]``, f32 on
+        the grid's device.  Bits are only ever set, samples outside the box mark nothing, and ``outside`` plays no part.  The cell
+        arithmetic is the select's, so a sample this call marks is a sample ``dm_nerf_fine_skip`` evaluates.  One launch
+        (``dmnerf_skip_grid_mark``), no allocation, no synchronisation: it can be captured in a graph."""
+        threshold = float(threshold)
+        if not threshold >= 0.0:
+            raise ValueError(f"SkipGrid.mark: threshold must be >= 0, got {threshold}")
+        for name, t in (("rays_o", rays_o), ("rays_d", rays_d), ("z", z), ("weights", weights)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32:
+                raise ValueError(f"SkipGrid.mark: {name} must be a float32 tensor")
+        _lib.require_gpu(rays_o, rays_d, z, weights)
+        if z.dim() != 2 or weights.shape != z.shape or tuple(rays_o.shape) != (z.shape[0], 3) or rays_d.shape != rays_o.shape:
+            raise ValueError(f"SkipGrid.mark expects rays_o, rays_d [N, 3] and z, weights [N, S], got {tuple(rays_o.shape)}, "
+                             f"{tuple(rays_d.shape)}, {tuple(z.shape)}, {tuple(weights.shape)}")
+        if any(t.device != self.bits.device for t in (rays_o, rays_d, z, weights)):
+            raise RuntimeError("SkipGrid.mark: the grid lives on another device than the samples")
+        N, S = z.shape
+        if N * S >= 2 ** 31:
+            raise ValueError(f"SkipGrid.mark: {N * S} samples do not fit int32; mark in smaller chunks")
+        if N * S == 0:
+            return self
+        g = self.c_struct()
+        _lib.check(_lib.load().dmnerf_skip_grid_mark(ctypes.byref(g), _lib.ptr(self.bits), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z),
+                                                     _lib.ptr(weights), N, S, threshold, _lib.stream()), "dmnerf_skip_grid_mark")
+        return self
+
+    def dilated(self, r):
+        """A new grid, same box and ``outside``: a cell is set iff any cell of its ``(2 r + 1)^3`` neighbourhood, clipped at the faces,
+        is set here (``0 <= r <= 4``; ``dmnerf_skip_grid_dilate``).  ``from_sigma(s, dilate=0).dilated(r)`` is ``from_sigma(s, dilate=r)``."""
+        out = SkipGrid.empty(self.lo, self.hi, self.dims, self.outside, self.bits.device)
+        dx, dy, dz = self.dims
+        _lib.check(_lib.load().dmnerf_skip_grid_dilate(_lib.ptr(self.bits), dx, dy, dz, int(r), _lib.ptr(out.bits), _lib.stream()),
+                   "dmnerf_skip_grid_dilate")
+        return out
+
+    @classmethod
+    def from_views(cls, poses, hwk, models, args, lo, hi, dims=128, threshold=0.0, dilate=0, levels=("coarse", "fine"), chunk=4096,
+                   outside="evaluate"):
+        """From renders: every pose of ``poses`` is rendered dense through ``distributed.render_frame(..., mark=grid)`` (near, far and
+        ``N_samples`` from ``args``, chunks of ``chunk`` rays) and the cell of every sample whose weight is ``> threshold`` is set, at
+        the levels named in ``levels``; then ``dilated(dilate)``.  With ``threshold = 0`` and ``outside="evaluate"``, re-rendering the
+        same views through the grid gives the dense frames bit for bit ("The grid from rendered views").  Nothing
+        touches the host.  With more than one rank every rank marks its own band of rows; the words are then all-gathered and OR-ed
+        locally (``or_gathered_words``: the collective library has no bitwise reduction), so every rank returns the same grid."""
+        from . import distributed as D
+        H, W, K = hwk
+        g = cls.empty(lo, hi, dims, outside, next(models[1].parameters()).device)
+        for c2w in poses:
+            D.render_frame(H, W, K, c2w, models, args.near, args.far, args, chunk=chunk, n_samples=int(getattr(args, "N_samples", 64)),
+                           mark=g, mark_threshold=threshold, mark_levels=levels)
+        _, world = D.world_info()
+        if D._active(world):
+            g.bits.copy_(or_gathered_words(D.all_gather_cat(g.bits), world))
+        return g.dilated(dilate)
 
     def unpack(self):
         """The bits as a bool tensor ``[dx, dy, dz]`` on the device."""

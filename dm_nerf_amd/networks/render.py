@@ -423,3 +423,41 @@ def dm_nerf_fine_skip(rays, position_embedder, view_embedder, model_coarse, mode
     if getattr(args, "is_train", False) and getattr(args, "N_ins", None) is not None:
         out['ins_fine'] = out['ins_fine'][-args.N_ins:]          # render.py:88-90
     return out
+
+
+def dm_nerf_fine_mark(rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args, grid, threshold=0.0,
+                      levels=("coarse", "fine"), t_rand=None, u=None, _events=None):
+    """``dm_nerf_fine`` (or, with ``args.mfma_split = "f16x2"``, ``dm_nerf_fine_f16``) that also records in ``grid`` (a
+    ``field.SkipGrid``, marked in place) which cells the render used: the cell of every sample whose compositing weight is
+    ``> threshold``.  The render is the dense one, unchanged -- the same ``dmnerf_render_rays_fwd_fine`` call -- so the returned keys
+    are ``torch.equal`` to ``dm_nerf_fine``'s.
+
+    ``"fine"`` in ``levels``: marked with ``z_vals_fine`` and the fine weights the compositing left in its workspace.  ``"coarse"``:
+    the coarse weights are recomputed from the coarse density the render left behind (``dmnerf_weights_from_sigma``, the kernel the
+    render itself ran, on the same inputs: these are the weights the resampler saw) into a scratch of this call, and marked with the
+    coarse depths the networks saw -- the jittered ones when ``args.perturb > 0``.  Nothing reaches the host and nothing is allocated
+    between the launches, so the call can be captured in a graph.  Serves the calls ``dm_nerf_fine_skip`` serves; anything else raises."""
+    from .. import field
+    if not isinstance(grid, field.SkipGrid):
+        raise TypeError("dm_nerf_fine_mark: grid must be a field.SkipGrid")
+    levels = check_skip_levels("dm_nerf_fine_mark", levels)
+    out, a, keep = _fine_prepare("dm_nerf_fine_mark", rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse,
+                                 args, t_rand, u, _events, modes=("f32", "f16x2"))
+    rays_o, rays_d, z_c, sigma, ws = keep[0], keep[1], keep[5], keep[6], keep[7]
+    if grid.bits.device != rays_o.device:
+        raise RuntimeError("dm_nerf_fine_mark: the grid lives on another device than the rays")
+    N, S = z_c.shape
+    w_c = torch.empty(N, S, dtype=torch.float32, device=rays_o.device) if "coarse" in levels else None
+    lib = _lib.load()
+    _lib.check(lib.dmnerf_render_rays_fwd_fine(ctypes.byref(a), _lib.stream()), "dmnerf_render_rays_fwd_fine")
+    if "fine" in levels:
+        grid.mark(rays_o, rays_d, out['z_vals_fine'], ws, threshold)
+    if w_c is not None and N:
+        _lib.check(lib.dmnerf_weights_from_sigma(_lib.ptr(sigma), _lib.ptr(z_c), _lib.ptr(rays_d), N, S, _lib.ptr(w_c), _lib.stream()),
+                   "dmnerf_weights_from_sigma")
+        grid.mark(rays_o, rays_d, z_c, w_c, threshold)
+    if a.fused_heads == 3:
+        _f16_probe(model_coarse, model_fine, args, keep, out)
+    if getattr(args, "is_train", False) and getattr(args, "N_ins", None) is not None:
+        out['ins_fine'] = out['ins_fine'][-args.N_ins:]          # render.py:88-90
+    return out

@@ -699,6 +699,25 @@ typedef struct {
 } dmnerf_render_fine_skip_args;
 int dmnerf_render_rays_fwd_fine_skip(const dmnerf_render_fine_skip_args* args, void* stream);
 
+/* The grid from rendered views instead of from the density at the cell centres (csrc/skip.hip): a cell is worth evaluating if, in
+ * some view of interest, a sample in it received a compositing weight (networks/render.py:6-20) above a threshold.  A dense render
+ * leaves what this needs on the device: the fine weights in d_weights_ws, the coarse sigma in d_sigma_ws (-> dmnerf_weights_from_sigma).
+ * Additive (the ABI version stays).
+ *   dmnerf_skip_grid_mark: sample m = n * S + s takes the cell of p = o + d * z (networks/render.py:49) with dmnerf_skip_select's
+ *     arithmetic, operation for operation; if p is inside the box and !(d_weights[m] <= threshold) the cell's bit is OR-ed into
+ *     d_bits (so a NaN weight marks, as NaN sigma does in the build).  Samples outside the box mark nothing.  Only lo / inv_cell /
+ *     dims of `grid` are read -- not grid->outside, not grid->d_bits; d_bits is the writable pointer to the same
+ *     ceil(cells / 32) words.  Bits are only ever set: what was set stays, the unused bits of the last word stay 0.  The one
+ *     atomic of the file (atomicOr, issued only where the bit still reads clear); OR commutes, so the words are the same every run.
+ *     d_z, d_weights [N,S].  N * S < 2^31, S >= 1, threshold >= 0 (NaN refused); N == 0 returns 0 without a launch.  Nothing is
+ *     allocated and nothing synchronises: the call can be captured in a graph.
+ *   dmnerf_skip_grid_dilate: out(g) = OR of in over the (2 dilate + 1)^3 neighbourhood of g, clipped at the faces -- the dilation
+ *     of dmnerf_skip_grid_build with a set bit as the predicate instead of sigma > threshold.  0 <= dilate <= 4; the unused bits
+ *     of the last word are written 0; d_bits_in == d_bits_out is refused. */
+int dmnerf_skip_grid_mark(const dmnerf_skip_grid* grid, uint32_t* d_bits, const float* d_rays_o, const float* d_rays_d,
+                          const float* d_z, const float* d_weights, int64_t N, int S, float threshold, void* stream);
+int dmnerf_skip_grid_dilate(const uint32_t* d_bits_in, int dx, int dy, int dz, int dilate, uint32_t* d_bits_out, void* stream);
+
 /* The two renders above on the OPT-IN split-f16 ("f16x2") kernels (csrc/mlp_f16_density.hip, csrc/mlp_f16_sparse.hip; the body of
  * csrc/mlp_f16_impl.h with template flags).  Additive (the ABI version stays).
  *   f16 density blob: dmnerf_blob_f16_density_words 32-bit words = [the f16 blob's 4096-float bias table | its 120 trunk groups
