@@ -6,6 +6,7 @@
     :233-339             the evaluation's pose loop with PSNR / SSIM / AP             ->  ``manipulate_eval_path``
     :472-488, :310-323   8-bit frame, label, label mask, coloured object image        ->  ``frame_products``, ``label_lut``
     (extension)          remove, duplicate, isolate: entries next to matrices / ``Deform``  ->  ``Remove``, ``Copy``, ``keep_labels=``
+    tools/pose_generator.py:67-77   a matrix about a centre; the centre from a ``field.LabelGrid``  ->  ``about``, ``object_centre``
 
 The frames are rendered by ``distributed.ManipulationFrameRenderer`` (rows sharded over the ranks, one all-gather per frame); the
 products are computed from the gathered frame's packed buffer in place (csrc/edit_frame.hip), so 7 bytes per pixel leave the
@@ -103,6 +104,35 @@ class Copy:
 def edit_kind(trans):
     """The exchange kind of a ``trans_list`` entry: ``networks.manipulator.MOVE`` / ``COPY`` / ``REMOVE``."""
     return 2 if isinstance(trans, Remove) else 1 if isinstance(trans, Copy) else 0
+
+
+def about(matrix, centre):
+    """``matrix`` (4 x 4: a rotation, a scale, any product of them) applied about ``centre [3]`` instead of the origin -> the float64
+    4 x 4 ``T(centre) @ matrix @ T(-centre)``, a ``trans_list`` entry.  The arithmetic of tools/pose_generator.py:67-77: the two
+    translations are float32 ``np.eye`` matrices (the centre is rounded to f32 once), the product is float64."""
+    matrix = np.asarray(matrix, dtype=np.float64)
+    centre = np.asarray(centre, dtype=np.float64).reshape(-1)
+    if matrix.shape != (4, 4) or centre.shape != (3,):
+        raise ValueError(f"about: expected a 4 x 4 matrix and a centre [3], got {matrix.shape} and {centre.shape}")
+    translation = np.eye(4, 4, dtype=np.float32)
+    translation[:3, -1] = -1 * centre
+    translation_inverse = np.eye(4, 4, dtype=np.float32)
+    translation_inverse[:3, -1] = -1 * translation[:3, -1]
+    return translation_inverse @ matrix @ translation
+
+
+def object_centre(label_grid_or_stats, label):
+    """The centre of object ``label`` -> numpy float64 ``[3]``: row ``label`` of ``stats()["centre"]`` of a ``field.LabelGrid`` (or of
+    the dict ``stats()`` returned), the mean of the centres of the cells the object owns.  This is the one host read of the label
+    grid: one copy of four numbers.  ``ValueError`` if the object owns no cell or ``label`` is not a row of the stats."""
+    stats = label_grid_or_stats if isinstance(label_grid_or_stats, dict) else label_grid_or_stats.stats()
+    label = int(label)
+    if not 0 <= label < stats["count"].shape[0]:
+        raise ValueError(f"object_centre: label {label} outside [0, {stats['count'].shape[0]})")
+    row = torch.cat([stats["count"][label].double().reshape(1), stats["centre"][label]]).cpu().numpy()
+    if row[0] == 0:
+        raise ValueError(f"object_centre: object {label} owns no cell of the label grid")
+    return row[1:].astype(np.float64)
 
 
 def edit_rays(H, W, K, poses, kinds, offsets=None, row0=0, nrows=None, device=None):

@@ -626,3 +626,148 @@ class SkipGrid:
     def occupancy(self):
         """Fraction of set cells (a device scalar)."""
         return self.unpack().float().mean()
+
+
+# ---- the occupancy volume labelled by object (csrc/label_grid.hip; tests/_label_grid_restate.py states it in numpy)
+UNLABELLED = 255
+MAX_LABELS = 128                # DMNERF_MAX_LOGITS (include/dmnerf_hip.h)
+
+
+def label_rays(occ, i0=0, i1=None):
+    """The rays whose samples are the label points of planes ``i0 .. i1 - 1`` of ``occ`` -> ``(o [n, 3], d [n, 3], z [n, dz])`` f32 on the
+    grid's device, ``n = (i1 - i0) dy``: one ray per ``(i, j)`` column, ``o`` = the ``cell_centres`` value of cell ``(i, j, 0)``,
+    ``d = (0, 0, cell_z)``, ``z[n, k] = float(k)``.  The label point of cell ``(i, j, k)`` is DEFINED as the network kernels'
+    ``o + d z`` in f32 (multiply, then add, each rounded): x and y are the centre's exactly, z is ``centre_z(0) + cell_z k``, which may
+    differ from ``cell_centres``' ``(k + 0.5) cell_z + lo_z`` in the last bits.  Device ops only."""
+    dx, dy, dz = occ.dims
+    i1 = dx if i1 is None else int(i1)
+    dev = occ.bits.device
+    ax = [(torch.arange(n0, n1, dtype=torch.float32, device=dev) + 0.5) * float(occ.cell[a]) + float(occ.lo[a])
+          for a, (n0, n1) in enumerate(((int(i0), i1), (0, dy), (0, 1)))]
+    ni = i1 - int(i0)
+    o = torch.stack([ax[0][:, None].expand(ni, dy), ax[1][None, :].expand(ni, dy), ax[2][None, :].expand(ni, dy)], dim=-1).reshape(-1, 3)
+    d = torch.zeros(ni * dy, 3, dtype=torch.float32, device=dev)
+    d[:, 2].fill_(float(occ.cell[2]))
+    z = torch.arange(dz, dtype=torch.float32, device=dev)[None, :].expand(ni * dy, dz).contiguous()
+    return o, d, z
+
+
+def label_mask_words(labels, C):
+    """``labels`` (an int or an iterable of ints in ``[0, C)``, else ``ValueError``) as the four 32-bit words
+    ``dmnerf_skip_grid_from_labels`` takes: ``networks.manipulator.keep_words``' two 64-bit words, little end first."""
+    from .networks.manipulator import keep_words
+    if isinstance(labels, (int, np.integer)):
+        labels = [labels]
+    try:
+        labels = list(labels)
+    except TypeError:
+        raise ValueError(f"labels must be an int or an iterable of ints, got {labels!r}") from None
+    for l in labels:
+        if not isinstance(l, (int, np.integer)):
+            raise ValueError(f"label {l!r} is not an integer")
+    w = keep_words(labels, C)
+    return [w[0] & 0xffffffff, w[0] >> 32, w[1] & 0xffffffff, w[1] >> 32]
+
+
+def _check_label_points(occ):
+    """Host arithmetic on ``dx + dy + dz`` floats: every label point lies in its own cell under ``SkipGrid``'s cell arithmetic (it
+    does unless the box sits so far from the origin that f32 cannot resolve half a cell)."""
+    f = np.float32
+    for a in range(3):
+        idx = np.arange(occ.dims[a], dtype=f)
+        if a < 2:
+            p = ((idx + f(0.5)) * occ.cell[a] + occ.lo[a]).astype(f)
+        else:
+            p = ((f(0.5) * occ.cell[a] + occ.lo[a]).astype(f) + (occ.cell[a] * idx).astype(f)).astype(f)
+        c = np.floor(((p - occ.lo[a]).astype(f) * occ.inv_cell[a]).astype(f))
+        if not np.array_equal(c, idx):
+            raise ValueError(f"label_grid: float32 cannot place the label points of axis {a} in their cells (box {occ.lo} .. {occ.hi}, "
+                             f"dims {occ.dims})")
+
+
+def label_grid(model_fine, occ, sigma_threshold=0.0, slab=1 << 20, split=None):
+    """Which object owns each cell of ``occ`` (a ``SkipGrid``) -> ``LabelGrid`` with its box and dims: the fine network at the label
+    point of every set cell (``label_rays``), through ``render.run_network_skip`` -- clear cells get the empty row and are not
+    evaluated -- then ``dmnerf_label_cells``: the first index of the maximum of all ``C = ins_num + 1`` logits where
+    ``sigma > sigma_threshold``, else 255.  Label ``C - 1`` is the field's own "empty" class.  The label points lie inside the box, so
+    ``occ.outside`` plays no part.  In slabs of whole i-planes of about ``slab`` cells; nothing reaches the host, so after one warm-up
+    call it can be captured in a graph and follows ``occ.bits`` on replay.  ``split``, the network shape and device errors are what
+    ``run_network_skip`` raises; ``sigma_threshold < 0`` or NaN raises ``ValueError``."""
+    sigma_threshold = float(sigma_threshold)
+    if not sigma_threshold >= 0.0:
+        raise ValueError(f"label_grid: sigma_threshold must be >= 0, got {sigma_threshold}")
+    if not isinstance(occ, SkipGrid):
+        raise TypeError("label_grid: occ must be a SkipGrid")
+    slab = int(slab)
+    if slab < 1:
+        raise ValueError("slab must be >= 1")
+    _check_label_points(occ)
+    dx, dy, dz = occ.dims
+    C = model_fine.ins_num + 1
+    labels = torch.empty(dx, dy, dz, dtype=torch.uint8, device=occ.bits.device)
+    fn, step = _lib.load().dmnerf_label_cells, max(1, slab // (dy * dz))
+    for i0 in range(0, dx, step):
+        i1 = min(i0 + step, dx)
+        o, d, z = label_rays(occ, i0, i1)
+        raw = R.run_network_skip(model_fine, o, d, z, occ, split=split)
+        _lib.check(fn(_lib.ptr(raw), (i1 - i0) * dy * dz, C, sigma_threshold, _lib.ptr(labels[i0:i1]), _lib.stream()), "dmnerf_label_cells")
+    return LabelGrid(labels, occ.lo, occ.hi, C)
+
+
+class LabelGrid:
+    """``labels``: uint8 ``[dx, dy, dz]`` on the device over the box ``[lo, hi)`` of a ``SkipGrid`` (same ``cell`` arithmetic): the object
+    that owns each cell, ``0 .. C - 1``, or 255 for none.  ``C`` is the number of labels the reductions cover."""
+
+    def __init__(self, labels, lo, hi, C):
+        _lib.require_gpu(labels)
+        if labels.dtype != torch.uint8 or labels.dim() != 3:
+            raise ValueError(f"LabelGrid: labels must be uint8 [dx, dy, dz], got {labels.dtype} {tuple(labels.shape)}")
+        self.dims = _dims3(tuple(labels.shape))
+        self.C = int(C)
+        if not 1 <= self.C <= MAX_LABELS:
+            raise ValueError(f"LabelGrid: C must be in [1, {MAX_LABELS}], got {self.C}")
+        self.lo = np.asarray(lo, dtype=np.float32).reshape(3)
+        self.hi = np.asarray(hi, dtype=np.float32).reshape(3)
+        if not np.all(self.hi > self.lo):
+            raise ValueError("LabelGrid: hi must be > lo on every axis")
+        self.cell = (self.hi - self.lo) / np.asarray(self.dims, dtype=np.float32)
+        self.labels = labels
+
+    @classmethod
+    def from_labels(cls, labels, lo, hi, C=MAX_LABELS):
+        """Wraps a given uint8 volume ``[dx, dy, dz]`` on the device.  ``C``: labels ``>= C`` count as unlabelled."""
+        return cls(labels, lo, hi, C)
+
+    def stats(self):
+        """What every object covers -> a dict of device tensors, row ``l`` for label ``l < C``:
+
+        ``count [C]`` int64 cells, ``index_sum [C, 3]`` int64 sums of their ``(i, j, k)``, ``lo_idx`` / ``hi_idx [C, 3]`` int32 smallest
+        index and largest index + 1 per axis (``dims`` and 0 for a label without a cell) -- ``dmnerf_label_stats``, integer atomics
+        only, the same every run -- and in float64 from them: ``centre [C, 3] = lo + (index_sum / count + 0.5) cell``, the mean of the
+        cell centres (NaN where ``count == 0``), ``box_lo`` / ``box_hi [C, 3] = lo + idx cell``, and ``volume [C] = count cell_x cell_y
+        cell_z``, the volume of the object's cells.  Nothing reaches the host."""
+        dev, C = self.labels.device, self.C
+        dx, dy, dz = self.dims
+        count = torch.empty(C, dtype=torch.int64, device=dev)
+        index_sum = torch.empty(C, 3, dtype=torch.int64, device=dev)
+        lo_idx = torch.empty(C, 3, dtype=torch.int32, device=dev)
+        hi_idx = torch.empty(C, 3, dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().dmnerf_label_stats(_lib.ptr(self.labels), dx, dy, dz, C, _lib.ptr(count), _lib.ptr(index_sum),
+                                                  _lib.ptr(lo_idx), _lib.ptr(hi_idx), _lib.stream()), "dmnerf_label_stats")
+        n = count.double()
+        lo, cell = self.lo.astype(np.float64), self.cell.astype(np.float64)
+        # (python scalars, not a host tensor: no host-to-device copy, so the call can be captured)
+        per_axis = lambda idx, plus: torch.stack([(idx[:, a] + plus) * float(cell[a]) + float(lo[a]) for a in range(3)], dim=-1)
+        return {"count": count, "index_sum": index_sum, "lo_idx": lo_idx, "hi_idx": hi_idx,
+                "centre": per_axis(index_sum.double() / n[:, None], 0.5),
+                "box_lo": per_axis(lo_idx.double(), 0.0), "box_hi": per_axis(hi_idx.double(), 0.0),
+                "volume": n * float(cell[0] * cell[1] * cell[2])}
+
+    def skip_grid(self, labels, dilate=0, outside="evaluate"):
+        """The cells owned by ``labels`` (an int or an iterable of ints in ``[0, C)``, else ``ValueError``) as a ``SkipGrid`` over the
+        same box: ``dmnerf_skip_grid_from_labels``, then ``dilated(dilate)``.  An unlabelled cell is never set."""
+        mask = (ctypes.c_uint32 * 4)(*label_mask_words(labels, self.C))
+        g = SkipGrid.empty(self.lo, self.hi, self.dims, outside, self.labels.device)
+        _lib.check(_lib.load().dmnerf_skip_grid_from_labels(_lib.ptr(self.labels), g.n_cells, mask, _lib.ptr(g.bits), _lib.stream()),
+                   "dmnerf_skip_grid_from_labels")
+        return g.dilated(dilate) if int(dilate) else g

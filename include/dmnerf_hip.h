@@ -718,6 +718,32 @@ int dmnerf_skip_grid_mark(const dmnerf_skip_grid* grid, uint32_t* d_bits, const 
                           const float* d_z, const float* d_weights, int64_t N, int S, float threshold, void* stream);
 int dmnerf_skip_grid_dilate(const uint32_t* d_bits_in, int dx, int dy, int dz, int dilate, uint32_t* d_bits_out, void* stream);
 
+/* The occupancy volume labelled by object (csrc/label_grid.hip): which object owns a cell of the box, what every object covers, and
+ * the bit grid of a set of objects.  The network runs in front of these (networks/render.py run_network_skip at one point per cell:
+ * field.label_grid); none of the three allocates or synchronises, so the chain can be captured in a graph.  Additive (the ABI
+ * version stays).
+ *   dmnerf_label_cells: one sample per lane.  d_labels[m] = the first index of the maximum of d_raw[m, 4 : 4 + C] if
+ *     d_raw[m, 3] > sigma_threshold, else 255 (unlabelled).  The comparison is exactly that: a NaN sigma is unlabelled, and so is
+ *     the empty row (sigma 0).  The argmax is dmnerf_ins_label_conf's: best = 0, and channel c > 0 replaces it iff x[c] > x[best];
+ *     ties go to the first channel, a NaN logit in a channel c > 0 is never chosen and a NaN in channel 0 is never replaced
+ *     (label 0).  The exchanger takes the same first-maximum argmax over ALL C logits, behind a sigmoid (networks/manipulator.py:18-20;
+ *     monotone, so the two agree unless two unequal logits round to one f32 sigmoid -- both above ~17, where the exchanger keeps
+ *     the first): a cell labelled k is a cell whose centre sample the manipulation render treats as object k.  1 <= C <= 128,
+ *     sigma_threshold >= 0 (NaN refused), M == 0 returns 0 without a launch.
+ *   dmnerf_label_stats: over d_labels [dx,dy,dz] (cell (i,j,k) at (i * dy + j) * dz + k), per label l < C: d_count [C] = number of
+ *     cells, d_index_sum [C,3] = sums of their i, j, k, d_lo [C,3] = smallest index per axis, d_hi [C,3] = largest index + 1.  The
+ *     call initialises the outputs itself (count 0, sums 0, lo = dims, hi = 0: what a label without a cell keeps).  Labels >= C,
+ *     255 included, are ignored.  Integer atomics only (LDS table per workgroup, then atomicAdd / atomicMin / atomicMax): the same
+ *     result every run.  1 <= C <= 128, dx dy dz < 2^31.
+ *   dmnerf_skip_grid_from_labels: bit g of d_bits [ceil(n_cells / 32)] (the packing of dmnerf_skip_grid) is set iff
+ *     d_labels[g] < 128 and bit d_labels[g] of the 128-bit `mask` is set: label l is bit l & 31 of mask[l >> 5], a HOST array --
+ *     the two 64-bit words of networks/manipulator.py keep_words, little end first.  Every word is written, the unused bits of the
+ *     last one 0; no atomics.  1 <= n_cells < 2^31. */
+int dmnerf_label_cells(const float* d_raw, int64_t M, int C, float sigma_threshold, uint8_t* d_labels, void* stream);
+int dmnerf_label_stats(const uint8_t* d_labels, int dx, int dy, int dz, int C, int64_t* d_count, int64_t* d_index_sum, int32_t* d_lo,
+                       int32_t* d_hi, void* stream);
+int dmnerf_skip_grid_from_labels(const uint8_t* d_labels, int64_t n_cells, const uint32_t mask[4], uint32_t* d_bits, void* stream);
+
 /* The two renders above on the OPT-IN split-f16 ("f16x2") kernels (csrc/mlp_f16_density.hip, csrc/mlp_f16_sparse.hip; the body of
  * csrc/mlp_f16_impl.h with template flags).  Additive (the ABI version stays).
  *   f16 density blob: dmnerf_blob_f16_density_words 32-bit words = [the f16 blob's 4096-float bias table | its 120 trunk groups

@@ -1,0 +1,104 @@
+"""numpy restatement of the label grid of ``dm_nerf_amd.field`` / csrc/label_grid.hip: the label of a network row, the per-object
+reduction with the quantities ``LabelGrid.stats()`` derives from it, the bits of a set of labels, and the rays whose samples are the
+label points.  Loops and array ops only: nothing here shares code with the product."""
+import numpy as np
+
+import _skip_restate as RS
+
+F = np.float32
+UNLABELLED = 255
+
+
+def label_row(row, C, sigma_threshold):
+    """One row ``[4 + C]`` -> its label.  ``sigma > threshold`` exactly so (false for a NaN sigma), else 255.  The argmax is the walk
+    of ``dmnerf_ins_label_conf``: best = 0; channel ``c > 0`` replaces it iff ``x[c] > x[best]``.  So ties keep the first channel, a
+    NaN in a channel ``c > 0`` is never chosen (``NaN > v`` is false) and a NaN in channel 0 is never replaced (``v > NaN`` is false):
+    the label is then 0."""
+    if not (F(row[3]) > F(sigma_threshold)):
+        return UNLABELLED
+    best, bv = 0, F(row[4])
+    for c in range(1, C):
+        v = F(row[4 + c])
+        if v > bv:
+            best, bv = c, v
+    return best
+
+
+def label_cells(raw, C, sigma_threshold=0.0):
+    raw = np.asarray(raw, dtype=F).reshape(-1, 4 + C)
+    with np.errstate(invalid="ignore"):
+        return np.array([label_row(r, C, sigma_threshold) for r in raw], dtype=np.uint8)
+
+
+def label_stats(labels, C):
+    """-> ``count [C]`` int64, ``index_sum [C, 3]`` int64, ``lo_idx`` / ``hi_idx [C, 3]`` int32 (inclusive minimum, exclusive maximum;
+    ``dims`` and 0 for a label without a cell).  Labels ``>= C`` are ignored."""
+    labels = np.asarray(labels, dtype=np.uint8)
+    dims = labels.shape
+    count = np.zeros(C, np.int64)
+    index_sum = np.zeros((C, 3), np.int64)
+    lo = np.tile(np.asarray(dims, np.int32), (C, 1))
+    hi = np.zeros((C, 3), np.int32)
+    for i in range(dims[0]):
+        for j in range(dims[1]):
+            for k in range(dims[2]):
+                l = int(labels[i, j, k])
+                if l >= C:
+                    continue
+                count[l] += 1
+                for a, v in enumerate((i, j, k)):
+                    index_sum[l, a] += v
+                    lo[l, a] = min(lo[l, a], v)
+                    hi[l, a] = max(hi[l, a], v + 1)
+    return count, index_sum, lo, hi
+
+
+def derived(count, index_sum, lo_idx, hi_idx, lo, hi, dims):
+    """float64 from the integers: ``centre = lo + (index_sum / count + 0.5) cell`` (NaN where count is 0), ``box = lo + idx cell``,
+    ``volume = count cell_x cell_y cell_z``; ``lo`` and ``cell`` are the grid's f32 values widened."""
+    lo32, cell32, _ = RS.grid_consts(lo, hi, dims)
+    lo64, cell = lo32.astype(np.float64), cell32.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        centre = lo64 + (index_sum.astype(np.float64) / count.astype(np.float64)[:, None] + 0.5) * cell
+    return {"centre": centre, "box_lo": lo64 + lo_idx.astype(np.float64) * cell, "box_hi": lo64 + hi_idx.astype(np.float64) * cell,
+            "volume": count.astype(np.float64) * (cell[0] * cell[1] * cell[2])}
+
+
+def mask_words(labels):
+    """Label ``l`` -> bit ``l & 31`` of word ``l >> 5`` of four uint32 words."""
+    words = [0, 0, 0, 0]
+    for l in ([labels] if np.ndim(labels) == 0 else labels):
+        words[int(l) >> 5] |= 1 << (int(l) & 31)
+    return words
+
+
+def skip_words(labels, words4):
+    """Bit ``g`` = ``labels[g] < 128`` and bit ``labels[g]`` of the mask; uint32 ``[ceil(n / 32)]``, unused bits 0."""
+    flat = np.asarray(labels, dtype=np.uint8).reshape(-1)
+    keep = np.array([l < 128 and ((words4[l >> 5] >> (l & 31)) & 1) == 1 for l in flat.tolist()], dtype=bool)
+    return RS.pack_bits(keep)
+
+
+def label_rays(lo, hi, dims, i0=0, i1=None):
+    """One ray per ``(i, j)`` column of planes ``i0 .. i1 - 1`` -> ``(o [n, 3], d [n, 3], z [n, dz])`` f32: ``o`` = the centre of cell
+    ``(i, j, 0)``, ``d = (0, 0, cell_z)``, ``z[n, k] = k``.  The label point of cell ``(i, j, k)`` is the kernels' ``o + d z`` in f32
+    (multiply, then add); ASSERTS that this point lies in cell ``(i, j, k)`` under the grid's own cell arithmetic."""
+    dx, dy, dz = dims
+    i1 = dx if i1 is None else i1
+    lo32, cell, inv = RS.grid_consts(lo, hi, dims)
+    cx = ((np.arange(i0, i1, dtype=F) + F(0.5)) * cell[0] + lo32[0]).astype(F)
+    cy = ((np.arange(dy, dtype=F) + F(0.5)) * cell[1] + lo32[1]).astype(F)
+    cz0 = F(F(F(0.5) * cell[2]) + lo32[2])
+    n = (i1 - i0) * dy
+    o = np.zeros((i1 - i0, dy, 3), dtype=F)
+    o[..., 0], o[..., 1], o[..., 2] = cx[:, None], cy[None, :], cz0
+    o = o.reshape(n, 3)
+    d = np.zeros((n, 3), dtype=F)
+    d[:, 2] = cell[2]
+    z = np.tile(np.arange(dz, dtype=F), (n, 1))
+    p = (o[:, None, :] + (d[:, None, :] * z[:, :, None]).astype(F)).astype(F)                     # [n, dz, 3]
+    c = np.floor(((p - lo32).astype(F) * inv).astype(F))
+    ii, jj, kk = np.meshgrid(np.arange(i0, i1), np.arange(dy), np.arange(dz), indexing="ij")
+    want = np.stack([ii, jj, kk], -1).reshape(n, dz, 3).astype(F)
+    assert np.array_equal(c, want), "a label point lies outside its cell"
+    return o, d, z
