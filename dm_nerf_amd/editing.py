@@ -205,6 +205,90 @@ def frame_products(rgb, ins=None, lut=None):
     return rgb8, label, mask, ins_img
 
 
+# ---- the label volume seen from a camera (csrc/label_trace.hip): an object from a pixel, an edit before it is rendered
+def pick(label_grid, H, W, K, pose, pixels, near, far, labels=None):
+    """The object under each pixel of ``pixels`` (an iterable of ``(col, row)``) -> numpy ``label [P]`` uint8, ``t [P]`` f32, ``point
+    [P, 3]`` float64, ``cell [P, 3]`` int64: the first labelled cell of ``label_grid`` (a ``field.LabelGrid``) along the pixel's
+    ``get_rays_k`` ray (``dmnerf_raygen_select``), restricted to ``labels`` (as in ``LabelGrid.trace``).  ``point = o + d t`` in
+    float64, ``cell = (i, j, k)``; a pixel that hits nothing gets label 255, ``t = inf``, a non-finite ``point`` and ``cell = -1``.
+    One host read at the end (eleven numbers per pixel)."""
+    from .networks import helpers
+    H, W = int(H), int(W)
+    pixels = [(int(c), int(r)) for c, r in pixels]
+    for c, r in pixels:
+        if not (0 <= c < W and 0 <= r < H):
+            raise ValueError(f"pick: pixel (col {c}, row {r}) outside the {W} x {H} frame")
+    P = len(pixels)
+    dev = label_grid.labels.device
+    intr, c2w = helpers._camera(K, pose)
+    idx = torch.tensor([r * W + c for c, r in pixels], dtype=torch.int64).to(dev)
+    rays = torch.empty(2, P, 3, dtype=torch.float32, device=dev)
+    if P:
+        _lib.check(_lib.load().dmnerf_raygen_select(H, W, intr.ctypes.data_as(ctypes.c_void_p), c2w.ctypes.data_as(ctypes.c_void_p),
+                                                    _lib.ptr(idx), P, _lib.ptr(rays[0]), _lib.ptr(rays[1]), _lib.stream()),
+                   "dmnerf_raygen_select")
+    out = label_grid.trace(rays[0], rays[1], near, far, labels)
+    host = torch.cat([out["label"].double()[:, None], out["t"].double()[:, None], out["cell"].double()[:, None], rays[0].double(),
+                      rays[1].double()], dim=1).cpu().numpy()                     # the one host read; every value is exact in float64
+    label, t, g = host[:, 0].astype(np.uint8), host[:, 1].astype(np.float32), host[:, 2].astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        point = host[:, 3:6] + host[:, 6:9] * host[:, 1:2]
+    _, dy, dz = label_grid.dims
+    cell = np.where(g[:, None] >= 0, np.stack([g // (dy * dz), (g // dz) % dy, g % dz], axis=1), -1)
+    return label, t, point, cell
+
+
+def preview_frame(label_grid, H, W, K, pose, trans_list=(), target_labels=(), keep_labels=None, near=0.0, far=float("inf"), lut=None):
+    """What an edit does to a frame, from the label volume alone: ``label`` uint8 ``[H, W]`` (255: nothing), ``depth`` f32 ``[H, W]``
+    (the hit's ``t``, ``+inf`` on a miss), ``source`` uint8 ``[H, W]`` (0: the original rays, ``1 + e``: the target rays of the e-th
+    entry WITH rays, 255: nothing) and ``ins_img`` uint8 ``[H, W, 3]`` = ``lut[label]``, black on a miss (``None`` without ``lut``, the
+    table of ``label_lut`` with at least ``C`` rows), all on the device.
+
+    ``trans_list`` / ``target_labels`` / ``keep_labels`` are ``ManipulationFrameRenderer``'s: 4 x 4 matrices, ``Deform``, ``Remove()``,
+    ``Copy(...)``.  The original and target rays ARE that renderer's (``models=None``: same ``trans @ pose``, same ray kernels, same
+    ``Deform`` offsets).  ONE ``dmnerf_label_trace`` with ``R = 1 +`` (entries with rays) sets: set 0, the original rays, accepts
+    every label but those of MOVE and REMOVE entries; set ``1 + e``, the target rays of entry e, accepts ``target_labels[e]`` only;
+    with ``keep_labels`` every set is intersected with it.  This is the exchanger's per-sample rule: along the original ray the moved
+    object's samples are dropped, along the target ray only its own are taken.  A pixel's rays share the ray parameter (a target ray
+    is the original one under an affine map), so the smallest ``t`` over the sets is the nearest surface along the pixel.
+
+    A hard-surface proxy: the first labelled cell, no transmittance, no colour; how well it agrees with ``argmax`` of
+    ``manipulate_frame`` on a trained field is not measured.  Nothing reaches the host: with matrices (the poses are
+    host data) it can be captured in a graph after a warm-up call and follows ``label_grid.labels`` on replay; a ``Deform`` uploads
+    its offset table on every call."""
+    import types
+    H, W = int(H), int(W)
+    C = label_grid.C
+    trans_list, target_labels = list(trans_list), [int(l) for l in target_labels]
+    if len(trans_list) != len(target_labels):
+        raise ValueError(f"preview_frame: {len(target_labels)} target labels for {len(trans_list)} edits")
+    keep = None if keep_labels is None else sorted({int(l) for l in keep_labels})
+    for l in target_labels + (keep or []):
+        if not 0 <= l < C:
+            raise ValueError(f"preview_frame: label {l} outside [0, {C})")
+    kinds = [edit_kind(trans) for trans in trans_list]
+    args = types.SimpleNamespace(N_importance=0, target_labels=target_labels)
+    pose = torch.as_tensor(pose, dtype=torch.float32).cpu()                         # host data: 12 floats into the ray kernels' arguments
+    fr = D.ManipulationFrameRenderer(H, W, K, pose, trans_list, None, args, ins_num=C - 1, rank=0, world=1,
+                                     keep_labels=keep if (keep is not None or trans_list) else ())
+    if fr.ori.device != label_grid.labels.device:
+        raise RuntimeError("preview_frame: the label volume lives on another device than the rays")
+    allowed = set(range(C)) if keep is None else set(keep)
+    gone = {l for l, k in zip(target_labels, kinds) if k != 1}                      # MOVE and REMOVE: not where it was
+    sets = [sorted(allowed - gone)] + [[l] if l in allowed else [] for l, k in zip(target_labels, kinds) if k != 2]
+    rays = torch.cat([fr.ori[None], fr.tar], dim=0) if fr.T else fr.ori[None]
+    out = label_grid.trace_sets(rays, sets, near, far)
+    label = out["label"].reshape(H, W)
+    ins_img = None
+    if lut is not None:
+        _lib.require_gpu(lut)
+        if lut.dtype != torch.uint8 or lut.dim() != 2 or lut.shape[1] != 3 or lut.shape[0] < C:
+            raise ValueError(f"preview_frame: lut must be uint8 [>= {C}, 3], got {lut.dtype} {tuple(lut.shape)}")
+        hit = label != 255
+        ins_img = lut[torch.where(hit, label, torch.zeros_like(label)).long()] * hit[..., None].to(torch.uint8)
+    return {"label": label, "depth": out["t"].reshape(H, W), "source": out["source"].reshape(H, W), "ins_img": ins_img}
+
+
 def _render(H, W, K, pose, edits, models, args, frame_kw):
     fr = D.ManipulationFrameRenderer(H, W, K, pose, edits, models, args, **frame_kw)
     for c in range(fr.n_chunks):

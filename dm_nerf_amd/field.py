@@ -631,6 +631,7 @@ class SkipGrid:
 # ---- the occupancy volume labelled by object (csrc/label_grid.hip; tests/_label_grid_restate.py states it in numpy)
 UNLABELLED = 255
 MAX_LABELS = 128                # DMNERF_MAX_LOGITS (include/dmnerf_hip.h)
+MAX_TRACE_SETS = 16             # ray sets of one dmnerf_label_trace
 
 
 def label_rays(occ, i0=0, i1=None):
@@ -731,6 +732,7 @@ class LabelGrid:
         if not np.all(self.hi > self.lo):
             raise ValueError("LabelGrid: hi must be > lo on every axis")
         self.cell = (self.hi - self.lo) / np.asarray(self.dims, dtype=np.float32)
+        self.inv_cell = np.float32(1.0) / self.cell
         self.labels = labels
 
     @classmethod
@@ -771,3 +773,49 @@ class LabelGrid:
         _lib.check(_lib.load().dmnerf_skip_grid_from_labels(_lib.ptr(self.labels), g.n_cells, mask, _lib.ptr(g.bits), _lib.stream()),
                    "dmnerf_skip_grid_from_labels")
         return g.dilated(dilate) if int(dilate) else g
+
+    # ---- rays through the volume (csrc/label_trace.hip; tests/_label_trace_restate.py states it in numpy)
+    def trace_sets(self, rays, label_sets, near, far):
+        """The first cell along every ray whose label is in the ray set's own label set -> ``{"label" [N] uint8, "t" [N] f32, "cell" [N]
+        int32, "source" [N] uint8}`` on the device.  ``rays [R, 2, N, 3]`` f32: ``R <= 16`` sets of N (origin, direction) pairs, the
+        n-th rays of all sets belonging to one pixel; ``label_sets``: R entries, each an int or an iterable of ints in ``[0, C)`` (else
+        ``ValueError``; an empty iterable accepts nothing).  Per pixel the hit with the smallest ``t`` over the sets wins, the lowest
+        set on equal ``t``; ``cell = (i dy + j) dz + k``, ``source`` = the winning set; a pixel without a hit gets (255, +inf, -1, 255).
+        The traversal is exact, cell by cell, between ``near`` and ``far`` (``dmnerf_label_trace``); label 255 and labels ``>= C`` are
+        never hit.  One launch, nothing reaches the host: after a warm-up call it can be captured in a graph and follows ``labels`` on
+        replay."""
+        if not torch.is_tensor(rays) or rays.dtype != torch.float32:
+            raise ValueError("LabelGrid.trace_sets: rays must be a float32 tensor")
+        _lib.require_gpu(rays)
+        if rays.dim() != 4 or rays.shape[1] != 2 or rays.shape[3] != 3 or not 1 <= rays.shape[0] <= MAX_TRACE_SETS:
+            raise ValueError(f"LabelGrid.trace_sets expects rays [R <= {MAX_TRACE_SETS}, 2, N, 3], got {tuple(rays.shape)}")
+        if rays.device != self.labels.device:
+            raise RuntimeError("LabelGrid.trace_sets: the volume lives on another device than the rays")
+        R, _, N, _ = rays.shape
+        label_sets = list(label_sets)
+        if len(label_sets) != R:
+            raise ValueError(f"LabelGrid.trace_sets: {len(label_sets)} label sets for {R} ray sets")
+        words = [w for labels in label_sets for w in label_mask_words(labels, self.C)]
+        dev = rays.device
+        out = {"label": torch.empty(N, dtype=torch.uint8, device=dev), "t": torch.empty(N, dtype=torch.float32, device=dev),
+               "cell": torch.empty(N, dtype=torch.int32, device=dev), "source": torch.empty(N, dtype=torch.uint8, device=dev)}
+        f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
+        _lib.check(_lib.load().dmnerf_label_trace(_lib.ptr(self.labels), f3(self.lo), f3(self.cell), f3(self.inv_cell),
+                                                  (ctypes.c_int * 3)(*self.dims), self.C, _lib.ptr(rays), R, N,
+                                                  (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), _lib.ptr(out["label"]),
+                                                  _lib.ptr(out["t"]), _lib.ptr(out["cell"]), _lib.ptr(out["source"]), _lib.stream()),
+                   "dmnerf_label_trace")
+        return out
+
+    def trace(self, rays_o, rays_d, near, far, labels=None):
+        """``trace_sets`` with one ray set: ``rays_o``, ``rays_d [N, 3]`` f32 -> ``{"label", "t", "cell"}``.  ``labels``: an int or an
+        iterable as in ``skip_grid``; the default is every label ``0 .. C - 1``."""
+        for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32:
+                raise ValueError(f"LabelGrid.trace: {name} must be a float32 tensor")
+        _lib.require_gpu(rays_o, rays_d)
+        if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
+            raise ValueError(f"LabelGrid.trace expects rays_o, rays_d [N, 3], got {tuple(rays_o.shape)} and {tuple(rays_d.shape)}")
+        out = self.trace_sets(torch.stack([rays_o, rays_d])[None], [range(self.C) if labels is None else labels], near, far)
+        del out["source"]
+        return out

@@ -744,6 +744,26 @@ int dmnerf_label_stats(const uint8_t* d_labels, int dx, int dy, int dz, int C, i
                        int32_t* d_hi, void* stream);
 int dmnerf_skip_grid_from_labels(const uint8_t* d_labels, int64_t n_cells, const uint32_t mask[4], uint32_t* d_bits, void* stream);
 
+/* Rays through the label volume (csrc/label_trace.hip): the first cell along a ray whose label belongs to a set -- an object from
+ * a pixel, an edit previewed without the networks.  Additive (the ABI version stays).
+ *   dmnerf_label_trace: d_labels [dx,dy,dz] uint8 over the box whose lower corner, cell size, 1 / cell size and dims are the HOST
+ *     arrays lo, cell, inv_cell, dims (the values field.SkipGrid / field.LabelGrid compute); d_rays [R,2,N,3] = R ray sets of N
+ *     (origin, direction) pairs; masks = R x 4 HOST words, set r accepting label l iff l < C and bit l & 31 of masks[4 r + (l >> 5)]
+ *     is set (dmnerf_skip_grid_from_labels' words).  Label 255 and every label >= C are never accepted.  Per set and pixel, one
+ *     lane: exact cell-by-cell traversal, every f32 operation rounded on its own (tests/_label_trace_restate.py states it in numpy).
+ *     The planes of axis a are lo_a + float(b) * cell_a, b = 0 .. dims_a; the ray is clipped against the box and [t_near, t_far]
+ *     (an axis with d_a == 0 bounds nothing if lo_a <= o_a < plane_a(dims_a), else the ray misses) and misses unless
+ *     t_enter < t_exit, so a NaN anywhere is a miss; the walk starts in the (clamped) cell of o + d t_enter, visits at most
+ *     dx + dy + dz + 1 cells, accepts the first cell of the set at the current t, and otherwise crosses the nearest next plane
+ *     (tmax_a recomputed from the integer index, the lowest axis on ties), missing once that plane is not in front of t_exit.
+ *     Per pixel the hit with the smallest t over the sets wins, the lowest set on equal t: d_label [N] uint8 (255 on a miss),
+ *     d_t [N] f32 (+inf), d_cell [N] int32 = (i * dy + j) * dz + k (-1), d_source [N] uint8 = the set (255).
+ *     1 <= R <= 16, 1 <= C <= 128, dims >= 1 with dx dy dz < 2^31, N >= 0; N == 0 returns 0 without a launch.  No allocation, no
+ *     synchronisation, no atomics: it can be captured in a graph and reads d_labels anew on every replay. */
+int dmnerf_label_trace(const uint8_t* d_labels, const float lo[3], const float cell[3], const float inv_cell[3], const int dims[3], int C,
+                       const float* d_rays, int R, int64_t N, const uint32_t* masks, float t_near, float t_far, uint8_t* d_label,
+                       float* d_t, int32_t* d_cell, uint8_t* d_source, void* stream);
+
 /* The two renders above on the OPT-IN split-f16 ("f16x2") kernels (csrc/mlp_f16_density.hip, csrc/mlp_f16_sparse.hip; the body of
  * csrc/mlp_f16_impl.h with template flags).  Additive (the ABI version stays).
  *   f16 density blob: dmnerf_blob_f16_density_words 32-bit words = [the f16 blob's 4096-float bias table | its 120 trunk groups
