@@ -13,16 +13,7 @@ import numpy as np
 import pytest
 
 from dm_nerf_amd import _lib
-
-JOB = np.dtype([("a_off", "<i8"), ("b_off", "<i8"), ("a_R", "<i4"), ("b_R", "<i4"), ("a_row0", "<i4"), ("b_row0", "<i4"),
-                ("part_off", "<i8"), ("bias_off", "<i8"), ("a_src", "<i4"), ("b_src", "<i4"), ("rowsA", "<i4"), ("rowsB", "<i4"),
-                ("cls", "<i4"), ("chunk0", "<i4"), ("nchunk", "<i4"), ("follow", "<i4"), ("next", "<i4"), ("pad", "<i4")])
-OUT = np.dtype([("part_off", "<i8"), ("slice_stride", "<i8"), ("bias_part_off", "<i8"), ("bias_slice_stride", "<i8"),
-                ("out_off", "<i8"), ("bias_out_off", "<i8"), ("n_slices", "<i4"), ("rowsA", "<i4"), ("rowsB", "<i4"), ("ldp", "<i4"),
-                ("ld_out", "<i4"), ("col_off", "<i4"), ("bias_sub", "<i4"), ("ldb", "<i4"), ("perm_a", "<i4"), ("perm_b", "<i4"),
-                ("to_scratch", "<i4"), ("bias_split", "<i4"), ("bias_out_off2", "<i8")])
-MODES = {"f32": ("dmnerf_wgrad_plan_sizes", "dmnerf_wgrad_plan"), "bf16x3": ("dmnerf_wgrad_plan_sizes_split", "dmnerf_wgrad_plan_split"),
-         "f16x2": ("dmnerf_wgrad_plan_sizes_f16", "dmnerf_wgrad_plan_f16")}
+from _wgrad_restate import JOB, MODES, OUT          # the struct layouts of csrc/wgrad_common.h and the C entries per cost table
 
 
 def plan(mode, ins_num, M, max_wgs):
