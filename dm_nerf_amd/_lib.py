@@ -207,6 +207,9 @@ SIGNATURES = {
     "dmnerf_render_rays_fwd_fine_skip": (c_int, [ctypes.POINTER(RenderFineSkipArgs), c_vp]),
     "dmnerf_skip_grid_mark": (c_int, [ctypes.POINTER(SkipGridArgs), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_float, c_vp]),
     "dmnerf_skip_grid_dilate": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "dmnerf_skip_gather_samples": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_rows_scatter": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    "dmnerf_rows_gather": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
     "dmnerf_label_cells": (c_int, [c_vp, c_i64, c_int, c_float, c_vp, c_vp]),
     "dmnerf_label_stats": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_skip_grid_from_labels": (c_int, [c_vp, c_i64, ctypes.POINTER(ctypes.c_uint32), c_vp, c_vp]),

@@ -657,6 +657,124 @@ def _run_network_train(model, rays_o, rays_d, z, mode):
                       for s in range(0, N, max_rays)], 0)
 
 
+# ---- training that does not evaluate empty space (csrc/train_skip.hip; DESIGN.md 8a, "Training through the grid") ---------------
+TRAIN_SKIP_BUCKET = 32768           # the compact batch is padded to a multiple of this: few distinct sizes, few wgrad plans
+
+_zero_rows = {}
+
+
+def _zero_row(width, device):
+    """The all-zero fill row of ``run_network_train_skip`` (kept per width and device, like ``render.empty_row``)."""
+    key = (int(width), str(device))
+    if key not in _zero_rows:
+        _zero_rows[key] = torch.zeros(int(width), dtype=torch.float32, device=device)
+    return _zero_rows[key]
+
+
+class ScatterRows(torch.autograd.Function):
+    """``raw[sel[i]] = raw_c[i]`` for ``i < n_sel`` into the pre-filled ``raw [N,S,width]`` (in place: ``dmnerf_rows_scatter``);
+    backward: ``g_c[i] = g_raw[sel[i]]`` and exact zeros for the padded rows ``n_sel <= i < n_pad`` (``dmnerf_rows_gather``).
+    ``raw`` itself gets no gradient: its other rows are the constant fill."""
+
+    @staticmethod
+    def forward(ctx, raw_c, raw, sel, n_sel):
+        n_pad, width = raw_c.shape[0], raw.shape[-1]
+        _lib.check(_lib.load().dmnerf_rows_scatter(_lib.ptr(raw_c), n_pad, _lib.ptr(sel), n_sel, _lib.ptr(raw), raw.shape[0] * raw.shape[1],
+                                                   width, _lib.stream()), "dmnerf_rows_scatter")
+        ctx.sel, ctx.n_sel, ctx.shape_c = sel, n_sel, tuple(raw_c.shape)
+        ctx.mark_dirty(raw)
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        g = _lib.f32(g_raw)
+        g_c = torch.empty(ctx.shape_c, dtype=torch.float32, device=g.device)
+        _lib.check(_lib.load().dmnerf_rows_gather(_lib.ptr(g), g.shape[0] * g.shape[1], _lib.ptr(ctx.sel), ctx.n_sel, _lib.ptr(g_c),
+                                                  ctx.shape_c[0], g.shape[-1], _lib.stream()), "dmnerf_rows_gather")
+        return g_c, None, None, None
+
+
+def run_network_train_skip(model, rays_o, rays_d, z, grid, split=None, check_f16=None, bucket=TRAIN_SKIP_BUCKET, counts=None):
+    """``run_network_train`` that does not evaluate empty space: ``raw [N,S,4+C]`` whose rows are the dense call's, bit for bit, where
+    the sample's cell of ``grid`` (a ``field.SkipGrid``) is set -- or the sample lies outside its box and ``grid.outside ==
+    "evaluate"`` -- and EXACT ZEROS everywhere else; differentiable w.r.t. the parameters, with the gradient of
+    ``sum(raw * G * flag)``: a skipped sample contributes nothing, forward or backward.
+
+    1. ``dmnerf_skip_select_fill`` with an all-zero fill row (not ``render.empty_row``: sigma 0 makes the row's compositing weight
+       and its sigma gradient path exactly neutral to ``render_train``, and zero logits are a constant to the penalizer);
+    2. the selection length ``M'`` is read on the HOST -- the one synchronisation of the call, i.e. one per level of a training
+       step: the training kernels size their workspace and their split-K plan on the host, so the length cannot stay on the device
+       (which is also why a step with a grid cannot be captured in a graph);
+    3. ``Mp`` = ``M'`` rounded up to a multiple of ``bucket`` (``wgrad_plan`` keeps 32 plans; with the default bucket a level sees few
+       distinct sizes);
+    4. ``dmnerf_skip_gather_samples`` (no grad): ``Mp`` one-sample rays, the padding repeating the last selected sample;
+    5. the existing training path (``_run_network_train``: forward with saved activations, its own split at
+       ``MAX_TRAIN_SAMPLES``, the MLP autograd) on the batch ``N = Mp, S = 1``;
+    6. ``ScatterRows`` into the pre-filled ``raw``.  Padded rows receive zero cotangents: they add exact zeros to every gradient sum.
+
+    ``M' = 0`` launches no network kernel and returns the all-zero ``raw``; it still hangs off the parameters, whose gradients are
+    then exact ZEROS (not ``None``): a loss made of skipped levels only can still be back-propagated, and a gradient arena gets
+    its slot written.  ``split``: None (f32) or ``"f16x2"`` (the range scans of ``check_f16`` then see the compact workspace).
+    ``counts``: as in ``render.run_network_skip`` -- optional int64 ``[2]`` device tensor, ``+= (evaluated, samples)`` on the device.
+
+    There is no dense detour: ``"bf16x3"`` and a network shape other than the 8 x 256 one raise ``ValueError``, a grid on another
+    device raises ``RuntimeError``, ``N S >= 2^31`` raises ``ValueError``."""
+    import ctypes
+
+    from . import field
+    if not isinstance(grid, field.SkipGrid):
+        raise TypeError("run_network_train_skip: grid must be a field.SkipGrid")
+    split = split or None
+    if split not in (None, "f16x2"):
+        raise ValueError(f"run_network_train_skip: no training through the grid for args.mfma_split = {split!r} (f32 and 'f16x2' only)")
+    if not model._fused_ok():
+        raise ValueError("run_network_train_skip: training through the grid exists for the 8 x 256 network only")
+    bucket = int(bucket)
+    if bucket < 1:
+        raise ValueError(f"run_network_train_skip: bucket must be >= 1, got {bucket}")
+    N, S = z.shape
+    if N * S >= 2 ** 31:
+        raise ValueError(f"run_network_train_skip: {N * S} samples do not fit the int32 selection; train on smaller batches")
+    rays_o, rays_d, z = _lib.f32(rays_o.reshape(-1, 3)).detach(), _lib.f32(rays_d.reshape(-1, 3)).detach(), _lib.f32(z).detach()
+    _lib.require_gpu(rays_o, rays_d, z)
+    dev = z.device
+    if grid.bits.device != dev:
+        raise RuntimeError("run_network_train_skip: the grid lives on another device than the rays")
+    if counts is not None:
+        _lib.require_gpu(counts)
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (2,) or counts.device != dev or not counts.is_contiguous():
+            raise ValueError("run_network_train_skip: counts must be a contiguous int64 [2] tensor on the rays' device")
+    width = 4 + model.ins_num + 1
+    raw = torch.empty(N, S, width, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    n_sel = 0
+    sel = None
+    if N * S:
+        sel = torch.empty(N * S, dtype=torch.int32, device=dev)
+        flag = torch.empty(N * S, dtype=torch.uint8, device=dev)
+        work = torch.empty(int(lib.dmnerf_skip_select_work_ints(N * S)), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        g = grid.c_struct()
+        _lib.check(lib.dmnerf_skip_select_fill(ctypes.byref(g), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z), N, S, _lib.ptr(flag),
+                                               _lib.ptr(sel), _lib.ptr(count), _lib.ptr(work), _lib.ptr(raw), _lib.ptr(_zero_row(width, dev)),
+                                               width, _lib.ptr(counts), _lib.stream()), "dmnerf_skip_select_fill")
+        n_sel = int(count.item())                                  # the host read: one synchronisation per call
+    n_pad = -(-n_sel // bucket) * bucket
+    o_c = torch.empty(n_pad, 3, dtype=torch.float32, device=dev)
+    d_c = torch.empty(n_pad, 3, dtype=torch.float32, device=dev)
+    z_c = torch.empty(n_pad, 1, dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        _lib.check(lib.dmnerf_skip_gather_samples(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z), N, max(S, 1), _lib.ptr(sel), n_sel, n_pad,
+                                                  _lib.ptr(o_c), _lib.ptr(d_c), _lib.ptr(z_c), _lib.stream()), "dmnerf_skip_gather_samples")
+    mode = "f16" if split == "f16x2" else None
+    _check_f16_call[0] = None if check_f16 is None else bool(check_f16)
+    try:
+        raw_c = _run_network_train(model, o_c, d_c, z_c, mode)     # [n_pad, 1, width]; n_pad = 0: no launch, zero gradients
+    finally:
+        _check_f16_call[0] = None
+    return ScatterRows.apply(raw_c, raw, sel, n_sel)
+
+
 def render_train_train(raw, z_vals, rays_d):
     raw, z, d = _lib.f32(raw), _lib.f32(z_vals.detach()), _lib.f32(rays_d.detach())
     _lib.require_gpu(raw, z, d)
@@ -686,8 +804,26 @@ def mlp_forward_train(model, x):
     return out.reshape(*x.shape[:-1], out.shape[-1])
 
 
-def dm_nerf_train(rays, model_coarse, model_fine, z_vals_coarse, args, t_rand=None, u=None):
-    """Training-mode ``dm_nerf`` (networks/render.py:31-96): same dict, differentiable w.r.t. both models."""
+def dm_nerf_train(rays, model_coarse, model_fine, z_vals_coarse, args, t_rand=None, u=None, skip=None, skip_levels=("coarse", "fine")):
+    """Training-mode ``dm_nerf`` (networks/render.py:31-96): same dict, differentiable w.r.t. both models.
+
+    ``skip`` (a ``field.SkipGrid``, or a ``field.TrainSkip`` whose current ``.grid`` is taken; default None: every call, kernel and
+    output is what it was): the levels named in ``skip_levels`` go through ``run_network_train_skip`` -- samples in clear cells are
+    not evaluated, their rows of ``raw_*`` are exact zeros and they receive no gradient.  Compositing, penalizer partial sums,
+    importance resampling, the ``N_ins`` slice and the order of the RNG draws are unchanged; one host read per skipped level.
+    With ``SkipGrid.full`` every key equals the dense call's.  ``args.fuse_heads``, ``args.mfma_split = "bf16x3"`` and a network
+    shape other than 8 x 256 raise ``ValueError`` (there is no dense detour).  ``args.train_skip_counts`` (optional int64 ``[2]``
+    device tensor per level name, a dict) receives ``+= (evaluated, samples)``; ``args.train_skip_bucket`` overrides the padding
+    bucket of ``run_network_train_skip``."""
+    if skip is not None:
+        from . import field
+        from .networks.render import check_skip_levels
+        skip = skip.grid if isinstance(skip, field.TrainSkip) else skip
+        if not isinstance(skip, field.SkipGrid):
+            raise TypeError("dm_nerf_train: skip must be a field.SkipGrid or a field.TrainSkip")
+        skip_levels = check_skip_levels("dm_nerf_train", skip_levels)
+        if bool(getattr(args, "fuse_heads", False)):
+            raise ValueError("dm_nerf_train: no training through the grid with args.fuse_heads (f32 and mfma_split = 'f16x2' only)")
     rays_o, rays_d = rays
     rays_o, rays_d = _lib.f32(rays_o.reshape(-1, 3)).detach(), _lib.f32(rays_d.reshape(-1, 3)).detach()
     z_in = _lib.f32(z_vals_coarse).detach()
@@ -710,14 +846,21 @@ def dm_nerf_train(rays, model_coarse, model_fine, z_vals_coarse, args, t_rand=No
         rgb, w, depth, ins, part = CompositePenFunction.apply(raw, z, rays_d, consts)
         depth._dmn_pen = (part, raw.data_ptr(), z.data_ptr(), rays_d.data_ptr(), consts)       # see pen_partials
         return rgb, w, depth, ins
-    raw_coarse = run_network_train(model_coarse, rays_o, rays_d, z_coarse, fused, split, check_f16=chk)
+    cnts = (getattr(args, "train_skip_counts", None) or {}) if skip is not None else {}
+
+    def network(level, model, z):
+        if skip is None or level not in skip_levels:
+            return run_network_train(model, rays_o, rays_d, z, fused, split, check_f16=chk)
+        return run_network_train_skip(model, rays_o, rays_d, z, skip, split=split, check_f16=chk,
+                                      bucket=int(getattr(args, "train_skip_bucket", TRAIN_SKIP_BUCKET)), counts=cnts.get(level))
+    raw_coarse = network("coarse", model_coarse, z_coarse)
     rgb_coarse, weights_coarse, depth_coarse, ins_coarse = composite(raw_coarse, z_coarse)
     with torch.no_grad():                              # z_samples.detach()  (render.py:68)
         if n_imp == 0:                                 # sample_pdf returns [N, 0]: the fine depths are the coarse ones
             z_fine = z_coarse.clone()
         else:
             z_fine = helpers.importance_resample(z_coarse, weights_coarse.detach(), n_imp, det=(perturb == 0.), u=u)
-    raw_fine = run_network_train(model_fine, rays_o, rays_d, z_fine, fused, split, check_f16=chk)
+    raw_fine = network("fine", model_fine, z_fine)
     rgb_fine, weights_fine, depth_fine, ins_fine = composite(raw_fine, z_fine)
     if getattr(args, "is_train", False) and getattr(args, "N_ins", None) is not None:
         ins_fine = ins_fine[-args.N_ins:]

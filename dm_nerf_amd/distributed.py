@@ -274,7 +274,11 @@ def sharded_train_step(rays, z_vals, target, labels, models, args, optimizer, in
 
     ``render / mse / criterion / penalizer`` default to the HIP path (networks.render.dm_nerf, evaluator.img2mse,
     evaluator.ins_criterion, penalizer.ins_penalizer); they are injectable so that the sharding logic itself is
-    covered on CPU with gloo.  Returns the (global) loss and the number of bytes all-reduced."""
+    covered on CPU with gloo.  Returns the (global) loss and the number of bytes all-reduced.
+
+    ``args.train_skip`` (a ``field.SkipGrid`` / ``field.TrainSkip``) needs nothing here: the default render reaches
+    ``autograd.dm_nerf_train`` through ``args``, every rank selects within its own ray slice (one host read per skipped level
+    and rank), a rank whose slice selects nothing contributes exact zeros, and the collectives are unchanged."""
     from .networks import evaluator as E, penalizer as P, render as R
     rank, world = world_info()
     multi = _active(world)                               # (a forced world of one takes every multi-rank branch below)

@@ -628,6 +628,44 @@ class SkipGrid:
         return self.unpack().float().mean()
 
 
+class TrainSkip:
+    """When the grid of a training run that skips empty space (``autograd.dm_nerf_train(..., skip=)``, ``args.train_skip``) is
+    refreshed from the network it trains.  There is no grid kernel of its own here: the object only decides when.
+
+    ``.grid`` is ``SkipGrid.full`` for the first ``warmup`` steps (the step equals the dense one).  ``.step(model_fine)`` is called
+    once per optimisation step, after the optimizer; on the call that completes the warm-up and on every ``every``-th call after it
+    the bits are overwritten IN PLACE (same tensor, same ``data_ptr``) with
+    ``SkipGrid.from_model(model_fine, ..., threshold=threshold, dilate=0).dilated(dilate)``.  Returns True when it refreshed.
+
+    Defaults ("Training through the grid"): ``warmup=500`` -- an untrained network's density has a random sign, and a
+    sample that is skipped can never receive the gradient that would raise its density, so the grid must not be read before the
+    field has a shape; ``every=16`` -- a 128^3 refresh is one trunk-only pass over 2.1 M points, a fraction of a step when spread
+    over 16; ``threshold=0.0`` on the raw density: ``relu(sigma) = 0`` is the only value that is exactly neutral; ``dilate=1`` --
+    the centre sample says nothing about the rest of the cell, and a surface can grow by one cell per refresh;
+    ``outside="evaluate"``: nothing outside the box is assumed empty."""
+
+    def __init__(self, lo, hi, dims=128, every=16, warmup=500, threshold=0.0, dilate=1, outside="evaluate", device="cuda"):
+        self.every, self.warmup = int(every), int(warmup)
+        if self.every < 1 or self.warmup < 0:
+            raise ValueError(f"TrainSkip: every must be >= 1 and warmup >= 0, got {every}, {warmup}")
+        self.threshold, self.dilate = float(threshold), int(dilate)
+        self.grid = SkipGrid.full(lo, hi, dims, outside, device)
+        self.steps = 0                  # calls of step() so far
+        self.refreshes = 0
+
+    def step(self, model_fine):
+        self.steps += 1
+        if self.steps < self.warmup or (self.steps - self.warmup) % self.every:
+            return False
+        g = self.grid
+        with torch.no_grad():
+            new = SkipGrid.from_model(model_fine, g.lo, g.hi, g.dims, threshold=self.threshold, dilate=0, outside=g.outside,
+                                      device=g.bits.device).dilated(self.dilate)
+            g.bits.copy_(new.bits)
+        self.refreshes += 1
+        return True
+
+
 # ---- the occupancy volume labelled by object (csrc/label_grid.hip; tests/_label_grid_restate.py states it in numpy)
 UNLABELLED = 255
 MAX_LABELS = 128                # DMNERF_MAX_LOGITS (include/dmnerf_hip.h)

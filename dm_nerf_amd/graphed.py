@@ -29,6 +29,10 @@ class GraphedTrainStep:
         (``capturable=True`` or ``fused=True``) with a tensor learning rate if ``set_lr`` is to be used."""
         if not rays.is_cuda:
             raise RuntimeError("GraphedTrainStep needs GPU tensors")
+        if getattr(args, "train_skip", None) is not None:
+            # (autograd.run_network_train_skip reads the selection length on the host to size the compact batch)
+            raise ValueError("GraphedTrainStep: args.train_skip cannot be captured -- a step through the grid reads the number of "
+                             "selected samples on the host; train eagerly, or without the grid")
         for grp in optimizer.param_groups:
             if not (grp.get("capturable", False) or grp.get("fused", False)):
                 raise ValueError("GraphedTrainStep: build the optimizer with capturable=True (or fused=True)")

@@ -168,7 +168,13 @@ def dm_nerf(rays, position_embedder, view_embedder, model_coarse, model_fine, z_
     training = torch.is_grad_enabled() and any(p.requires_grad for m in (model_coarse, model_fine) for p in m.parameters())
     if training:
         from .. import autograd
-        return autograd.dm_nerf_train(rays, model_coarse, model_fine, z_vals_coarse, args, t_rand=t_rand, u=u)
+        # args.train_skip (extension, default None): a field.SkipGrid / field.TrainSkip -- the levels in args.train_skip_levels are
+        # trained through the grid (autograd.run_network_train_skip); the reference's train loops opt in as with args.mfma_split
+        grid = getattr(args, "train_skip", None)
+        if grid is None:
+            return autograd.dm_nerf_train(rays, model_coarse, model_fine, z_vals_coarse, args, t_rand=t_rand, u=u)
+        return autograd.dm_nerf_train(rays, model_coarse, model_fine, z_vals_coarse, args, t_rand=t_rand, u=u, skip=grid,
+                                      skip_levels=getattr(args, "train_skip_levels", ("coarse", "fine")))
     for emb, want in ((position_embedder, model_fine.input_ch_pts), (view_embedder, model_fine.input_ch_views)):
         if getattr(emb, "out_dim", want) != want:
             raise ValueError("dm_nerf: the embedders' out_dim does not match the models' input channels")

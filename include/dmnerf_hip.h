@@ -718,6 +718,30 @@ int dmnerf_skip_grid_mark(const dmnerf_skip_grid* grid, uint32_t* d_bits, const 
                           const float* d_z, const float* d_weights, int64_t N, int S, float threshold, void* stream);
 int dmnerf_skip_grid_dilate(const uint32_t* d_bits_in, int dx, int dy, int dz, int dilate, uint32_t* d_bits_out, void* stream);
 
+/* A TRAINING step that does not evaluate empty space (opt-in; csrc/train_skip.hip, autograd.run_network_train_skip).  The select
+ * pass above flags the samples and fills the clear rows of raw with zeros; these three entries move data between the dense
+ * [N*S, ..] tensors and the compact batch of n_pad >= n_sel one-sample rays that the unchanged training kernels
+ * (dmnerf_mlp_fwd_rays_train*, dmnerf_mlp_bwd_data*, dmnerf_mlp_bwd_weights*) run on with N = n_pad, S = 1.  n_sel is the HOST copy
+ * of the select's *d_count (the one host read of the path); d_sel is the select's ascending list.  No atomics (the list is strictly
+ * ascending: one writer per row), no allocation, no synchronisation.  Additive (the ABI version stays).
+ *   dmnerf_skip_gather_samples: d_o, d_d [n_pad,3], d_zc [n_pad]: row i < n_sel is the ray (row d_sel[i] / S of d_rays_o, d_rays_d)
+ *     and the depth d_z[d_sel[i]] of sample d_sel[i], copied bit for bit; rows n_sel <= i < n_pad repeat row n_sel - 1, so the padded
+ *     launch reads finite, in-range data.  n_pad == 0 returns 0 without a launch; n_pad > 0 with n_sel == 0 is refused.
+ *   dmnerf_rows_scatter: row i of d_src [n_pad, width] goes to row d_sel[i] of d_dst [n_rows, width] for i < n_sel; no other row of
+ *     d_dst is touched.  n_sel == 0 returns 0 without a launch.
+ *   dmnerf_rows_gather: the transpose.  d_dst [n_pad, width]: row i = row d_sel[i] of d_src [n_rows, width] for i < n_sel, exact
+ *     zeros for n_sel <= i < n_pad (a padded row's cotangent: it adds exact zeros to every gradient sum).
+ *   Rows need no alignment: as in dmnerf_skip_select_fill a block owns the contiguous run of its 256 compact rows, one float per lane
+ *   per step.  1 <= width <= 65536.  Refused with DMNERF_E_ARG: negative sizes, n_sel > n_pad, n_sel > n_rows, n_rows (= N * S) or
+ *   n_pad >= 2^31, a null pointer with non-zero sizes.  An entry of d_sel outside [0, n_rows) is the caller's bug: that row is
+ *   not scattered and gathers as zeros (gather_samples: the last sample), so nothing is read or written out of bounds. */
+int dmnerf_skip_gather_samples(const float* d_rays_o, const float* d_rays_d, const float* d_z, int64_t N, int S, const int* d_sel,
+                               int64_t n_sel, int64_t n_pad, float* d_o, float* d_d, float* d_zc, void* stream);
+int dmnerf_rows_scatter(const float* d_src, int64_t n_pad, const int* d_sel, int64_t n_sel, float* d_dst, int64_t n_rows, int width,
+                        void* stream);
+int dmnerf_rows_gather(const float* d_src, int64_t n_rows, const int* d_sel, int64_t n_sel, float* d_dst, int64_t n_pad, int width,
+                       void* stream);
+
 /* The occupancy volume labelled by object (csrc/label_grid.hip): which object owns a cell of the box, what every object covers, and
  * the bit grid of a set of objects.  The network runs in front of these (networks/render.py run_network_skip at one point per cell:
  * field.label_grid); none of the three allocates or synchronises, so the chain can be captured in a graph.  Additive (the ABI
