@@ -282,10 +282,11 @@ def grad_arena(models):
 
 class MLPRaysFunction(torch.autograd.Function):
     """raw[N,S,4+C] = DM_NeRF(embed(o + d z) | embed(d/|d|)); parameters are inputs 5.. in state_dict order.
-    ``mode``: None (default f32 kernels) | "fused" | "split" (the opt-in variants of run_network_train)."""
+    ``mode``: None (default f32 kernels) | "fused" | "split" | "f16" (the opt-in variants of run_network_train); ``check_f16``: the
+    caller's ``args.check_f16`` for the range scans of this forward and its backward (None: the module flag / DMNERF_CHECK_F16)."""
 
     @staticmethod
-    def forward(ctx, model, mode, rays_o, rays_d, z, *params):
+    def forward(ctx, model, mode, check_f16, rays_o, rays_d, z, *params):
         lib = _lib.load()
         N, S = z.shape
         M = N * S
@@ -304,7 +305,7 @@ class MLPRaysFunction(torch.autograd.Function):
         with _timed("mlp_fwd_train", M):
             _lib.check(fn(_lib.ptr(fwd_blob), ins_num, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z),
                           N, S, _lib.ptr(raw), _lib.ptr(save), _lib.stream()), "dmnerf_mlp_fwd_rays_train")
-        ctx.check_f16 = mode == "f16" and (_check_f16_call[0] if _check_f16_call[0] is not None else f16_check_enabled())
+        ctx.check_f16 = mode == "f16" and (check_f16 if check_f16 is not None else f16_check_enabled())
         if ctx.check_f16:
             _f16_range_scan(save, M, False)
         ctx.model, ctx.M, ctx.save = model, M, save
@@ -321,7 +322,7 @@ class MLPRaysFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_raw):
-        return (None, None, None, None, None) + _mlp_backward(ctx, g_raw)
+        return (None, None, None, None, None, None) + _mlp_backward(ctx, g_raw)
 
 
 def _grad_scale_buffer(device):
@@ -501,17 +502,39 @@ class MLPEmbeddedFunction(torch.autograd.Function):
         return (None, None) + _mlp_backward(ctx, g_raw)
 
 
+def _composite_outputs(raw):
+    """Sizes and the four outputs of a compositing forward over ``raw [N,S,4+C]`` -> ``(N, S, C, rgb, weights, depth, ins)``."""
+    N, S, ch = raw.shape
+    C = ch - 4
+    f = dict(dtype=torch.float32, device=raw.device)
+    rgb, w = torch.empty(N, 3, **f), torch.empty(N, S, **f)
+    depth, ins = torch.empty(N, **f), torch.empty(N, C - 1, **f)
+    return N, S, C, rgb, w, depth, ins
+
+
+def _composite_cotangents(raw, g_rgb, g_w, g_depth, g_ins):
+    """The cotangents as ``dmnerf_composite_bwd`` / ``.._pen_bwd`` take them: f32 at full shape, zeros for an absent ``g_rgb`` / ``g_ins``,
+    None for an absent ``g_w`` / ``g_depth`` -> ``(N, S, C, g_rgb, g_w, g_depth, g_ins, d_raw)`` with ``d_raw`` allocated last."""
+    N, S, ch = raw.shape
+    C = ch - 4
+
+    def prep(g, shape):
+        if g is None:
+            return None
+        return _lib.f32(g.expand(shape) if g.shape != torch.Size(shape) else g)
+    g_rgb = prep(g_rgb, (N, 3)) if g_rgb is not None else torch.zeros(N, 3, device=raw.device)
+    g_ins = prep(g_ins, (N, C - 1)) if g_ins is not None else torch.zeros(N, C - 1, device=raw.device)
+    g_w, g_depth = prep(g_w, (N, S)), prep(g_depth, (N,))
+    return N, S, C, g_rgb, g_w, g_depth, g_ins, torch.empty_like(raw)
+
+
 class CompositeFunction(torch.autograd.Function):
     """render_train (networks/render.py:6-28) with its analytic backward."""
 
     @staticmethod
     def forward(ctx, raw, z, rays_d):
         lib = _lib.load()
-        N, S, ch = raw.shape
-        C = ch - 4
-        f = dict(dtype=torch.float32, device=raw.device)
-        rgb, w = torch.empty(N, 3, **f), torch.empty(N, S, **f)
-        depth, ins = torch.empty(N, **f), torch.empty(N, C - 1, **f)
+        N, S, C, rgb, w, depth, ins = _composite_outputs(raw)
         _lib.check(lib.dmnerf_composite_fwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays_d), N, S, C, _lib.ptr(rgb), _lib.ptr(w),
                                             _lib.ptr(depth), _lib.ptr(ins), _lib.stream()), "dmnerf_composite_fwd")
         ctx.save_for_backward(raw, z, rays_d, ins)
@@ -522,17 +545,7 @@ class CompositeFunction(torch.autograd.Function):
     def backward(ctx, g_rgb, g_w, g_depth, g_ins):
         lib = _lib.load()
         raw, z, rays_d, ins = ctx.saved_tensors
-        N, S, ch = raw.shape
-        C = ch - 4
-
-        def prep(g, shape):
-            if g is None:
-                return None
-            return _lib.f32(g.expand(shape) if g.shape != torch.Size(shape) else g)
-        g_rgb = prep(g_rgb, (N, 3)) if g_rgb is not None else torch.zeros(N, 3, device=raw.device)
-        g_ins = prep(g_ins, (N, C - 1)) if g_ins is not None else torch.zeros(N, C - 1, device=raw.device)
-        g_w, g_depth = prep(g_w, (N, S)), prep(g_depth, (N,))
-        d_raw = torch.empty_like(raw)
+        N, S, C, g_rgb, g_w, g_depth, g_ins, d_raw = _composite_cotangents(raw, g_rgb, g_w, g_depth, g_ins)
         _lib.check(lib.dmnerf_composite_bwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays_d), _lib.ptr(ins), _lib.ptr(g_rgb), _lib.ptr(g_ins),
                                             _lib.ptr(g_depth), _lib.ptr(g_w), N, S, C, _lib.ptr(d_raw), _lib.stream()), "dmnerf_composite_bwd")
         return d_raw, None, None
@@ -549,11 +562,7 @@ class CompositePenFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, z, rays_d, consts):
         lib = _lib.load()
-        N, S, ch = raw.shape
-        C = ch - 4
-        f = dict(dtype=torch.float32, device=raw.device)
-        rgb, w = torch.empty(N, 3, **f), torch.empty(N, S, **f)
-        depth, ins = torch.empty(N, **f), torch.empty(N, C - 1, **f)
+        N, S, C, rgb, w, depth, ins = _composite_outputs(raw)
         part = torch.empty(N, 4, dtype=torch.float64, device=raw.device)
         tol, k2w, kh = consts
         _lib.check(lib.dmnerf_composite_pen_fwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays_d), N, S, C, tol, k2w, kh, _lib.ptr(rgb), _lib.ptr(w),
@@ -567,17 +576,7 @@ class CompositePenFunction(torch.autograd.Function):
     def backward(ctx, g_rgb, g_w, g_depth, g_ins, g_part):
         lib = _lib.load()
         raw, z, rays_d, ins, depth = ctx.saved_tensors
-        N, S, ch = raw.shape
-        C = ch - 4
-
-        def prep(g, shape):
-            if g is None:
-                return None
-            return _lib.f32(g.expand(shape) if g.shape != torch.Size(shape) else g)
-        g_rgb = prep(g_rgb, (N, 3)) if g_rgb is not None else torch.zeros(N, 3, device=raw.device)
-        g_ins = prep(g_ins, (N, C - 1)) if g_ins is not None else torch.zeros(N, C - 1, device=raw.device)
-        g_w, g_depth = prep(g_w, (N, S)), prep(g_depth, (N,))
-        d_raw = torch.empty_like(raw)
+        N, S, C, g_rgb, g_w, g_depth, g_ins, d_raw = _composite_cotangents(raw, g_rgb, g_w, g_depth, g_ins)
         if g_part is None or N == 0:
             _lib.check(lib.dmnerf_composite_bwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays_d), _lib.ptr(ins), _lib.ptr(g_rgb), _lib.ptr(g_ins),
                                                 _lib.ptr(g_depth), _lib.ptr(g_w), N, S, C, _lib.ptr(d_raw), _lib.stream()), "dmnerf_composite_bwd")
@@ -621,9 +620,6 @@ def _params(model):
     return [p for _, p in model.named_parameters()]
 
 
-_check_f16_call = [None]            # run_network_train(check_f16=): the caller's args.check_f16 for the launches of this call
-
-
 def run_network_train(model, rays_o, rays_d, z, fused=False, split=None, check_f16=None):
     """Differentiable (w.r.t. the parameters) fused points + encoding + MLP.  Opt-in variants: ``fused`` (``args.fuse_heads``)
     runs the FORWARD on the fused-heads blob (-19 % MACs; values equal up to f32 re-association, not bit-equal to the inference
@@ -632,14 +628,11 @@ def run_network_train(model, rays_o, rays_d, z, fused=False, split=None, check_f
     f32-class values).  ``check_f16`` (``f16_check_enabled(args)``): scan what the f16x2 forward AND the
     backward of these launches convert for saturation (None: the module flag / DMNERF_CHECK_F16)."""
     mode = {"bf16x3": "split", "f16x2": "f16", True: "split"}[split] if split else ("fused" if fused else None)
-    _check_f16_call[0] = None if check_f16 is None else bool(check_f16)
-    try:
-        return _run_network_train(model, rays_o, rays_d, z, mode)
-    finally:
-        _check_f16_call[0] = None
+    return _run_network_train(model, rays_o, rays_d, z, mode, check_f16)
 
 
-def _run_network_train(model, rays_o, rays_d, z, mode):
+def _run_network_train(model, rays_o, rays_d, z, mode, check_f16=None):
+    check_f16 = None if check_f16 is None else bool(check_f16)
     if not model._fused_ok():                              # another network shape: layer by layer, its own autograd Function
         from . import generic
         return generic.run_network(model, rays_o, rays_d, z, train=True)
@@ -648,27 +641,20 @@ def _run_network_train(model, rays_o, rays_d, z, mode):
     N, S = z.shape
     max_rays = max(1, MAX_TRAIN_SAMPLES // S)
     if N <= max_rays:
-        return MLPRaysFunction.apply(model, mode, rays_o, rays_d, z, *_params(model))
+        return MLPRaysFunction.apply(model, mode, check_f16, rays_o, rays_d, z, *_params(model))
     # a training launch addresses its saved-activation workspace with 32-bit byte offsets (DMNERF_MAX_TRAIN_SAMPLES in
     # include/dmnerf_hip.h): larger batches run as several launches, each with its own workspace; autograd adds the
     # parameter gradients of the pieces (rays are independent, so this is the same sum in a different order)
     params = _params(model)
-    return torch.cat([MLPRaysFunction.apply(model, mode, rays_o[s:s + max_rays], rays_d[s:s + max_rays], z[s:s + max_rays], *params)
+    return torch.cat([MLPRaysFunction.apply(model, mode, check_f16, rays_o[s:s + max_rays], rays_d[s:s + max_rays], z[s:s + max_rays], *params)
                       for s in range(0, N, max_rays)], 0)
 
 
 # ---- training that does not evaluate empty space (csrc/train_skip.hip; DESIGN.md 8a, "Training through the grid") ---------------
 TRAIN_SKIP_BUCKET = 32768           # the compact batch is padded to a multiple of this: few distinct sizes, few wgrad plans
 
-_zero_rows = {}
-
-
-def _zero_row(width, device):
-    """The all-zero fill row of ``run_network_train_skip`` (kept per width and device, like ``render.empty_row``)."""
-    key = (int(width), str(device))
-    if key not in _zero_rows:
-        _zero_rows[key] = torch.zeros(int(width), dtype=torch.float32, device=device)
-    return _zero_rows[key]
+# run_network_train_skip's wording of the selection's refusals (render.SPARSE_WORDS)
+TRAIN_SKIP_WORDS = ("no training through the grid", "training through the grid exists", "train on smaller batches")
 
 
 class ScatterRows(torch.autograd.Function):
@@ -700,7 +686,7 @@ def run_network_train_skip(model, rays_o, rays_d, z, grid, split=None, check_f16
     "evaluate"`` -- and EXACT ZEROS everywhere else; differentiable w.r.t. the parameters, with the gradient of
     ``sum(raw * G * flag)``: a skipped sample contributes nothing, forward or backward.
 
-    1. ``dmnerf_skip_select_fill`` with an all-zero fill row (not ``render.empty_row``: sigma 0 makes the row's compositing weight
+    1. ``render.skip_select`` with an all-zero fill row (not ``render.empty_row``: sigma 0 makes the row's compositing weight
        and its sigma gradient path exactly neutral to ``render_train``, and zero logits are a constant to the penalizer);
     2. the selection length ``M'`` is read on the HOST -- the one synchronisation of the call, i.e. one per level of a training
        step: the training kernels size their workspace and their split-K plan on the host, so the length cannot stay on the device
@@ -719,46 +705,17 @@ def run_network_train_skip(model, rays_o, rays_d, z, grid, split=None, check_f16
 
     There is no dense detour: ``"bf16x3"`` and a network shape other than the 8 x 256 one raise ``ValueError``, a grid on another
     device raises ``RuntimeError``, ``N S >= 2^31`` raises ``ValueError``."""
-    import ctypes
-
-    from . import field
-    if not isinstance(grid, field.SkipGrid):
-        raise TypeError("run_network_train_skip: grid must be a field.SkipGrid")
-    split = split or None
-    if split not in (None, "f16x2"):
-        raise ValueError(f"run_network_train_skip: no training through the grid for args.mfma_split = {split!r} (f32 and 'f16x2' only)")
-    if not model._fused_ok():
-        raise ValueError("run_network_train_skip: training through the grid exists for the 8 x 256 network only")
+    from .networks import render
+    who = "run_network_train_skip"
+    split = render.check_skip_network(who, TRAIN_SKIP_WORDS, model, grid, split)
     bucket = int(bucket)
     if bucket < 1:
         raise ValueError(f"run_network_train_skip: bucket must be >= 1, got {bucket}")
     N, S = z.shape
-    if N * S >= 2 ** 31:
-        raise ValueError(f"run_network_train_skip: {N * S} samples do not fit the int32 selection; train on smaller batches")
-    rays_o, rays_d, z = _lib.f32(rays_o.reshape(-1, 3)).detach(), _lib.f32(rays_d.reshape(-1, 3)).detach(), _lib.f32(z).detach()
-    _lib.require_gpu(rays_o, rays_d, z)
-    dev = z.device
-    if grid.bits.device != dev:
-        raise RuntimeError("run_network_train_skip: the grid lives on another device than the rays")
-    if counts is not None:
-        _lib.require_gpu(counts)
-        if counts.dtype != torch.int64 or tuple(counts.shape) != (2,) or counts.device != dev or not counts.is_contiguous():
-            raise ValueError("run_network_train_skip: counts must be a contiguous int64 [2] tensor on the rays' device")
-    width = 4 + model.ins_num + 1
-    raw = torch.empty(N, S, width, dtype=torch.float32, device=dev)
+    rays_o, rays_d, z, raw, sel, count = render.skip_select(who, TRAIN_SKIP_WORDS, grid, rays_o, rays_d, z, 4 + model.ins_num + 1, 0.0, counts)
+    rays_o, rays_d, z, dev = rays_o.detach(), rays_d.detach(), z.detach(), z.device
     lib = _lib.load()
-    n_sel = 0
-    sel = None
-    if N * S:
-        sel = torch.empty(N * S, dtype=torch.int32, device=dev)
-        flag = torch.empty(N * S, dtype=torch.uint8, device=dev)
-        work = torch.empty(int(lib.dmnerf_skip_select_work_ints(N * S)), dtype=torch.int32, device=dev)
-        count = torch.empty(1, dtype=torch.int32, device=dev)
-        g = grid.c_struct()
-        _lib.check(lib.dmnerf_skip_select_fill(ctypes.byref(g), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z), N, S, _lib.ptr(flag),
-                                               _lib.ptr(sel), _lib.ptr(count), _lib.ptr(work), _lib.ptr(raw), _lib.ptr(_zero_row(width, dev)),
-                                               width, _lib.ptr(counts), _lib.stream()), "dmnerf_skip_select_fill")
-        n_sel = int(count.item())                                  # the host read: one synchronisation per call
+    n_sel = 0 if count is None else int(count.item())              # the host read: one synchronisation per call
     n_pad = -(-n_sel // bucket) * bucket
     o_c = torch.empty(n_pad, 3, dtype=torch.float32, device=dev)
     d_c = torch.empty(n_pad, 3, dtype=torch.float32, device=dev)
@@ -767,11 +724,7 @@ def run_network_train_skip(model, rays_o, rays_d, z, grid, split=None, check_f16
         _lib.check(lib.dmnerf_skip_gather_samples(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z), N, max(S, 1), _lib.ptr(sel), n_sel, n_pad,
                                                   _lib.ptr(o_c), _lib.ptr(d_c), _lib.ptr(z_c), _lib.stream()), "dmnerf_skip_gather_samples")
     mode = "f16" if split == "f16x2" else None
-    _check_f16_call[0] = None if check_f16 is None else bool(check_f16)
-    try:
-        raw_c = _run_network_train(model, o_c, d_c, z_c, mode)     # [n_pad, 1, width]; n_pad = 0: no launch, zero gradients
-    finally:
-        _check_f16_call[0] = None
+    raw_c = _run_network_train(model, o_c, d_c, z_c, mode, check_f16)     # [n_pad, 1, width]; n_pad = 0: no launch, zero gradients
     return ScatterRows.apply(raw_c, raw, sel, n_sel)
 
 
@@ -815,13 +768,13 @@ def dm_nerf_train(rays, model_coarse, model_fine, z_vals_coarse, args, t_rand=No
     shape other than 8 x 256 raise ``ValueError`` (there is no dense detour).  ``args.train_skip_counts`` (optional int64 ``[2]``
     device tensor per level name, a dict) receives ``+= (evaluated, samples)``; ``args.train_skip_bucket`` overrides the padding
     bucket of ``run_network_train_skip``."""
+    from .networks import render
     if skip is not None:
         from . import field
-        from .networks.render import check_skip_levels
         skip = skip.grid if isinstance(skip, field.TrainSkip) else skip
         if not isinstance(skip, field.SkipGrid):
             raise TypeError("dm_nerf_train: skip must be a field.SkipGrid or a field.TrainSkip")
-        skip_levels = check_skip_levels("dm_nerf_train", skip_levels)
+        skip_levels = render.check_skip_levels("dm_nerf_train", skip_levels)
         if bool(getattr(args, "fuse_heads", False)):
             raise ValueError("dm_nerf_train: no training through the grid with args.fuse_heads (f32 and mfma_split = 'f16x2' only)")
     rays_o, rays_d = rays
@@ -831,8 +784,8 @@ def dm_nerf_train(rays, model_coarse, model_fine, z_vals_coarse, args, t_rand=No
     N, S = z_in.shape
     n_imp = int(args.N_importance)
     perturb = float(args.perturb)
-    from .networks.render import check_draws             # RNG order of the reference: [N,S] then [N,n_imp]; shapes validated
-    t_rand, u, _ = check_draws(t_rand, u, N, S, n_imp, perturb, z_in.device)
+    # RNG order of the reference: [N,S] then [N,n_imp]; shapes validated
+    t_rand, u, _ = render.check_draws(t_rand, u, N, S, n_imp, perturb, z_in.device)
     z_coarse = helpers.stratify(z_in, t_rand) if t_rand is not None else z_in
     from . import weights
     fused, split = bool(getattr(args, "fuse_heads", False)), weights.split_mode(args)
@@ -862,9 +815,6 @@ def dm_nerf_train(rays, model_coarse, model_fine, z_vals_coarse, args, t_rand=No
             z_fine = helpers.importance_resample(z_coarse, weights_coarse.detach(), n_imp, det=(perturb == 0.), u=u)
     raw_fine = network("fine", model_fine, z_fine)
     rgb_fine, weights_fine, depth_fine, ins_fine = composite(raw_fine, z_fine)
-    if getattr(args, "is_train", False) and getattr(args, "N_ins", None) is not None:
-        ins_fine = ins_fine[-args.N_ins:]
-        ins_coarse = ins_coarse[-args.N_ins:]
-    return {'rgb_fine': rgb_fine, 'ins_fine': ins_fine, 'z_vals_fine': z_fine, 'raw_fine': raw_fine,
-            'raw_coarse': raw_coarse, 'rgb_coarse': rgb_coarse, 'ins_coarse': ins_coarse,
-            'z_vals_coarse': z_coarse, 'depth_fine': depth_fine, 'depth_coarse': depth_coarse}
+    return render.ins_slice({'rgb_fine': rgb_fine, 'ins_fine': ins_fine, 'z_vals_fine': z_fine, 'raw_fine': raw_fine,
+                             'raw_coarse': raw_coarse, 'rgb_coarse': rgb_coarse, 'ins_coarse': ins_coarse,
+                             'z_vals_coarse': z_coarse, 'depth_fine': depth_fine, 'depth_coarse': depth_coarse}, args)

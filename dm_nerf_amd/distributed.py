@@ -357,25 +357,12 @@ def _default_raygen(H, W, K, c2w, row0, nrows):
     return helpers.get_rays_k(H, W, K, c2w, row0=row0, nrows=nrows)
 
 
-def _default_render_chunk(rays_o, rays_d, z, models, args, events=None):
+def _render_chunk(rays_o, rays_d, z, models, args, events=None, entry=None, **kw):
+    """One chunk through the render entry ``entry`` with its keywords ``kw`` -> the three maps a frame keeps.  No entry: the frame
+    keeps the fine level only (tester.py:71-77), so where the density-only coarse pass exists, the coarse heads are skipped."""
     from .networks import render
-    # the frame keeps the fine level only (tester.py:71-77): where the density-only coarse pass exists, skip the coarse heads
-    fn = render.fine_renderer(models[0], models[1], args)
-    out = fn(torch.stack([rays_o, rays_d]), None, None, models[0], models[1], z, args, _events=events)
-    return out['rgb_fine'], out['ins_fine'], out['depth_fine']
-
-
-def _skip_render_chunk(rays_o, rays_d, z, models, args, events=None, grid=None, levels=("coarse", "fine")):
-    from .networks import render
-    out = render.dm_nerf_fine_skip(torch.stack([rays_o, rays_d]), None, None, models[0], models[1], z, args, grid, levels=levels,
-                                   _events=events)
-    return out['rgb_fine'], out['ins_fine'], out['depth_fine']
-
-
-def _mark_render_chunk(rays_o, rays_d, z, models, args, events=None, grid=None, threshold=0.0, levels=("coarse", "fine")):
-    from .networks import render
-    out = render.dm_nerf_fine_mark(torch.stack([rays_o, rays_d]), None, None, models[0], models[1], z, args, grid, threshold=threshold,
-                                   levels=levels, _events=events)
+    fn = entry or render.fine_renderer(models[0], models[1], args)
+    out = fn(torch.stack([rays_o, rays_d]), None, None, models[0], models[1], z, args, _events=events, **kw)
     return out['rgb_fine'], out['ins_fine'], out['depth_fine']
 
 
@@ -423,7 +410,9 @@ class FrameRenderer:
             if render_chunk is not None:
                 raise ValueError("FrameRenderer: skip= routes the chunks through dm_nerf_fine_skip; it cannot be combined with render_chunk=")
             import functools
-            render_chunk = functools.partial(_skip_render_chunk, grid=skip, levels=skip_levels)
+
+            from .networks import render
+            render_chunk = functools.partial(_render_chunk, entry=render.dm_nerf_fine_skip, grid=skip, levels=skip_levels)
         if mark is not None:
             # mark = a field.SkipGrid: the chunks go through render.dm_nerf_fine_mark -- the dense render, which also sets in the grid
             # the cells of the samples it gave a weight > mark_threshold.  This rank marks the rows of its own band.
@@ -432,8 +421,11 @@ class FrameRenderer:
             if render_chunk is not None:
                 raise ValueError("FrameRenderer: mark= routes the chunks through dm_nerf_fine_mark; it cannot be combined with render_chunk=")
             import functools
-            render_chunk = functools.partial(_mark_render_chunk, grid=mark, threshold=mark_threshold, levels=mark_levels)
-        self.render_chunk = render_chunk or _default_render_chunk
+
+            from .networks import render
+            render_chunk = functools.partial(_render_chunk, entry=render.dm_nerf_fine_mark, grid=mark, threshold=mark_threshold,
+                                             levels=mark_levels)
+        self.render_chunk = render_chunk or _render_chunk
         if z_fn is None:
             from .networks import helpers
             z_fn = lambda n, dev: helpers.z_val_sample(n, near, far, n_samples, device=dev)

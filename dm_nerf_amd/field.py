@@ -414,6 +414,20 @@ def _dims3(dims):
     return dims
 
 
+def _box(who, lo, hi, dims):
+    """The box of ``who`` (``SkipGrid`` / ``LabelGrid``) over ``dims`` (a ``_dims3``) -> float32 ``(lo, hi, cell, inv_cell)``."""
+    lo, hi = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
+    if not np.all(hi > lo):
+        raise ValueError(f"{who}: hi must be > lo on every axis")
+    cell = (hi - lo) / np.asarray(dims, dtype=np.float32)
+    return lo, hi, cell, np.float32(1.0) / cell
+
+
+def _axis_centres(grid, a, n0, n1, dev):
+    """The centres of cells ``n0 .. n1 - 1`` of ``grid`` along axis ``a`` on ``dev`` (f32 ops, one rounding each)."""
+    return (torch.arange(n0, n1, dtype=torch.float32, device=dev) + 0.5) * float(grid.cell[a]) + float(grid.lo[a])
+
+
 def or_gathered_words(gathered, world):
     """The bitwise OR over ranks of ``gathered [world * n_words]`` (the ranks' packed words, concatenated as
     ``distributed.all_gather_cat`` returns them) -> ``[n_words]``, same dtype and device.  Plain torch ops: the collective library
@@ -442,12 +456,7 @@ class SkipGrid:
 
     def __init__(self, lo, hi, dims, bits, outside="evaluate"):
         self.dims = _dims3(dims)
-        self.lo = np.asarray(lo, dtype=np.float32).reshape(3)
-        self.hi = np.asarray(hi, dtype=np.float32).reshape(3)
-        if not np.all(self.hi > self.lo):
-            raise ValueError("SkipGrid: hi must be > lo on every axis")
-        self.cell = (self.hi - self.lo) / np.asarray(self.dims, dtype=np.float32)
-        self.inv_cell = np.float32(1.0) / self.cell
+        self.lo, self.hi, self.cell, self.inv_cell = _box("SkipGrid", lo, hi, self.dims)
         if outside not in SKIP_OUTSIDE:
             raise ValueError(f"SkipGrid: outside must be 'evaluate' or 'empty', got {outside!r}")
         self.outside = outside
@@ -517,8 +526,7 @@ class SkipGrid:
         dx, dy, dz = self.dims
         i1 = dx if i1 is None else int(i1)
         dev = device or self.bits.device
-        ax = [(torch.arange(n0, n1, dtype=torch.float32, device=dev) + 0.5) * float(self.cell[a]) + float(self.lo[a])
-              for a, (n0, n1) in enumerate(((int(i0), i1), (0, dy), (0, dz)))]
+        ax = [_axis_centres(self, a, n0, n1, dev) for a, (n0, n1) in enumerate(((int(i0), i1), (0, dy), (0, dz)))]
         ni = i1 - int(i0)
         return torch.stack([ax[0][:, None, None].expand(ni, dy, dz), ax[1][None, :, None].expand(ni, dy, dz),
                             ax[2][None, None, :].expand(ni, dy, dz)], dim=-1).reshape(-1, 3)
@@ -681,8 +689,7 @@ def label_rays(occ, i0=0, i1=None):
     dx, dy, dz = occ.dims
     i1 = dx if i1 is None else int(i1)
     dev = occ.bits.device
-    ax = [(torch.arange(n0, n1, dtype=torch.float32, device=dev) + 0.5) * float(occ.cell[a]) + float(occ.lo[a])
-          for a, (n0, n1) in enumerate(((int(i0), i1), (0, dy), (0, 1)))]
+    ax = [_axis_centres(occ, a, n0, n1, dev) for a, (n0, n1) in enumerate(((int(i0), i1), (0, dy), (0, 1)))]
     ni = i1 - int(i0)
     o = torch.stack([ax[0][:, None].expand(ni, dy), ax[1][None, :].expand(ni, dy), ax[2][None, :].expand(ni, dy)], dim=-1).reshape(-1, 3)
     d = torch.zeros(ni * dy, 3, dtype=torch.float32, device=dev)
@@ -765,12 +772,7 @@ class LabelGrid:
         self.C = int(C)
         if not 1 <= self.C <= MAX_LABELS:
             raise ValueError(f"LabelGrid: C must be in [1, {MAX_LABELS}], got {self.C}")
-        self.lo = np.asarray(lo, dtype=np.float32).reshape(3)
-        self.hi = np.asarray(hi, dtype=np.float32).reshape(3)
-        if not np.all(self.hi > self.lo):
-            raise ValueError("LabelGrid: hi must be > lo on every axis")
-        self.cell = (self.hi - self.lo) / np.asarray(self.dims, dtype=np.float32)
-        self.inv_cell = np.float32(1.0) / self.cell
+        self.lo, self.hi, self.cell, self.inv_cell = _box("LabelGrid", lo, hi, self.dims)
         self.labels = labels
 
     @classmethod

@@ -5,6 +5,7 @@ the ranks), ``manipulator_eval`` (:208-364) is ``dm_nerf_amd.editing.manipulate_
 and coloured images) and ``manipulator_demo`` (:367-491) is ``dm_nerf_amd.editing.manipulate_demo_path`` (several objects per
 view, rigid or deformed).  File output and the pose JSON stay with the caller (LPIPS: ``manipulate_eval_path(..., lpips=evaluator.LPIPSVGG...)``)."""
 import ctypes
+from types import SimpleNamespace
 
 import torch
 
@@ -117,22 +118,25 @@ def manipulator_nerf(rays, position_embedder, view_embedder, model, N_samples=No
     return raw, z_vals
 
 
-def _skip_plan(model_coarse, model_fine, split, skip, skip_levels):
-    """-> the ``manipulator_nerf`` keywords of the coarse and of the fine model's calls.  Everything ``skip=`` cannot serve is refused
-    here, before the first launch."""
-    if skip is None:
-        return {}, {}
-    from .. import field
-    from . import render
-    if not isinstance(skip, field.SkipGrid):
-        raise TypeError("manipulator: skip must be a field.SkipGrid")
-    levels = render.check_skip_levels("manipulator", skip_levels)
-    if split not in (None, "f16x2"):
-        raise ValueError(f"manipulator: skip= has no sparse network kernel for args.mfma_split = {split!r} (f32 and 'f16x2' only)")
-    for name, model in (("coarse", model_coarse), ("fine", model_fine)):
-        if name in levels and not model._fused_ok():
-            raise ValueError(f"manipulator: skip= needs the 8 x 256 network at the {name} level (the sparse kernels exist for it only)")
-    return tuple({"skip": skip} if name in levels else {} for name in ("coarse", "fine"))
+def _skip_plan(model_coarse, model_fine, args, skip, skip_levels, skip_counts):
+    """-> the ``manipulator_nerf`` keywords of the coarse and of the fine model's calls: ``args.mfma_split``, the counts and, at the
+    levels ``skip=`` names, the grid.  Everything ``skip=`` cannot serve is refused here, before the first launch."""
+    from .. import weights
+    split = weights.split_mode(args)
+    kc = kf = {}
+    if skip is not None:
+        from .. import field
+        from . import render
+        if not isinstance(skip, field.SkipGrid):
+            raise TypeError("manipulator: skip must be a field.SkipGrid")
+        levels = render.check_skip_levels("manipulator", skip_levels)
+        if split not in (None, "f16x2"):
+            raise ValueError(f"manipulator: skip= has no sparse network kernel for args.mfma_split = {split!r} (f32 and 'f16x2' only)")
+        for name, model in (("coarse", model_coarse), ("fine", model_fine)):
+            if name in levels and not model._fused_ok():
+                raise ValueError(f"manipulator: skip= needs the 8 x 256 network at the {name} level (the sparse kernels exist for it only)")
+        kc, kf = ({"skip": skip} if name in levels else {} for name in ("coarse", "fine"))
+    return dict(kc, split=split, counts=skip_counts), dict(kf, split=split, counts=skip_counts)
 
 
 def sort_rows(x):
@@ -144,15 +148,34 @@ def sort_rows(x):
     return out
 
 
-def _manipulator_edit(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, kinds, keep_labels, skip=None,
-                      skip_levels=("coarse", "fine"), skip_counts=None):
+def _first_pass(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, kc, kf):
+    """Step 1 of ``manipulator``, with or without edit kinds: the original rays, then every target ray set, through coarse ->
+    resample -> fine -> accumulate.  One draw each, in that order (``us`` when given); ``draw`` makes the later ones."""
+    N_samples, N_importance, near, far = args.N_samples, args.N_importance, args.near, args.far
+    dev = ori_rays.device
+    Nr = ori_rays.shape[1]
+    us = list(us) if us is not None else None
+    draw = lambda: _lib.f32(us.pop(0)) if us is not None else torch.rand([Nr, N_importance], device=dev)
+    p = SimpleNamespace(draw=draw, tar_raws=[], f_tar_z=[], f_tar_zs=[], tar_ins_accums=[], tar_rgb=None, tar_ins_accum=None)
+    p.ori_raw, p.ori_z = manipulator_nerf(ori_rays, None, None, model_coarse, N_samples, near, far, **kc)
+    _, ori_w, _, _ = manipulator_render(p.ori_raw, p.ori_z, ori_rays[1])
+    ori_z_full = helpers.importance_resample(p.ori_z, ori_w, N_importance, u=draw())
+    ori_raw_full, _ = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z_full, **kf)
+    _, _, _, p.ori_ins_accum = manipulator_render(ori_raw_full, ori_z_full, ori_rays[1])
+    for tar_rays in f_tar_rays:
+        tar_raw, tar_z = manipulator_nerf(tar_rays, None, None, model_coarse, N_samples, near, far, **kc)
+        p.tar_raws.append(tar_raw); p.f_tar_z.append(tar_z)
+        p.tar_rgb, tar_w, _, _ = manipulator_render(tar_raw, tar_z, tar_rays[1])
+        tar_z_full, tar_zs = helpers.importance_resample(tar_z, tar_w, N_importance, u=draw(), return_samples=True)
+        tar_raw_full, _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z_full, **kf)
+        _, _, _, p.tar_ins_accum = manipulator_render(tar_raw_full, tar_z_full, tar_rays[1])
+        p.f_tar_zs.append(tar_zs); p.tar_ins_accums.append(p.tar_ins_accum)
+    return p
+
+
+def _manipulator_edit(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, kinds, keep_labels, kc, kf):
     """``manipulator`` with edit kinds: the chain below with ``edit_exchanger`` in place of ``exchanger``, the target side run for
     the ``T_r`` entries that have rays (MOVE and COPY) only, and the original's fine network on the merged depths evaluated once."""
-    from .. import weights
-    split = weights.split_mode(args)
-    kc, kf = _skip_plan(model_coarse, model_fine, split or None, skip, skip_levels)
-    kc, kf = dict(kc, split=split, counts=skip_counts), dict(kf, split=split, counts=skip_counts)
-    N_samples, N_importance, near, far = args.N_samples, args.N_importance, args.near, args.far
     labels = [int(v) for v in args.target_labels]
     kinds = [MOVE] * len(labels) if kinds is None else [int(k) for k in kinds]
     if len(kinds) != len(labels):
@@ -164,43 +187,26 @@ def _manipulator_edit(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, 
         raise ValueError(f"manipulator: {len(f_tar_rays)} target ray sets for {sum(has_rays)} MOVE / COPY entries")
     if not labels and keep_labels is None:
         raise ValueError("manipulator: no edit and no keep_labels")
-    dev = ori_rays.device
-    Nr = ori_rays.shape[1]
-    us = list(us) if us is not None else None
-    draw = lambda: _lib.f32(us.pop(0)) if us is not None else torch.rand([Nr, N_importance], device=dev)
-    ori_raw, ori_z = manipulator_nerf(ori_rays, None, None, model_coarse, N_samples, near, far, **kc)
-    _, ori_w, _, _ = manipulator_render(ori_raw, ori_z, ori_rays[1])
-    ori_z_full = helpers.importance_resample(ori_z, ori_w, N_importance, u=draw())
-    ori_raw_full, _ = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z_full, **kf)
-    _, _, _, ori_ins_accum = manipulator_render(ori_raw_full, ori_z_full, ori_rays[1])
-    tar_raws, f_tar_z, f_tar_zs, tar_ins_accums = [], [], [], []
-    tar_rgb = tar_ins_accum = None
-    for tar_rays in f_tar_rays:
-        tar_raw, tar_z = manipulator_nerf(tar_rays, None, None, model_coarse, N_samples, near, far, **kc)
-        tar_raws.append(tar_raw); f_tar_z.append(tar_z)
-        tar_rgb, tar_w, _, _ = manipulator_render(tar_raw, tar_z, tar_rays[1])
-        tar_z_full, tar_zs = helpers.importance_resample(tar_z, tar_w, N_importance, u=draw(), return_samples=True)
-        tar_raw_full, _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z_full, **kf)
-        _, _, _, tar_ins_accum = manipulator_render(tar_raw_full, tar_z_full, tar_rays[1])
-        f_tar_zs.append(tar_zs); tar_ins_accums.append(tar_ins_accum)
+    p = _first_pass(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, kc, kf)
+    ori_z, tar_raws, f_tar_zs, N_importance = p.ori_z, p.tar_raws, p.f_tar_zs, args.N_importance
 
     def per_edit(with_rays):                    # one slot per edit: the next ray entry's tensor, None for a REMOVE
         it = iter(with_rays)
         return [next(it) if h else None for h in has_rays]
-    accs = per_edit(tar_ins_accums)
-    ori_raw, _ = edit_exchanger(ori_raw, per_edit(tar_raws), ori_ins_accum, accs, labels, kinds, keep_labels, want_label=False)
+    accs = per_edit(p.tar_ins_accums)
+    ori_raw, _ = edit_exchanger(p.ori_raw, per_edit(tar_raws), p.ori_ins_accum, accs, labels, kinds, keep_labels, want_label=False)
     _, ori_w, _, _ = manipulator_render(ori_raw, ori_z, ori_rays[1])
-    _, ori_zs = helpers.importance_resample(ori_z, ori_w, N_importance, u=draw(), return_samples=True)
+    _, ori_zs = helpers.importance_resample(ori_z, ori_w, N_importance, u=p.draw(), return_samples=True)
     ori_z = sort_rows(torch.cat([ori_z, ori_zs] + f_tar_zs, dim=-1))
     ori_raw, _ = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z, **kf)
     for idx, tar_rays in enumerate(f_tar_rays):
-        tar_z = sort_rows(torch.cat([f_tar_z[idx], ori_zs] + f_tar_zs, dim=-1))
+        tar_z = sort_rows(torch.cat([p.f_tar_z[idx], ori_zs] + f_tar_zs, dim=-1))
         tar_raws[idx], _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z, **kf)
-    ori_raw, _ = edit_exchanger(ori_raw, per_edit(tar_raws), ori_ins_accum, accs, labels, kinds, keep_labels, want_label=False)
+    ori_raw, _ = edit_exchanger(ori_raw, per_edit(tar_raws), p.ori_ins_accum, accs, labels, kinds, keep_labels, want_label=False)
     final_rgb, _, _, final_ins = manipulator_render(ori_raw, ori_z, ori_rays[1])
     if not f_tar_rays:
-        tar_rgb, tar_ins_accum = torch.zeros_like(final_rgb), torch.zeros_like(final_ins)
-    return final_rgb, final_ins, tar_rgb, tar_ins_accum
+        return final_rgb, final_ins, torch.zeros_like(final_rgb), torch.zeros_like(final_ins)
+    return final_rgb, final_ins, p.tar_rgb, p.tar_ins_accum
 
 
 def manipulator(position_embedder, view_embedder, model_coarse, model_fine, ori_rays, f_tar_rays, args, us=None, kinds=None,
@@ -229,44 +235,21 @@ def manipulator(position_embedder, view_embedder, model_coarse, model_fine, ori_
     shape other than 8 x 256 at a named level raise ``ValueError`` (no dense detour).  ``skip_counts``: optional int64 ``[2]`` device
     tensor, += (samples evaluated, samples) over the calls that went through the grid.
     """
+    kc, kf = _skip_plan(model_coarse, model_fine, args, skip, skip_levels, skip_counts)
     if kinds is not None or keep_labels is not None:
-        return _manipulator_edit(model_coarse, model_fine, ori_rays, list(f_tar_rays), args, us, kinds, keep_labels, skip=skip,
-                                 skip_levels=skip_levels, skip_counts=skip_counts)
-    from .. import weights
-    split = weights.split_mode(args)
-    kc, kf = _skip_plan(model_coarse, model_fine, split or None, skip, skip_levels)
-    kc, kf = dict(kc, split=split, counts=skip_counts), dict(kf, split=split, counts=skip_counts)
-    N_samples, N_importance, near, far = args.N_samples, args.N_importance, args.near, args.far
-    dev = ori_rays.device
-    Nr = ori_rays.shape[1]
-    us = list(us) if us is not None else None
-    draw = lambda: _lib.f32(us.pop(0)) if us is not None else torch.rand([Nr, N_importance], device=dev)
-    pe, ve = position_embedder, view_embedder
-    ori_raw, ori_z = manipulator_nerf(ori_rays, pe, ve, model_coarse, N_samples, near, far, **kc)
-    _, ori_w, _, _ = manipulator_render(ori_raw, ori_z, ori_rays[1])
-    ori_z_full = helpers.importance_resample(ori_z, ori_w, N_importance, u=draw())
-    ori_raw_full, _ = manipulator_nerf(ori_rays, pe, ve, model_fine, z_vals=ori_z_full, **kf)
-    _, _, _, ori_ins_accum = manipulator_render(ori_raw_full, ori_z_full, ori_rays[1])
-    tar_raws, f_tar_z, f_tar_zs, tar_ins_accums = [], [], [], []
-    tar_rgb = tar_ins_accum = None
-    for tar_rays in f_tar_rays:
-        tar_raw, tar_z = manipulator_nerf(tar_rays, pe, ve, model_coarse, N_samples, near, far, **kc)
-        tar_raws.append(tar_raw); f_tar_z.append(tar_z)
-        tar_rgb, tar_w, _, _ = manipulator_render(tar_raw, tar_z, tar_rays[1])
-        tar_z_full, tar_zs = helpers.importance_resample(tar_z, tar_w, N_importance, u=draw(), return_samples=True)
-        tar_raw_full, _ = manipulator_nerf(tar_rays, pe, ve, model_fine, z_vals=tar_z_full, **kf)
-        _, _, _, tar_ins_accum = manipulator_render(tar_raw_full, tar_z_full, tar_rays[1])
-        f_tar_zs.append(tar_zs); tar_ins_accums.append(tar_ins_accum)
-    ori_raw, _, _, _ = exchanger(ori_raw, tar_raws, ori_ins_accum, tar_ins_accums, args.target_labels)
+        return _manipulator_edit(model_coarse, model_fine, ori_rays, list(f_tar_rays), args, us, kinds, keep_labels, kc, kf)
+    p = _first_pass(model_coarse, model_fine, ori_rays, f_tar_rays, args, us, kc, kf)
+    ori_z, tar_raws, N_importance = p.ori_z, p.tar_raws, args.N_importance
+    ori_raw, _, _, _ = exchanger(p.ori_raw, tar_raws, p.ori_ins_accum, p.tar_ins_accums, args.target_labels)
     # step 2: re-render the edited coarse field, resample, and evaluate the fine model on the merged depths
     _, ori_w, _, _ = manipulator_render(ori_raw, ori_z, ori_rays[1])
-    _, ori_zs = helpers.importance_resample(ori_z, ori_w, N_importance, u=draw(), return_samples=True)
-    f_tar_zs = torch.cat(f_tar_zs, dim=-1)
+    _, ori_zs = helpers.importance_resample(ori_z, ori_w, N_importance, u=p.draw(), return_samples=True)
+    f_tar_zs = torch.cat(p.f_tar_zs, dim=-1)
     ori_z = sort_rows(torch.cat([ori_z, ori_zs, f_tar_zs], dim=-1))
     for idx, tar_rays in enumerate(f_tar_rays):
-        ori_raw, ori_z = manipulator_nerf(ori_rays, pe, ve, model_fine, z_vals=ori_z, **kf)
-        tar_z = sort_rows(torch.cat([f_tar_z[idx], ori_zs, f_tar_zs], dim=-1))
-        tar_raws[idx], _ = manipulator_nerf(tar_rays, pe, ve, model_fine, z_vals=tar_z, **kf)
-    ori_raw, _, _, _ = exchanger(ori_raw, tar_raws, ori_ins_accum, tar_ins_accums, args.target_labels)
+        ori_raw, ori_z = manipulator_nerf(ori_rays, None, None, model_fine, z_vals=ori_z, **kf)
+        tar_z = sort_rows(torch.cat([p.f_tar_z[idx], ori_zs, f_tar_zs], dim=-1))
+        tar_raws[idx], _ = manipulator_nerf(tar_rays, None, None, model_fine, z_vals=tar_z, **kf)
+    ori_raw, _, _, _ = exchanger(ori_raw, tar_raws, p.ori_ins_accum, p.tar_ins_accums, args.target_labels)
     final_rgb, _, _, final_ins = manipulator_render(ori_raw, ori_z, ori_rays[1])
-    return final_rgb, final_ins, tar_rgb, tar_ins_accum
+    return final_rgb, final_ins, p.tar_rgb, p.tar_ins_accum
