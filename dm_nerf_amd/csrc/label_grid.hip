@@ -11,6 +11,8 @@
 //                                 walk over ALL C logits behind a sigmoid (argmax_sigmoid, render_kernels.hip), which is monotone:
 //                                 a cell labelled k is a cell whose centre sample the manipulation render treats as object k
 //                                 (they can differ only where two unequal logits round to one f32 sigmoid, both above ~17).
+//   dmnerf_bake_cells             dmnerf_label_cells, and cells[m, 0:4] = raw[m, 0:4] bit for bit for a labelled row, four zeros for an
+//                                 unlabelled one: the colour logits and the density that csrc/baked.hip composites along rays.
 //   dmnerf_label_stats            per label l < C over labels [dx, dy, dz]: the number of cells, the sums of their i, j and k, the
 //                                 smallest index and the largest index + 1 per axis.  Labels >= C (255 included) are ignored.
 //   dmnerf_skip_grid_from_labels  bit g = labels[g] < 128 and bit labels[g] of a 128-bit mask: SkipGrid's words (skip.hip).
@@ -34,11 +36,7 @@ constexpr int RUN = 16;                       // cells per lane and step of the 
 constexpr int STATS_MAX_BLOCKS = 2048;        // the stats grid; beyond it a workgroup strides
 
 // ---- labels.  One sample per lane; a row is 4 + C <= 132 floats.
-__global__ __launch_bounds__(BLOCK) void label_cells_kernel(const float* __restrict__ raw, int64_t M, int C, float sigma_threshold,
-                                                            uint8_t* __restrict__ labels) {
-    const int64_t m = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (m >= M) return;
-    const float* x = raw + m * (4 + C);
+__device__ __forceinline__ int label_of_row(const float* __restrict__ x, int C, float sigma_threshold) {
     int best = UNLABELLED;
     if (x[3] > sigma_threshold) {             // (false for NaN)
         best = 0;
@@ -48,7 +46,32 @@ __global__ __launch_bounds__(BLOCK) void label_cells_kernel(const float* __restr
             if (v > bv) { bv = v; best = c; }
         }
     }
+    return best;
+}
+
+__global__ __launch_bounds__(BLOCK) void label_cells_kernel(const float* __restrict__ raw, int64_t M, int C, float sigma_threshold,
+                                                            uint8_t* __restrict__ labels) {
+    const int64_t m = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (m >= M) return;
+    labels[m] = (uint8_t)label_of_row(raw + m * (4 + C), C, sigma_threshold);
+}
+
+// The same rule, and what the row says about colour and density kept next to the label: the row's first four words (three colour
+// logits, sigma) as they are for a labelled cell, zeros for an unlabelled one; one 16-byte store per row.  (The words travel as
+// integers: a NaN keeps its payload.)
+__global__ __launch_bounds__(BLOCK) void bake_cells_kernel(const float* __restrict__ raw, int64_t M, int C, float sigma_threshold,
+                                                           uint8_t* __restrict__ labels, uint4* __restrict__ cells) {
+    const int64_t m = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (m >= M) return;
+    const float* x = raw + m * (4 + C);
+    const int best = label_of_row(x, C, sigma_threshold);
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (best != UNLABELLED) {
+        const uint32_t* u = reinterpret_cast<const uint32_t*>(x);
+        v = make_uint4(u[0], u[1], u[2], u[3]);
+    }
     labels[m] = (uint8_t)best;
+    cells[m] = v;
 }
 
 // ---- stats
@@ -223,6 +246,21 @@ extern "C" int dmnerf_label_cells(const float* d_raw, int64_t M, int C, float si
     if (!d_raw || !d_labels) return dmn_fail(DMNERF_E_ARG, "label_cells: null pointer");
     hipLaunchKernelGGL(label_cells_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, (hipStream_t)stream, d_raw, M, C, sigma_threshold, d_labels);
     return dmn_check_launch("label_cells");
+}
+
+extern "C" int dmnerf_bake_cells(const float* d_raw, int64_t M, int C, float sigma_threshold, uint8_t* d_labels, float* d_cells,
+                                 void* stream) {
+    if (C < 1 || C > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "bake_cells: C=%d outside 1..%d", C, DMNERF_MAX_LOGITS);
+    if (M < 0) return dmn_fail(DMNERF_E_ARG, "bake_cells: bad M=%lld", (long long)M);
+    if (!(sigma_threshold >= 0.f)) return dmn_fail(DMNERF_E_ARG, "bake_cells: sigma_threshold %g must be >= 0", (double)sigma_threshold);
+    const int64_t nb = (M + BLOCK - 1) / BLOCK;
+    if (nb > 0x7fffffffLL) return dmn_fail(DMNERF_E_ARG, "bake_cells: %lld samples is too many for one launch", (long long)M);
+    if (M == 0) return DMNERF_OK;
+    if (!d_raw || !d_labels || !d_cells) return dmn_fail(DMNERF_E_ARG, "bake_cells: null pointer");
+    if ((uintptr_t)d_cells & 15) return dmn_fail(DMNERF_E_ARG, "bake_cells: d_cells must be 16-byte aligned");
+    hipLaunchKernelGGL(bake_cells_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, (hipStream_t)stream, d_raw, M, C, sigma_threshold, d_labels,
+                       reinterpret_cast<uint4*>(d_cells));
+    return dmn_check_launch("bake_cells");
 }
 
 extern "C" int dmnerf_label_stats(const uint8_t* d_labels, int dx, int dy, int dz, int C, int64_t* d_count, int64_t* d_index_sum,

@@ -33,6 +33,7 @@
 
 #include "../../include/dmnerf_hip.h"
 #include "common.h"
+#include "label_walk.h"                       // TraceGrid, nan_min / nan_max, plane_of
 
 namespace {
 
@@ -40,20 +41,9 @@ constexpr int BLOCK = 64;
 constexpr int MAX_SETS = 16;
 constexpr int UNLABELLED = 255;
 
-struct TraceGrid {
-    float lo[3], cell[3], inv_cell[3];
-    int dims[3];
-};
-
 struct TraceMasks {
     uint32_t w[MAX_SETS * 4];
 };
-
-// minimum and maximum that hand a NaN operand on (fminf / fmaxf drop it)
-__device__ __forceinline__ float nan_min(float x, float y) { return (x < y || x != x) ? x : y; }
-__device__ __forceinline__ float nan_max(float x, float y) { return (x > y || x != x) ? x : y; }
-
-__device__ __forceinline__ float plane_of(float lo, float cell, int b) { return __fadd_rn(lo, __fmul_rn((float)b, cell)); }
 
 __global__ __launch_bounds__(BLOCK) void label_trace_kernel(const uint8_t* __restrict__ labels, TraceGrid G, int C,
                                                             const float* __restrict__ rays, int R, int64_t N, TraceMasks M,

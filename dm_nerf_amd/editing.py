@@ -238,6 +238,48 @@ def pick(label_grid, H, W, K, pose, pixels, near, far, labels=None):
     return label, t, point, cell
 
 
+def _preview_sets(who, label_grid, H, W, K, pose, trans_list, target_labels, keep_labels, max_sets=None):
+    """The rays and label sets of an edit preview (``preview_frame``'s docstring) -> ``(rays [R, 2, H W, 3], R label sets)``: set 0 the
+    original rays of ``ManipulationFrameRenderer`` with every label but those of MOVE and REMOVE entries, set ``1 + e`` the target rays
+    of the e-th entry with rays and its own label; with ``keep_labels`` every set is intersected with it.  ``max_sets``: more sets
+    raise ``ValueError``.  The argument checks come before anything touches a device."""
+    import types
+    C = label_grid.C
+    trans_list, target_labels = list(trans_list), [int(l) for l in target_labels]
+    if len(trans_list) != len(target_labels):
+        raise ValueError(f"{who}: {len(target_labels)} target labels for {len(trans_list)} edits")
+    keep = None if keep_labels is None else sorted({int(l) for l in keep_labels})
+    for l in target_labels + (keep or []):
+        if not 0 <= l < C:
+            raise ValueError(f"{who}: label {l} outside [0, {C})")
+    kinds = [edit_kind(trans) for trans in trans_list]
+    with_rays = sum(k != 2 for k in kinds)
+    if max_sets is not None and 1 + with_rays > max_sets:
+        raise ValueError(f"{who}: {with_rays} edits with rays, at most {max_sets - 1} (one launch composites {max_sets} ray sets)")
+    args = types.SimpleNamespace(N_importance=0, target_labels=target_labels)
+    pose = torch.as_tensor(pose, dtype=torch.float32).cpu()                         # host data: 12 floats into the ray kernels' arguments
+    fr = D.ManipulationFrameRenderer(H, W, K, pose, trans_list, None, args, ins_num=C - 1, rank=0, world=1,
+                                     keep_labels=keep if (keep is not None or trans_list) else ())
+    if fr.ori.device != label_grid.labels.device:
+        raise RuntimeError(f"{who}: the label volume lives on another device than the rays")
+    allowed = set(range(C)) if keep is None else set(keep)
+    gone = {l for l, k in zip(target_labels, kinds) if k != 1}                      # MOVE and REMOVE: not where it was
+    sets = [sorted(allowed - gone)] + [[l] if l in allowed else [] for l, k in zip(target_labels, kinds) if k != 2]
+    rays = torch.cat([fr.ori[None], fr.tar], dim=0) if fr.T else fr.ori[None]
+    return rays, sets
+
+
+def _preview_colours(who, label, lut, C):
+    """``lut[label]`` uint8 ``[H, W, 3]``, black where ``label == 255``; ``None`` without ``lut``."""
+    if lut is None:
+        return None
+    _lib.require_gpu(lut)
+    if lut.dtype != torch.uint8 or lut.dim() != 2 or lut.shape[1] != 3 or lut.shape[0] < C:
+        raise ValueError(f"{who}: lut must be uint8 [>= {C}, 3], got {lut.dtype} {tuple(lut.shape)}")
+    hit = label != 255
+    return lut[torch.where(hit, label, torch.zeros_like(label)).long()] * hit[..., None].to(torch.uint8)
+
+
 def preview_frame(label_grid, H, W, K, pose, trans_list=(), target_labels=(), keep_labels=None, near=0.0, far=float("inf"), lut=None):
     """What an edit does to a frame, from the label volume alone: ``label`` uint8 ``[H, W]`` (255: nothing), ``depth`` f32 ``[H, W]``
     (the hit's ``t``, ``+inf`` on a miss), ``source`` uint8 ``[H, W]`` (0: the original rays, ``1 + e``: the target rays of the e-th
@@ -253,40 +295,39 @@ def preview_frame(label_grid, H, W, K, pose, trans_list=(), target_labels=(), ke
     is the original one under an affine map), so the smallest ``t`` over the sets is the nearest surface along the pixel.
 
     A hard-surface proxy: the first labelled cell, no transmittance, no colour; how well it agrees with ``argmax`` of
-    ``manipulate_frame`` on a trained field is not measured.  Nothing reaches the host: with matrices (the poses are
+    ``manipulate_frame`` is measured on the analytic scene only; ``render_preview`` composites instead.  Nothing reaches the host: with matrices (the poses are
     host data) it can be captured in a graph after a warm-up call and follows ``label_grid.labels`` on replay; a ``Deform`` uploads
     its offset table on every call."""
-    import types
     H, W = int(H), int(W)
-    C = label_grid.C
-    trans_list, target_labels = list(trans_list), [int(l) for l in target_labels]
-    if len(trans_list) != len(target_labels):
-        raise ValueError(f"preview_frame: {len(target_labels)} target labels for {len(trans_list)} edits")
-    keep = None if keep_labels is None else sorted({int(l) for l in keep_labels})
-    for l in target_labels + (keep or []):
-        if not 0 <= l < C:
-            raise ValueError(f"preview_frame: label {l} outside [0, {C})")
-    kinds = [edit_kind(trans) for trans in trans_list]
-    args = types.SimpleNamespace(N_importance=0, target_labels=target_labels)
-    pose = torch.as_tensor(pose, dtype=torch.float32).cpu()                         # host data: 12 floats into the ray kernels' arguments
-    fr = D.ManipulationFrameRenderer(H, W, K, pose, trans_list, None, args, ins_num=C - 1, rank=0, world=1,
-                                     keep_labels=keep if (keep is not None or trans_list) else ())
-    if fr.ori.device != label_grid.labels.device:
-        raise RuntimeError("preview_frame: the label volume lives on another device than the rays")
-    allowed = set(range(C)) if keep is None else set(keep)
-    gone = {l for l, k in zip(target_labels, kinds) if k != 1}                      # MOVE and REMOVE: not where it was
-    sets = [sorted(allowed - gone)] + [[l] if l in allowed else [] for l, k in zip(target_labels, kinds) if k != 2]
-    rays = torch.cat([fr.ori[None], fr.tar], dim=0) if fr.T else fr.ori[None]
+    rays, sets = _preview_sets("preview_frame", label_grid, H, W, K, pose, trans_list, target_labels, keep_labels)
     out = label_grid.trace_sets(rays, sets, near, far)
     label = out["label"].reshape(H, W)
-    ins_img = None
-    if lut is not None:
-        _lib.require_gpu(lut)
-        if lut.dtype != torch.uint8 or lut.dim() != 2 or lut.shape[1] != 3 or lut.shape[0] < C:
-            raise ValueError(f"preview_frame: lut must be uint8 [>= {C}, 3], got {lut.dtype} {tuple(lut.shape)}")
-        hit = label != 255
-        ins_img = lut[torch.where(hit, label, torch.zeros_like(label)).long()] * hit[..., None].to(torch.uint8)
+    ins_img = _preview_colours("preview_frame", label, lut, label_grid.C)
     return {"label": label, "depth": out["t"].reshape(H, W), "source": out["source"].reshape(H, W), "ins_img": ins_img}
+
+
+def render_preview(baked, H, W, K, pose, trans_list=(), target_labels=(), keep_labels=None, near=0.0, far=float("inf"), stop=0.0, lut=None):
+    """``preview_frame`` with colour and transmittance, from a ``field.BakedGrid``: the same rays and the same label sets, but ONE
+    ``dmnerf_baked_render`` that volume-renders the baked cells of every set along the pixel instead of stopping at the first one
+    (``BakedGrid.render_sets``).  Returns ``rgb`` f32 ``[H, W, 3]``, ``depth`` f32 ``[H, W]`` (the weighted ``t``, 0 on a miss), ``acc``
+    f32 ``[H, W]``, ``label`` / ``source`` uint8 ``[H, W]`` (those of the heaviest segment; 255: nothing), ``nseg`` int32 ``[H, W]`` and
+    ``ins_img`` as ``preview_frame`` makes it, all on the device.
+
+    Matrices, ``Deform``, ``Remove``, ``Copy`` and ``keep_labels`` work as there.  The kernel keeps every set's walk in registers and
+    takes at most 4 ray sets, so more than three entries with rays raise ``ValueError`` (``Remove`` entries have none).  ``stop``: a
+    pixel ends once its transmittance is below it.  Still a proxy: one colour per cell, baked for one view direction
+    (``field.bake_grid``), piecewise constant density, no background; DESIGN.md 8a has the measured agreement with rendered frames
+    on the analytic scene.  Graph capture as for ``preview_frame``; a replay follows ``baked.labels`` and ``baked.cells``."""
+    from . import field
+    H, W, stop = int(H), int(W), float(stop)
+    if not stop >= 0.0:
+        raise ValueError(f"render_preview: stop must be >= 0, got {stop}")
+    rays, sets = _preview_sets("render_preview", baked, H, W, K, pose, trans_list, target_labels, keep_labels, max_sets=field.MAX_RENDER_SETS)
+    out = baked.render_sets(rays, sets, near, far, stop)
+    label = out["label"].reshape(H, W)
+    return {"rgb": out["rgb"].reshape(H, W, 3), "depth": out["depth"].reshape(H, W), "acc": out["acc"].reshape(H, W), "label": label,
+            "source": out["source"].reshape(H, W), "nseg": out["nseg"].reshape(H, W),
+            "ins_img": _preview_colours("render_preview", label, lut, baked.C)}
 
 
 def _render(H, W, K, pose, edits, models, args, frame_kw):

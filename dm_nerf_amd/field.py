@@ -678,6 +678,7 @@ class TrainSkip:
 UNLABELLED = 255
 MAX_LABELS = 128                # DMNERF_MAX_LOGITS (include/dmnerf_hip.h)
 MAX_TRACE_SETS = 16             # ray sets of one dmnerf_label_trace
+MAX_RENDER_SETS = 4             # ray sets of one dmnerf_baked_render
 
 
 def label_rays(occ, i0=0, i1=None):
@@ -731,6 +732,36 @@ def _check_label_points(occ):
                              f"dims {occ.dims})")
 
 
+def _label_loop(who, model_fine, occ, sigma_threshold, slab, split, bake):
+    """The loop of ``label_grid`` and ``bake_grid`` -> ``(labels, cells or None, C)``: the fine network at the label points of whole
+    i-planes, then ``dmnerf_label_cells`` or, with ``bake``, ``dmnerf_bake_cells`` (the same labels, and ``cells [dx, dy, dz, 4]``)."""
+    sigma_threshold = float(sigma_threshold)
+    if not sigma_threshold >= 0.0:
+        raise ValueError(f"{who}: sigma_threshold must be >= 0, got {sigma_threshold}")
+    if not isinstance(occ, SkipGrid):
+        raise TypeError(f"{who}: occ must be a SkipGrid")
+    slab = int(slab)
+    if slab < 1:
+        raise ValueError("slab must be >= 1")
+    _check_label_points(occ)
+    dx, dy, dz = occ.dims
+    C = model_fine.ins_num + 1
+    labels = torch.empty(dx, dy, dz, dtype=torch.uint8, device=occ.bits.device)
+    cells = torch.empty(dx, dy, dz, 4, dtype=torch.float32, device=occ.bits.device) if bake else None
+    lib, step = _lib.load(), max(1, slab // (dy * dz))
+    for i0 in range(0, dx, step):
+        i1 = min(i0 + step, dx)
+        o, d, z = label_rays(occ, i0, i1)
+        raw = R.run_network_skip(model_fine, o, d, z, occ, split=split)
+        m = (i1 - i0) * dy * dz
+        if bake:
+            _lib.check(lib.dmnerf_bake_cells(_lib.ptr(raw), m, C, sigma_threshold, _lib.ptr(labels[i0:i1]), _lib.ptr(cells[i0:i1]),
+                                             _lib.stream()), "dmnerf_bake_cells")
+        else:
+            _lib.check(lib.dmnerf_label_cells(_lib.ptr(raw), m, C, sigma_threshold, _lib.ptr(labels[i0:i1]), _lib.stream()), "dmnerf_label_cells")
+    return labels, cells, C
+
+
 def label_grid(model_fine, occ, sigma_threshold=0.0, slab=1 << 20, split=None):
     """Which object owns each cell of ``occ`` (a ``SkipGrid``) -> ``LabelGrid`` with its box and dims: the fine network at the label
     point of every set cell (``label_rays``), through ``render.run_network_skip`` -- clear cells get the empty row and are not
@@ -739,24 +770,7 @@ def label_grid(model_fine, occ, sigma_threshold=0.0, slab=1 << 20, split=None):
     ``occ.outside`` plays no part.  In slabs of whole i-planes of about ``slab`` cells; nothing reaches the host, so after one warm-up
     call it can be captured in a graph and follows ``occ.bits`` on replay.  ``split``, the network shape and device errors are what
     ``run_network_skip`` raises; ``sigma_threshold < 0`` or NaN raises ``ValueError``."""
-    sigma_threshold = float(sigma_threshold)
-    if not sigma_threshold >= 0.0:
-        raise ValueError(f"label_grid: sigma_threshold must be >= 0, got {sigma_threshold}")
-    if not isinstance(occ, SkipGrid):
-        raise TypeError("label_grid: occ must be a SkipGrid")
-    slab = int(slab)
-    if slab < 1:
-        raise ValueError("slab must be >= 1")
-    _check_label_points(occ)
-    dx, dy, dz = occ.dims
-    C = model_fine.ins_num + 1
-    labels = torch.empty(dx, dy, dz, dtype=torch.uint8, device=occ.bits.device)
-    fn, step = _lib.load().dmnerf_label_cells, max(1, slab // (dy * dz))
-    for i0 in range(0, dx, step):
-        i1 = min(i0 + step, dx)
-        o, d, z = label_rays(occ, i0, i1)
-        raw = R.run_network_skip(model_fine, o, d, z, occ, split=split)
-        _lib.check(fn(_lib.ptr(raw), (i1 - i0) * dy * dz, C, sigma_threshold, _lib.ptr(labels[i0:i1]), _lib.stream()), "dmnerf_label_cells")
+    labels, _, C = _label_loop("label_grid", model_fine, occ, sigma_threshold, slab, split, bake=False)
     return LabelGrid(labels, occ.lo, occ.hi, C)
 
 
@@ -815,6 +829,22 @@ class LabelGrid:
         return g.dilated(dilate) if int(dilate) else g
 
     # ---- rays through the volume (csrc/label_trace.hip; tests/_label_trace_restate.py states it in numpy)
+    def _ray_sets(self, who, rays, label_sets, max_sets):
+        """What ``trace_sets`` and ``BakedGrid.render_sets`` check of ``rays [R <= max_sets, 2, N, 3]`` and ``label_sets`` -> ``(R, N,
+        the 4 R mask words)``."""
+        if not torch.is_tensor(rays) or rays.dtype != torch.float32:
+            raise ValueError(f"{who}: rays must be a float32 tensor")
+        _lib.require_gpu(rays)
+        if rays.dim() != 4 or rays.shape[1] != 2 or rays.shape[3] != 3 or not 1 <= rays.shape[0] <= max_sets:
+            raise ValueError(f"{who} expects rays [R <= {max_sets}, 2, N, 3], got {tuple(rays.shape)}")
+        if rays.device != self.labels.device:
+            raise RuntimeError(f"{who}: the volume lives on another device than the rays")
+        R, _, N, _ = rays.shape
+        label_sets = list(label_sets)
+        if len(label_sets) != R:
+            raise ValueError(f"{who}: {len(label_sets)} label sets for {R} ray sets")
+        return R, N, [w for labels in label_sets for w in label_mask_words(labels, self.C)]
+
     def trace_sets(self, rays, label_sets, near, far):
         """The first cell along every ray whose label is in the ray set's own label set -> ``{"label" [N] uint8, "t" [N] f32, "cell" [N]
         int32, "source" [N] uint8}`` on the device.  ``rays [R, 2, N, 3]`` f32: ``R <= 16`` sets of N (origin, direction) pairs, the
@@ -824,18 +854,7 @@ class LabelGrid:
         The traversal is exact, cell by cell, between ``near`` and ``far`` (``dmnerf_label_trace``); label 255 and labels ``>= C`` are
         never hit.  One launch, nothing reaches the host: after a warm-up call it can be captured in a graph and follows ``labels`` on
         replay."""
-        if not torch.is_tensor(rays) or rays.dtype != torch.float32:
-            raise ValueError("LabelGrid.trace_sets: rays must be a float32 tensor")
-        _lib.require_gpu(rays)
-        if rays.dim() != 4 or rays.shape[1] != 2 or rays.shape[3] != 3 or not 1 <= rays.shape[0] <= MAX_TRACE_SETS:
-            raise ValueError(f"LabelGrid.trace_sets expects rays [R <= {MAX_TRACE_SETS}, 2, N, 3], got {tuple(rays.shape)}")
-        if rays.device != self.labels.device:
-            raise RuntimeError("LabelGrid.trace_sets: the volume lives on another device than the rays")
-        R, _, N, _ = rays.shape
-        label_sets = list(label_sets)
-        if len(label_sets) != R:
-            raise ValueError(f"LabelGrid.trace_sets: {len(label_sets)} label sets for {R} ray sets")
-        words = [w for labels in label_sets for w in label_mask_words(labels, self.C)]
+        R, N, words = self._ray_sets("LabelGrid.trace_sets", rays, label_sets, MAX_TRACE_SETS)
         dev = rays.device
         out = {"label": torch.empty(N, dtype=torch.uint8, device=dev), "t": torch.empty(N, dtype=torch.float32, device=dev),
                "cell": torch.empty(N, dtype=torch.int32, device=dev), "source": torch.empty(N, dtype=torch.uint8, device=dev)}
@@ -859,3 +878,76 @@ class LabelGrid:
         out = self.trace_sets(torch.stack([rays_o, rays_d])[None], [range(self.C) if labels is None else labels], near, far)
         del out["source"]
         return out
+
+
+# ---- the baked field volume (csrc/label_grid.hip dmnerf_bake_cells, csrc/baked.hip; tests/_baked_restate.py states the render in numpy)
+def bake_grid(model_fine, occ, sigma_threshold=0.0, slab=1 << 20, split=None):
+    """``label_grid`` that keeps what the network said about colour and density -> ``BakedGrid``: the same loop with
+    ``dmnerf_bake_cells`` in place of ``dmnerf_label_cells``, so ``.labels`` equals ``label_grid(...)``'s and ``.cells[i, j, k]`` is
+    the first four floats of the cell's network row (three colour logits, sigma) for a labelled cell, zeros for an unlabelled one.
+    The baked colour is the field's colour for the label rays' view direction, +z of the box (``label_rays``: ``d = (0, 0, cell_z)``);
+    baking for another direction is out of scope.  Same arguments, same errors and the same graph-capture property as ``label_grid``."""
+    labels, cells, C = _label_loop("bake_grid", model_fine, occ, sigma_threshold, slab, split, bake=True)
+    return BakedGrid(labels, cells, occ.lo, occ.hi, C)
+
+
+class BakedGrid(LabelGrid):
+    """A ``LabelGrid`` with ``cells``: f32 ``[dx, dy, dz, 4]`` on the labels' device, per cell three colour logits and the density.
+    Everything ``LabelGrid`` does (``stats``, ``skip_grid``, ``trace``, ``editing.pick`` / ``preview_frame``) works on it unchanged;
+    ``render_sets`` / ``render`` volume-render the cells along rays (``dmnerf_baked_render``)."""
+
+    def __init__(self, labels, cells, lo, hi, C):
+        super().__init__(labels, lo, hi, C)
+        if not torch.is_tensor(cells) or cells.dtype != torch.float32 or tuple(cells.shape) != (*self.dims, 4):
+            raise ValueError(f"BakedGrid: cells must be a float32 tensor {(*self.dims, 4)}, got {getattr(cells, 'dtype', type(cells))} "
+                             f"{tuple(getattr(cells, 'shape', ()))}")
+        _lib.require_gpu(cells)
+        if cells.device != labels.device:
+            raise RuntimeError("BakedGrid: cells and labels live on different devices")
+        self.cells = cells
+
+    @classmethod
+    def from_arrays(cls, labels, cells, lo, hi, C=MAX_LABELS):
+        """Wraps given volumes on the device: ``labels`` uint8 ``[dx, dy, dz]``, ``cells`` f32 ``[dx, dy, dz, 4]``."""
+        return cls(labels, cells, lo, hi, C)
+
+    def render_sets(self, rays, label_sets, near, far, stop=0.0):
+        """The cells of every ray set's own label set, volume-rendered along the pixel -> ``{"rgb" [N, 3], "depth" [N], "acc" [N]`` f32,
+        ``"label" [N], "source" [N]`` uint8, ``"nseg" [N]`` int32``}`` on the device.  ``rays [R, 2, N, 3]`` and ``label_sets`` as in
+        ``trace_sets``, but ``R <= 4`` (``ValueError`` beyond: the kernel keeps every set's walk in registers).  Each set walks the
+        volume cell by cell as the trace does; a cell whose label is in the set is a segment from the walk's ``t`` to the next plane
+        (or the exit), of length ``(t_out - t_in) |d|``; the segments of all sets are composited in ascending ``t_in``, the lowest
+        set first on ties: ``alpha = 1 - exp(-max(sigma, 0) len)``, ``w = T alpha``, ``rgb += w sigmoid(logits)``, ``depth += w
+        t_in``, ``acc += w``.  ``label`` / ``source`` are those of the heaviest segment (255 / 255 without a positive weight),
+        ``nseg`` counts the segments.  ``stop``: a pixel ends once its transmittance is below it (0: never; negative or NaN raises).
+        One launch, nothing reaches the host: after a warm-up call it can be captured in a graph and follows ``labels`` and
+        ``cells`` on replay."""
+        who = "BakedGrid.render_sets"
+        if torch.is_tensor(rays) and rays.dim() == 4 and rays.shape[0] > MAX_RENDER_SETS:
+            raise ValueError(f"{who}: {rays.shape[0]} ray sets, at most {MAX_RENDER_SETS}")
+        stop = float(stop)
+        if not stop >= 0.0:
+            raise ValueError(f"{who}: stop must be >= 0, got {stop}")
+        R, N, words = self._ray_sets(who, rays, label_sets, MAX_RENDER_SETS)
+        dev = rays.device
+        out = {"rgb": torch.empty(N, 3, dtype=torch.float32, device=dev), "depth": torch.empty(N, dtype=torch.float32, device=dev),
+               "acc": torch.empty(N, dtype=torch.float32, device=dev), "label": torch.empty(N, dtype=torch.uint8, device=dev),
+               "source": torch.empty(N, dtype=torch.uint8, device=dev), "nseg": torch.empty(N, dtype=torch.int32, device=dev)}
+        f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
+        _lib.check(_lib.load().dmnerf_baked_render(_lib.ptr(self.labels), _lib.ptr(self.cells), f3(self.lo), f3(self.cell), f3(self.inv_cell),
+                                                   (ctypes.c_int * 3)(*self.dims), self.C, _lib.ptr(rays), R, N,
+                                                   (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), stop, _lib.ptr(out["rgb"]),
+                                                   _lib.ptr(out["depth"]), _lib.ptr(out["acc"]), _lib.ptr(out["label"]),
+                                                   _lib.ptr(out["source"]), _lib.ptr(out["nseg"]), _lib.stream()),
+                   "dmnerf_baked_render")
+        return out
+
+    def render(self, rays_o, rays_d, near, far, labels=None, stop=0.0):
+        """``render_sets`` with one ray set: ``rays_o``, ``rays_d [N, 3]`` f32; ``labels`` as in ``trace`` (default: every label)."""
+        for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32:
+                raise ValueError(f"BakedGrid.render: {name} must be a float32 tensor")
+        _lib.require_gpu(rays_o, rays_d)
+        if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
+            raise ValueError(f"BakedGrid.render expects rays_o, rays_d [N, 3], got {tuple(rays_o.shape)} and {tuple(rays_d.shape)}")
+        return self.render_sets(torch.stack([rays_o, rays_d])[None], [range(self.C) if labels is None else labels], near, far, stop)

@@ -788,6 +788,41 @@ int dmnerf_label_trace(const uint8_t* d_labels, const float lo[3], const float c
                        const float* d_rays, int R, int64_t N, const uint32_t* masks, float t_near, float t_far, uint8_t* d_label,
                        float* d_t, int32_t* d_cell, uint8_t* d_source, void* stream);
 
+/* The baked field volume (csrc/label_grid.hip, csrc/baked.hip): colour logits and density kept per cell next to the label, and
+ * volume-rendered along rays -- an edit previewed with colour, soft edges and a weighted depth, still without the networks.
+ * Additive (the ABI version stays).
+ *   dmnerf_bake_cells: one sample per lane over d_raw [M, 4 + C].  d_labels[m] follows exactly the rule of dmnerf_label_cells: the
+ *     first maximum over all C logits where d_raw[m, 3] > sigma_threshold, else 255.  d_cells [M, 4] holds, for a labelled row, the
+ *     four floats d_raw[m, 0:4] (three colour logits and sigma) copied bit for bit, and four exact zeros for an unlabelled row; each
+ *     row is one 16-byte store, so d_cells must be 16-byte aligned (else DMNERF_E_ARG).  1 <= C <= 128, sigma_threshold >= 0 (NaN
+ *     refused), M == 0 returns 0 without a launch.  No atomics, no allocation, no synchronisation.
+ *   dmnerf_baked_render: dmnerf_label_trace's arguments (d_labels, the box arrays, C, d_rays [R,2,N,3], R x 4 HOST mask words,
+ *     t_near, t_far) plus d_cells [dx,dy,dz,4] (16-byte aligned) and `stop`; 1 <= R <= 4 (every set's walk state lives in registers).
+ *     One lane per pixel, every f32 operation rounded on its own (tests/_baked_restate.py states it in numpy).
+ *     Walk: each set's clip, start cell, cell sequence and t values are dmnerf_label_trace's, but the walk goes on behind a counted
+ *       cell (at most dx + dy + dz + 1 cells per set).  A cell of set r counts if its label is < C and in the set's mask; the
+ *       16-byte d_cells entry is read for a counted cell only.
+ *     Segment: for a counted cell t_in is the walk's current t, t_out the next plane crossing tmax_a if tmax_a < t_exit, else
+ *       t_exit; len = (t_out - t_in) * |d_r|, |d| = sqrtf(d0 d0 + d1 d1 + d2 d2) summed in that order.
+ *     Merge: the pending segments of the R sets are composited in ascending t_in, the lowest set first on equal t_in (a pixel's rays
+ *       share the ray parameter); within a set the walk's order stands; a set without a further counted cell drops out.
+ *     Composite: alpha = 1 - expf(-max(sigma, 0) * len), w = T * alpha, T <- T * (1 - alpha) from T = 1;
+ *       rgb += w * 1 / (1 + expf(-logit)); depth += w * t_in; acc += w.  The label and source of the pixel are those of the segment
+ *       with the largest w so far (a strict > from best_w = 0: the first wins ties; without a positive weight 255 / 255).  After a
+ *       segment the pixel stops if T < stop; stop = 0 never stops early.  max(sigma, 0) is sigma > 0 ? sigma : 0: a NaN sigma
+ *       contributes nothing.  (A ray of direction 0 inside the box has segments of length 0 * (t_out - t_in): nothing for a finite
+ *       t_far, NaN for an infinite one.)
+ *     Outputs [N]: d_rgb [N,3], d_depth, d_acc f32; d_label, d_source uint8; d_nseg int32, the number of composited segments.  A
+ *     pixel whose sets all miss gets zeros, 255 / 255 and 0.
+ *     Refused: what dmnerf_label_trace refuses, R > 4, a stop that is negative or NaN, a misaligned d_cells.  N == 0 returns 0
+ *     without a launch.  No allocation, synchronisation, atomics or float reductions across lanes: it can be captured in a graph and
+ *     reads d_labels and d_cells anew on every replay. */
+int dmnerf_bake_cells(const float* d_raw, int64_t M, int C, float sigma_threshold, uint8_t* d_labels, float* d_cells, void* stream);
+int dmnerf_baked_render(const uint8_t* d_labels, const float* d_cells, const float lo[3], const float cell[3], const float inv_cell[3],
+                        const int dims[3], int C, const float* d_rays, int R, int64_t N, const uint32_t* masks, float t_near, float t_far,
+                        float stop, float* d_rgb, float* d_depth, float* d_acc, uint8_t* d_label, uint8_t* d_source, int32_t* d_nseg,
+                        void* stream);
+
 /* The two renders above on the OPT-IN split-f16 ("f16x2") kernels (csrc/mlp_f16_density.hip, csrc/mlp_f16_sparse.hip; the body of
  * csrc/mlp_f16_impl.h with template flags).  Additive (the ABI version stays).
  *   f16 density blob: dmnerf_blob_f16_density_words 32-bit words = [the f16 blob's 4096-float bias table | its 120 trunk groups
