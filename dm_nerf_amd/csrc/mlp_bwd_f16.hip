@@ -324,6 +324,9 @@ __global__ __launch_bounds__(256) void mlp_bwd_f16_kernel(const BwdHArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // the last (landing-zone) fetches
 }
 
+template <int OBI>
+struct Family { static constexpr auto kernel = mlp_bwd_f16_kernel<OBI>; };
+
 }  // namespace
 
 extern "C" int dmnerf_grad_scale(const float* d_graw, int64_t n, float* d_scale4, void* stream) {
@@ -335,22 +338,14 @@ extern "C" int dmnerf_grad_scale(const float* d_graw, int64_t n, float* d_scale4
 
 extern "C" int dmnerf_mlp_bwd_data_f16(const float* d_blob_t_f16, int ins_num, const float* d_save, const float* d_graw, int64_t M,
                                        float* d_dsave, float* d_graw_t, const float* d_scale, void* stream) {
-    if (int rc = dmn_check_ins_num("mlp_bwd_data_f16", ins_num)) return rc;
-    if (M < 0 || M > DMNERF_MAX_TRAIN_SAMPLES) return dmn_fail(DMNERF_E_ARG, "mlp_bwd_data_f16: M=%lld outside [0,%lld]", (long long)M, (long long)DMNERF_MAX_TRAIN_SAMPLES);
-    if (M == 0) return DMNERF_OK;
-    if (!d_blob_t_f16 || !d_save || !d_graw || !d_dsave) return dmn_fail(DMNERF_E_ARG, "mlp_bwd_data_f16: null pointer");
+    const char* who = "mlp_bwd_data_f16";
+    int rc = dmn_check_ins_num(who, ins_num);
+    if (rc) return rc;
+    if (M < 0 || M > DMNERF_MAX_TRAIN_SAMPLES) return dmn_fail(DMNERF_E_ARG, "%s: M=%lld outside [0,%lld]", who, (long long)M, (long long)DMNERF_MAX_TRAIN_SAMPLES);
+    if (!dmn_batch_given(&rc, who, M, {d_blob_t_f16, d_save, d_graw, d_dsave})) return rc;
     BwdHArgs a{};
     a.blob = d_blob_t_f16; a.L = make_layout(ins_num); a.LT = make_layout_t(ins_num); a.S = make_f16_layout_t(ins_num);
     a.save = d_save; a.graw = d_graw; a.dsave = d_dsave; a.graw_t = d_graw_t; a.scale = d_scale; a.M = M;
-    unsigned grid;
-    if (int rc = dmn_mlp_grid("mlp_bwd_data_f16", M, &grid)) return rc;
     constexpr int LDS = (F16_RING_FLOATS + TAB_T_FLOATS) * sizeof(float);
-    const char* what = "mlp_bwd_data_f16";
-    switch (a.L.OBI) {
-        case 1: return dmn_launch_lds<mlp_bwd_f16_kernel<1>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 2: return dmn_launch_lds<mlp_bwd_f16_kernel<2>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 3: return dmn_launch_lds<mlp_bwd_f16_kernel<3>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 4: return dmn_launch_lds<mlp_bwd_f16_kernel<4>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        default: return dmn_fail(DMNERF_E_ARG, "mlp_bwd_data_f16: unsupported logit count C=%d", a.L.C);
-    }
+    return dmn_launch_mlp_obx<Family, LDS, true>(who, who, false, a.L.OBI, a.L.C, a, (hipStream_t)stream);
 }

@@ -23,6 +23,9 @@ __global__ void pack_f16_kernel(const float* __restrict__ flat, const int* __res
     }
 }
 
+template <int OBX>
+struct Family { static constexpr auto kernel = mlp_f16_kernel<OBX>; };
+
 }  // namespace
 
 extern "C" int dmnerf_pack_f16(const float* d_flat, const int32_t* d_idx, float* d_stream_words, int64_t n_words, void* stream) {
@@ -39,23 +42,15 @@ extern "C" void dmnerf_f16_set_trace(long long* d_trace) { g_f16_trace = d_trace
 
 extern "C" int dmnerf_mlp_fwd_rays_f16(const float* d_blob_f16, int ins_num, const float* d_rays_o, const float* d_rays_d,
                                        const float* d_z, int64_t N, int S, float* d_raw, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_f16", ins_num, N, S)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob_f16 || !d_rays_o || !d_rays_d || !d_z || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_f16: null pointer");
+    const char* who = "mlp_fwd_rays_f16";
+    int rc;
+    if (!dmn_rays_given(&rc, who, ins_num, N, S, false, {d_blob_f16, d_rays_o, d_rays_d, d_z, d_raw})) return rc;
     F16Args a{};
     a.blob = d_blob_f16; a.S = make_f16_layout(ins_num);
     a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z; a.raw = d_raw; a.M = N * S; a.Sr = S;
 #ifdef DMN_F16_TRACE
     a.trace = g_f16_trace;
 #endif
-    unsigned grid;
-    if (int rc = dmn_mlp_grid("mlp_fwd_rays_f16", a.M, &grid, true)) return rc;
     constexpr int LDS = F16_LDS_FLOATS * sizeof(float);
-    const char* what = "mlp_fwd_rays_f16";
-    switch (a.S.OBX) {
-        case 1: return dmn_launch_lds<mlp_f16_kernel<1>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 2: return dmn_launch_lds<mlp_f16_kernel<2>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 4: return dmn_launch_lds<mlp_f16_kernel<4>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_f16: unsupported logit count C=%d", a.S.C);
-    }
+    return dmn_launch_mlp_obx<Family, LDS, false>(who, who, true, a.S.OBX, a.S.C, a, (hipStream_t)stream);
 }

@@ -50,27 +50,22 @@ extern "C" int dmnerf_blob_f16_density_from_f16(const float* d_blob_f16, int ins
 
 extern "C" int dmnerf_mlp_fwd_rays_density_f16(const float* d_blob_f16_density, int ins_num, const float* d_rays_o, const float* d_rays_d,
                                                const float* d_z, int64_t N, int S, float* d_sigma, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_density_f16", ins_num, N, S)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob_f16_density || !d_rays_o || !d_rays_d || !d_z || !d_sigma) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density_f16: null pointer");
+    const char* who = "mlp_fwd_rays_density_f16";
+    int rc;
+    if (!dmn_rays_given(&rc, who, ins_num, N, S, false, {d_blob_f16_density, d_rays_o, d_rays_d, d_z, d_sigma})) return rc;
     F16Args a{};
     fill_args(a, d_blob_f16_density, ins_num, d_rays_o, d_rays_d, d_z, N, S, d_sigma);
-    unsigned grid;
-    if (int rc = dmn_mlp_grid("mlp_fwd_rays_density_f16", a.M, &grid, true)) return rc;
-    return dmn_launch_lds<mlp_f16_density_kernel<false>, LDS_BYTES>("mlp_fwd_rays_density_f16", grid, 256, LDS_BYTES, (hipStream_t)stream, a);
+    return dmn_launch_mlp<mlp_f16_density_kernel<false>, LDS_BYTES>(who, true, a, (hipStream_t)stream);
 }
 
 extern "C" int dmnerf_mlp_fwd_rays_density_f16_sel(const float* d_blob_f16_density, int ins_num, const float* d_rays_o,
                                                    const float* d_rays_d, const float* d_z, int64_t N, int S, const int* d_sel,
                                                    const int* d_count, float* d_sigma, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_density_f16_sel", ins_num, N, S, true)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob_f16_density || !d_rays_o || !d_rays_d || !d_z || !d_sel || !d_count || !d_sigma)
-        return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density_f16_sel: null pointer");
+    const char* who = "mlp_fwd_rays_density_f16_sel";
+    int rc;
+    if (!dmn_rays_given(&rc, who, ins_num, N, S, true, {d_blob_f16_density, d_rays_o, d_rays_d, d_z, d_sel, d_count, d_sigma})) return rc;
     F16Args a{};
     fill_args(a, d_blob_f16_density, ins_num, d_rays_o, d_rays_d, d_z, N, S, d_sigma);
     a.sel = d_sel; a.count = d_count;
-    unsigned grid;                                                          // the worst case count == N * S
-    if (int rc = dmn_mlp_grid("mlp_fwd_rays_density_f16_sel", a.M, &grid)) return rc;
-    return dmn_launch_lds<mlp_f16_density_kernel<true>, LDS_BYTES>("mlp_fwd_rays_density_f16_sel", grid, 256, LDS_BYTES, (hipStream_t)stream, a);
+    return dmn_launch_mlp<mlp_f16_density_kernel<true>, LDS_BYTES>(who, false, a, (hipStream_t)stream);   // (the grid: the worst case count == N * S)
 }

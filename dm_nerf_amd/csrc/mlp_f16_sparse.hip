@@ -14,26 +14,21 @@ __global__ __launch_bounds__(256) void mlp_f16_sel_kernel(const F16Args a) {
 #include "mlp_f16_body.inc"
 }
 
+template <int OBX>
+struct Family { static constexpr auto kernel = mlp_f16_sel_kernel<OBX>; };
+
 }  // namespace
 
 extern "C" int dmnerf_mlp_fwd_rays_f16_sel(const float* d_blob_f16, int ins_num, const float* d_rays_o, const float* d_rays_d,
                                            const float* d_z, int64_t N, int S, const int* d_sel, const int* d_count, float* d_raw,
                                            void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_f16_sel", ins_num, N, S, true)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob_f16 || !d_rays_o || !d_rays_d || !d_z || !d_sel || !d_count || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_f16_sel: null pointer");
+    const char* who = "mlp_fwd_rays_f16_sel";
+    int rc;
+    if (!dmn_rays_given(&rc, who, ins_num, N, S, true, {d_blob_f16, d_rays_o, d_rays_d, d_z, d_sel, d_count, d_raw})) return rc;
     F16Args a{};
     a.blob = d_blob_f16; a.S = make_f16_layout(ins_num);
     a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z; a.raw = d_raw; a.M = N * S; a.Sr = S;
     a.sel = d_sel; a.count = d_count;
-    unsigned grid;                                                         // the worst case count == N * S (< 2^31 samples: fits)
-    if (int rc = dmn_mlp_grid("mlp_fwd_rays_f16_sel", a.M, &grid)) return rc;
-    constexpr int LDS = F16_LDS_FLOATS * sizeof(float);
-    const char* what = "mlp_fwd_rays_f16_sel";
-    switch (a.S.OBX) {
-        case 1: return dmn_launch_lds<mlp_f16_sel_kernel<1>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 2: return dmn_launch_lds<mlp_f16_sel_kernel<2>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 4: return dmn_launch_lds<mlp_f16_sel_kernel<4>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_f16_sel: unsupported logit count C=%d", a.S.C);
-    }
+    constexpr int LDS = F16_LDS_FLOATS * sizeof(float);                    // (the grid: the worst case count == N * S < 2^31 samples, fits)
+    return dmn_launch_mlp_obx<Family, LDS, false>(who, who, false, a.S.OBX, a.S.C, a, (hipStream_t)stream);
 }

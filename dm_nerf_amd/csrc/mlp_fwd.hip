@@ -10,9 +10,8 @@ extern "C" int dmnerf_debug_fwd_trace(long long* p) { g_dmn_fwd_trace = p; retur
 extern "C" int dmnerf_mlp_fwd_rays(const float* d_blob, int ins_num, const float* d_rays_o,
                                    const float* d_rays_d, const float* d_z, int64_t N, int S,
                                    float* d_raw, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays", ins_num, N, S)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob || !d_rays_o || !d_rays_d || !d_z || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays: null pointer");
+    int rc;
+    if (!dmn_rays_given(&rc, "mlp_fwd_rays", ins_num, N, S, false, {d_blob, d_rays_o, d_rays_d, d_z, d_raw})) return rc;
     MlpArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
     a.raw = d_raw; a.M = N * S; a.S = S;

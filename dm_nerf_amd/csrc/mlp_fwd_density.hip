@@ -38,15 +38,12 @@ __global__ __launch_bounds__(256) void mlp_fwd_density_kernel(const DensityArgs 
 extern "C" int dmnerf_mlp_fwd_rays_density(const float* d_blob, int ins_num, const float* d_rays_o,
                                            const float* d_rays_d, const float* d_z, int64_t N, int S,
                                            float* d_sigma, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_density", ins_num, N, S)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob || !d_rays_o || !d_rays_d || !d_z || !d_sigma) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density: null pointer");
+    const char* who = "mlp_fwd_rays_density";
+    int rc;
+    if (!dmn_rays_given(&rc, who, ins_num, N, S, false, {d_blob, d_rays_o, d_rays_d, d_z, d_sigma})) return rc;
     DensityArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
     a.sigma = d_sigma; a.M = N * S; a.S = S;
-    unsigned grid;
-    if (int rc = dmn_mlp_grid("mlp_fwd_rays_density", a.M, &grid)) return rc;
     constexpr int LDS = LDS_FLOATS * sizeof(float);                      // 147 456 B: one workgroup per CU, as the full kernel
-    return dmn_launch_lds<mlp_fwd_density_kernel, LDS>("mlp_fwd_rays_density", grid, 256, LDS,
-                                                       (hipStream_t)stream, a);
+    return dmn_launch_mlp<mlp_fwd_density_kernel, LDS>(who, false, a, (hipStream_t)stream);
 }

@@ -340,22 +340,22 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
     mlp_fwd_body<OBI, EMBEDDED, SAVE, FUSED, false>(a);
 }
 
+template <bool EMBEDDED, bool SAVE, bool FUSED>
+struct MlpFwd {
+    template <int OBI>
+    struct Family { static constexpr auto kernel = mlp_fwd_kernel<OBI, EMBEDDED, SAVE, FUSED>; };
+};
+
 template <bool EMBEDDED, bool SAVE, bool FUSED = false>
 int launch(const MlpArgs& a, hipStream_t stream) {
-    unsigned grid;
-    if (int rc = dmn_mlp_grid("mlp_fwd", a.M, &grid)) return rc;
-    if (SAVE && a.M > DMNERF_MAX_TRAIN_SAMPLES)
+    if (SAVE && a.M > DMNERF_MAX_TRAIN_SAMPLES) {                     // (a batch beyond one launch's grid is refused as such)
+        unsigned grid;
+        if (int rc = dmn_mlp_grid("mlp_fwd", a.M, &grid)) return rc;
         return dmn_fail(DMNERF_E_ARG, "mlp_fwd_train: %lld samples per launch exceed %lld (32-bit row offsets); split the batch",
                         (long long)a.M, (long long)DMNERF_MAX_TRAIN_SAMPLES);
-    constexpr int LDS = (LDS_FLOATS + PARK_FLOATS) * sizeof(float);   // 163 840 B = the CU's whole LDS: one workgroup per CU
-    const char* what = "mlp_fwd";
-    switch (a.L.OBI) {
-        case 1: return dmn_launch_lds<mlp_fwd_kernel<1, EMBEDDED, SAVE, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
-        case 2: return dmn_launch_lds<mlp_fwd_kernel<2, EMBEDDED, SAVE, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
-        case 3: return dmn_launch_lds<mlp_fwd_kernel<3, EMBEDDED, SAVE, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
-        case 4: return dmn_launch_lds<mlp_fwd_kernel<4, EMBEDDED, SAVE, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
-        default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd: unsupported logit count C=%d", a.L.C);
     }
+    constexpr int LDS = (LDS_FLOATS + PARK_FLOATS) * sizeof(float);   // 163 840 B = the CU's whole LDS: one workgroup per CU
+    return dmn_launch_mlp_obx<MlpFwd<EMBEDDED, SAVE, FUSED>::template Family, LDS, true>("mlp_fwd", "mlp_fwd", false, a.L.OBI, a.L.C, a, stream);
 }
 
 }  // namespace

@@ -169,10 +169,10 @@ int launch(const PointsArgs& a, const char* what, void* stream) {
 extern "C" int dmnerf_mlp_fwd_points_density(const float* d_blob, int ins_num, const float* d_pts, int64_t M, float* d_out,
                                              float voxel, void* stream) {
     const char* what = "mlp_fwd_points_density";
-    if (int rc = dmn_check_ins_num(what, ins_num)) return rc;
+    int rc = dmn_check_ins_num(what, ins_num);
+    if (rc) return rc;
     if (M < 0 || voxel != voxel) return dmn_fail(DMNERF_E_ARG, "%s: bad M=%lld voxel=%g", what, (long long)M, (double)voxel);
-    if (M == 0) return DMNERF_OK;
-    if (!d_blob || !d_pts || !d_out) return dmn_fail(DMNERF_E_ARG, "%s: null pointer", what);
+    if (!dmn_batch_given(&rc, what, M, {d_blob, d_pts, d_out})) return rc;
     PointsArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num); a.pts = d_pts; a.out = d_out; a.M = M; a.voxel = voxel;
     return voxel < 0.f ? launch<false, false>(a, what, stream) : launch<false, true>(a, what, stream);
@@ -181,15 +181,15 @@ extern "C" int dmnerf_mlp_fwd_points_density(const float* d_blob, int ins_num, c
 extern "C" int dmnerf_occupancy_slab(const float* d_blob, int ins_num, const float* d_t, int dim, const float* scale,
                                      const float* transform, int64_t m0, int64_t M, float* d_out, float voxel, void* stream) {
     const char* what = "occupancy_slab";
-    if (int rc = dmn_check_ins_num(what, ins_num)) return rc;
+    int rc = dmn_check_ins_num(what, ins_num);
+    if (rc) return rc;
     if (dim < 1 || dim > GRID_DIM_MAX) return dmn_fail(DMNERF_E_ARG, "%s: dim %d outside 1 .. %d", what, dim, GRID_DIM_MAX);
     const int64_t total = (int64_t)dim * dim * dim;
     if (m0 < 0 || M < 0 || m0 > total || M > total - m0)
         return dmn_fail(DMNERF_E_ARG, "%s: slab [%lld, %lld + %lld) leaves the %d^3 grid", what, (long long)m0, (long long)m0, (long long)M, dim);
     if (voxel != voxel) return dmn_fail(DMNERF_E_ARG, "%s: voxel is NaN", what);
     if (!scale || !transform) return dmn_fail(DMNERF_E_ARG, "%s: null scale / transform", what);
-    if (M == 0) return DMNERF_OK;
-    if (!d_blob || !d_t || !d_out) return dmn_fail(DMNERF_E_ARG, "%s: null pointer", what);
+    if (!dmn_batch_given(&rc, what, M, {d_blob, d_t, d_out})) return rc;
     PointsArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num); a.t = d_t; a.dim = (unsigned)dim; a.m0 = (unsigned)m0; a.out = d_out; a.M = M; a.voxel = voxel;
     for (int i = 0; i < 3; ++i) a.s[i] = scale[i];

@@ -17,18 +17,16 @@ __global__ __launch_bounds__(256) void mlp_fwd_sel_kernel(const MlpSelArgs a) {
 }
 
 template <bool FUSED>
+struct MlpFwdSel {
+    template <int OBI>
+    struct Family { static constexpr auto kernel = mlp_fwd_sel_kernel<OBI, FUSED>; };
+};
+
+template <bool FUSED>
 int launch_sel(const MlpSelArgs& a, hipStream_t stream) {
-    unsigned grid;                                                       // the worst case count == M (< 2^31 samples: fits)
-    if (int rc = dmn_mlp_grid("mlp_fwd_rays_sel", a.M, &grid)) return rc;
     constexpr int LDS = (LDS_FLOATS + PARK_FLOATS) * sizeof(float);
-    const char* what = "mlp_fwd_rays_sel";
-    switch (a.L.OBI) {
-        case 1: return dmn_launch_lds<mlp_fwd_sel_kernel<1, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
-        case 2: return dmn_launch_lds<mlp_fwd_sel_kernel<2, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
-        case 3: return dmn_launch_lds<mlp_fwd_sel_kernel<3, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
-        case 4: return dmn_launch_lds<mlp_fwd_sel_kernel<4, FUSED>, LDS>(what, grid, 256, LDS, stream, a);
-        default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_sel: unsupported logit count C=%d", a.L.C);
-    }
+    const char* what = "mlp_fwd_rays_sel";                               // (the grid is sized for the worst case count == M < 2^31 samples: fits)
+    return dmn_launch_mlp_obx<MlpFwdSel<FUSED>::template Family, LDS, true>(what, what, false, a.L.OBI, a.L.C, a, stream);
 }
 
 }  // namespace

@@ -40,10 +40,11 @@ __global__ __launch_bounds__(256) void mlp_fwd_density_sel_kernel(const DensityS
 extern "C" int dmnerf_mlp_fwd_rays_sel(const float* d_blob, int ins_num, int fused_heads, const float* d_rays_o,
                                        const float* d_rays_d, const float* d_z, int64_t N, int S,
                                        const int* d_sel, const int* d_count, float* d_raw, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_sel", ins_num, N, S, true)) return rc;
-    if (fused_heads != 0 && fused_heads != 1) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_sel: fused_heads %d unsupported", fused_heads);
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob || !d_rays_o || !d_rays_d || !d_z || !d_sel || !d_count || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_sel: null pointer");
+    const char* who = "mlp_fwd_rays_sel";
+    int rc = dmn_check_rays(who, ins_num, N, S, true);
+    if (rc) return rc;
+    if (fused_heads != 0 && fused_heads != 1) return dmn_fail(DMNERF_E_ARG, "%s: fused_heads %d unsupported", who, fused_heads);
+    if (!dmn_batch_given(&rc, who, N, {d_blob, d_rays_o, d_rays_d, d_z, d_sel, d_count, d_raw})) return rc;
     if (fused_heads) return dmn_mlp_fwd_rays_sel_fused(d_blob, ins_num, d_rays_o, d_rays_d, d_z, N, S, d_sel, d_count, d_raw, (hipStream_t)stream);
     MlpSelArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
@@ -54,15 +55,12 @@ extern "C" int dmnerf_mlp_fwd_rays_sel(const float* d_blob, int ins_num, int fus
 extern "C" int dmnerf_mlp_fwd_rays_density_sel(const float* d_blob, int ins_num, const float* d_rays_o,
                                                const float* d_rays_d, const float* d_z, int64_t N, int S,
                                                const int* d_sel, const int* d_count, float* d_sigma, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_density_sel", ins_num, N, S, true)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob || !d_rays_o || !d_rays_d || !d_z || !d_sel || !d_count || !d_sigma) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_density_sel: null pointer");
+    const char* who = "mlp_fwd_rays_density_sel";
+    int rc;
+    if (!dmn_rays_given(&rc, who, ins_num, N, S, true, {d_blob, d_rays_o, d_rays_d, d_z, d_sel, d_count, d_sigma})) return rc;
     DensitySelArgs a{};
     a.blob = d_blob; a.L = make_layout(ins_num); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
     a.sigma = d_sigma; a.M = N * S; a.S = S; a.sel = d_sel; a.count = d_count;
-    unsigned grid;
-    if (int rc = dmn_mlp_grid("mlp_fwd_rays_density_sel", a.M, &grid)) return rc;
     constexpr int LDS = LDS_FLOATS * sizeof(float);
-    return dmn_launch_lds<mlp_fwd_density_sel_kernel, LDS>("mlp_fwd_rays_density_sel", grid, 256,
-                                                           LDS, (hipStream_t)stream, a);
+    return dmn_launch_mlp<mlp_fwd_density_sel_kernel, LDS>(who, false, a, (hipStream_t)stream);
 }

@@ -8,9 +8,8 @@
 extern "C" int dmnerf_mlp_fwd_rays_train_fused(const float* d_blob_fused, int ins_num, const float* d_rays_o,
                                                const float* d_rays_d, const float* d_z, int64_t N, int S,
                                                float* d_raw, float* d_save, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_train_fused", ins_num, N, S)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob_fused || !d_rays_o || !d_rays_d || !d_z || !d_raw || !d_save) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_train_fused: null pointer");
+    int rc;
+    if (!dmn_rays_given(&rc, "mlp_fwd_rays_train_fused", ins_num, N, S, false, {d_blob_fused, d_rays_o, d_rays_d, d_z, d_raw, d_save})) return rc;
     MlpArgs a{};
     a.blob = d_blob_fused; a.L = make_layout(ins_num, true); a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z;
     a.raw = d_raw; a.save = d_save; a.M = N * S; a.S = S;

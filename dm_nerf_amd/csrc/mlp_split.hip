@@ -26,8 +26,10 @@ __global__ void pack_split_kernel(const float* __restrict__ flat, const int* __r
     }
 }
 
-}  // namespace
+template <int OBX>
+struct Family { static constexpr auto kernel = mlp_split_kernel<OBX>; };
 
+}  // namespace
 
 extern "C" int dmnerf_pack_split(const float* d_flat, const int32_t* d_idx, float* d_stream_words, int64_t n_words, void* stream) {
     if (!d_flat || !d_idx || !d_stream_words || n_words <= 0) return dmn_fail(DMNERF_E_ARG, "pack_split: bad argument");
@@ -38,20 +40,12 @@ extern "C" int dmnerf_pack_split(const float* d_flat, const int32_t* d_idx, floa
 
 extern "C" int dmnerf_mlp_fwd_rays_split(const float* d_blob_split, int ins_num, const float* d_rays_o, const float* d_rays_d,
                                          const float* d_z, int64_t N, int S, float* d_raw, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_split", ins_num, N, S)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob_split || !d_rays_o || !d_rays_d || !d_z || !d_raw) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_split: null pointer");
+    const char* who = "mlp_fwd_rays_split";
+    int rc;
+    if (!dmn_rays_given(&rc, who, ins_num, N, S, false, {d_blob_split, d_rays_o, d_rays_d, d_z, d_raw})) return rc;
     SplitArgs a{};
     a.blob = d_blob_split; a.L = make_layout(ins_num, true); a.S = make_split_layout(ins_num);
     a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z; a.raw = d_raw; a.M = N * S; a.Sr = S;
-    unsigned grid;
-    if (int rc = dmn_mlp_grid("mlp_fwd_rays_split", a.M, &grid, true)) return rc;
     constexpr int LDS = SP_LDS_FLOATS * sizeof(float);
-    const char* what = "mlp_fwd_rays_split";
-    switch (a.S.OBX) {
-        case 1: return dmn_launch_lds<mlp_split_kernel<1>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 2: return dmn_launch_lds<mlp_split_kernel<2>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 4: return dmn_launch_lds<mlp_split_kernel<4>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_split: unsupported logit count C=%d", a.S.C);
-    }
+    return dmn_launch_mlp_obx<Family, LDS, false>(who, who, true, a.S.OBX, a.S.C, a, (hipStream_t)stream);
 }

@@ -5,24 +5,21 @@
 // backward differentiates; values are f32-class (1e-7 against float64) but not the bitwise fmaf chain of the default path.
 #include "mlp_split_impl.h"
 
+namespace {
+template <int OBX>
+struct Family { static constexpr auto kernel = mlp_split_kernel<OBX, true>; };
+}  // namespace
+
 extern "C" int dmnerf_mlp_fwd_rays_train_split(const float* d_blob_split, int ins_num, const float* d_rays_o, const float* d_rays_d,
                                                const float* d_z, int64_t N, int S, float* d_raw, float* d_save, void* stream) {
-    if (int rc = dmn_check_rays("mlp_fwd_rays_train_split", ins_num, N, S)) return rc;
-    if (N == 0) return DMNERF_OK;
-    if (!d_blob_split || !d_rays_o || !d_rays_d || !d_z || !d_raw || !d_save) return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_train_split: null pointer");
+    const char* who = "mlp_fwd_rays_train_split";
+    int rc;
+    if (!dmn_rays_given(&rc, who, ins_num, N, S, false, {d_blob_split, d_rays_o, d_rays_d, d_z, d_raw, d_save})) return rc;
     SplitArgs a{};
     a.blob = d_blob_split; a.L = make_layout(ins_num, true); a.S = make_split_layout(ins_num);
     a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.z = d_z; a.raw = d_raw; a.save = d_save; a.M = N * S; a.Sr = S;
     if (a.M > DMNERF_MAX_TRAIN_SAMPLES)
-        return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_train_split: %lld samples per launch exceed %lld; split the batch", (long long)a.M, (long long)DMNERF_MAX_TRAIN_SAMPLES);
-    unsigned grid;
-    if (int rc = dmn_mlp_grid("mlp_fwd_rays_train_split", a.M, &grid)) return rc;
+        return dmn_fail(DMNERF_E_ARG, "%s: %lld samples per launch exceed %lld; split the batch", who, (long long)a.M, (long long)DMNERF_MAX_TRAIN_SAMPLES);
     constexpr int LDS = SP_LDS_FLOATS * sizeof(float);
-    const char* what = "mlp_fwd_rays_train_split";
-    switch (a.S.OBX) {
-        case 1: return dmn_launch_lds<mlp_split_kernel<1, true>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 2: return dmn_launch_lds<mlp_split_kernel<2, true>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        case 4: return dmn_launch_lds<mlp_split_kernel<4, true>, LDS>(what, grid, 256, LDS, (hipStream_t)stream, a);
-        default: return dmn_fail(DMNERF_E_ARG, "mlp_fwd_rays_train_split: unsupported logit count C=%d", a.S.C);
-    }
+    return dmn_launch_mlp_obx<Family, LDS, false>(who, who, false, a.S.OBX, a.S.C, a, (hipStream_t)stream);
 }
