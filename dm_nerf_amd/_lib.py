@@ -6,16 +6,17 @@ library is ``tensor.data_ptr()`` and every launch goes to ``torch.cuda.current_s
 import ctypes
 import os
 
+import numpy as np
 import torch  # must be imported first: the library binds to the HIP runtime torch already loaded
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdmnerf_hip.so")
 
-c_f32p = ctypes.c_void_p
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
 c_vp = ctypes.c_void_p
 c_float = ctypes.c_float
+c_double = ctypes.c_double
 
 
 class RenderArgs(ctypes.Structure):
@@ -64,8 +65,6 @@ class ChainLayer(ctypes.Structure):
     """``dmnerf_chain_layer`` (include/dmnerf_hip.h)."""
     _fields_ = [("d_B", c_vp), ("d_bias", c_vp), ("ldb", c_int), ("from_act", c_int), ("from_x", c_int), ("relu", c_int)]
 
-
-c_double = ctypes.c_double
 
 # name -> (restype, argtypes); exactly the symbols include/dmnerf_hip.h declares
 SIGNATURES = {
@@ -277,3 +276,25 @@ def f32(t):
 
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _arg(a):
+    """One argument as ctypes takes it: a tensor's / host array's address, a struct by reference, anything else (numbers,
+    None = null, ``byref`` of a scalar, ctypes arrays) as it is.  No validation: that is the caller's."""
+    if isinstance(a, torch.Tensor):
+        return a.data_ptr()
+    if isinstance(a, np.ndarray):
+        return a.ctypes.data
+    if isinstance(a, ctypes.Structure):
+        return ctypes.byref(a)
+    return a
+
+
+def call(name, *args):
+    """Host-only entry ``name`` (returns an int status, takes no stream); raises on a non-zero status."""
+    check(getattr(load(), name)(*map(_arg, args)), name)
+
+
+def launch(name, *args):
+    """Entry ``name`` whose last C parameter is ``void* stream``: launched on the stream that is current NOW."""
+    check(getattr(load(), name)(*map(_arg, args), stream()), name)

@@ -57,8 +57,7 @@ def _f16_flags_word(device):
 
 
 def _f16_range_scan(workspace, M, gradients):
-    _lib.check(_lib.load().dmnerf_f16x2_range_flags(_lib.ptr(workspace), M, 1 if gradients else 0, _lib.ptr(_f16_flags_word(workspace.device)),
-                                                    _lib.stream()), "dmnerf_f16x2_range_flags")
+    _lib.launch("dmnerf_f16x2_range_flags", workspace, M, 1 if gradients else 0, _f16_flags_word(workspace.device))
 
 
 def check_f16x2(device=None, reset=True, warn=True):
@@ -95,9 +94,8 @@ def f16x2_probe(model, rays_o, rays_d, z):
     save = torch.empty(lib.dmnerf_train_save_floats(step * S), dtype=torch.float32, device=z.device)
     for s0 in range(0, N, step):
         n = min(step, N - s0)
-        _lib.check(lib.dmnerf_mlp_fwd_rays_train_f16(_lib.ptr(model.blob_f16()), model.ins_num, _lib.ptr(rays_o[s0:s0 + n]),
-                                                     _lib.ptr(rays_d[s0:s0 + n]), _lib.ptr(z[s0:s0 + n]), n, S, _lib.ptr(raw), _lib.ptr(save),
-                                                     _lib.stream()), "dmnerf_mlp_fwd_rays_train_f16")
+        _lib.launch("dmnerf_mlp_fwd_rays_train_f16", model.blob_f16(), model.ins_num, rays_o[s0:s0 + n], rays_d[s0:s0 + n], z[s0:s0 + n],
+                    n, S, raw, save)
         _f16_range_scan(save, n * S, False)
 
 
@@ -163,17 +161,14 @@ def wgrad_plan(ins_num, M, device, max_wgs=None, split=False):
     kind = "f16x2" if split == "f16x2" else ("bf16x3" if split else None)
     key = (ins_num, M, str(device), max_wgs, kind)
     if key not in _plan_cache:
-        lib = _lib.load()
-        f_sizes, f_plan = {None: (lib.dmnerf_wgrad_plan_sizes, lib.dmnerf_wgrad_plan),
-                           "bf16x3": (lib.dmnerf_wgrad_plan_sizes_split, lib.dmnerf_wgrad_plan_split),
-                           "f16x2": (lib.dmnerf_wgrad_plan_sizes_f16, lib.dmnerf_wgrad_plan_f16)}[kind]
+        f_sizes, f_plan = {None: ("dmnerf_wgrad_plan_sizes", "dmnerf_wgrad_plan"),
+                           "bf16x3": ("dmnerf_wgrad_plan_sizes_split", "dmnerf_wgrad_plan_split"),
+                           "f16x2": ("dmnerf_wgrad_plan_sizes_f16", "dmnerf_wgrad_plan_f16")}[kind]
         jb, ob, pf = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         nj, no = ctypes.c_int(), ctypes.c_int()
-        _lib.check(f_sizes(ins_num, M, max_wgs, ctypes.byref(jb), ctypes.byref(ob), ctypes.byref(pf),
-                           ctypes.byref(nj), ctypes.byref(no)), "dmnerf_wgrad_plan_sizes")
+        _lib.call(f_sizes, ins_num, M, max_wgs, ctypes.byref(jb), ctypes.byref(ob), ctypes.byref(pf), ctypes.byref(nj), ctypes.byref(no))
         hj, ho = np.empty(jb.value, dtype=np.uint8), np.empty(ob.value, dtype=np.uint8)
-        _lib.check(f_plan(ins_num, M, max_wgs, hj.ctypes.data_as(ctypes.c_void_p), jb.value,
-                          ho.ctypes.data_as(ctypes.c_void_p), ob.value), "dmnerf_wgrad_plan")
+        _lib.call(f_plan, ins_num, M, max_wgs, hj, jb.value, ho, ob.value)
         while len(_plan_cache) >= 32:                      # a training run has one or two batch sizes; ragged callers do not pile up plans
             _plan_cache.pop(next(iter(_plan_cache)))
         _plan_cache[key] = (torch.from_numpy(hj).to(device), nj.value, torch.from_numpy(ho).to(device), no.value, pf.value)
@@ -295,16 +290,15 @@ class MLPRaysFunction(torch.autograd.Function):
         save = torch.empty(lib.dmnerf_train_save_floats(M), dtype=torch.float32, device=z.device)
         blob = None if mode in ("split", "f16") else model.blob()  # (the f32 dgrad reads it; the split kernels have their own blobs)
         if mode == "split":
-            fwd_blob, fn = model.blob_split(), lib.dmnerf_mlp_fwd_rays_train_split
+            fwd_blob, fn = model.blob_split(), "dmnerf_mlp_fwd_rays_train_split"
         elif mode == "f16":
-            fwd_blob, fn = model.blob_f16(), lib.dmnerf_mlp_fwd_rays_train_f16
+            fwd_blob, fn = model.blob_f16(), "dmnerf_mlp_fwd_rays_train_f16"
         elif mode == "fused":
-            fwd_blob, fn = model.blob_fused(), lib.dmnerf_mlp_fwd_rays_train_fused
+            fwd_blob, fn = model.blob_fused(), "dmnerf_mlp_fwd_rays_train_fused"
         else:
-            fwd_blob, fn = blob, lib.dmnerf_mlp_fwd_rays_train
+            fwd_blob, fn = blob, "dmnerf_mlp_fwd_rays_train"
         with _timed("mlp_fwd_train", M):
-            _lib.check(fn(_lib.ptr(fwd_blob), ins_num, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z),
-                          N, S, _lib.ptr(raw), _lib.ptr(save), _lib.stream()), "dmnerf_mlp_fwd_rays_train")
+            _lib.launch(fn, fwd_blob, ins_num, rays_o, rays_d, z, N, S, raw, save)
         ctx.check_f16 = mode == "f16" and (check_f16 if check_f16 is not None else f16_check_enabled())
         if ctx.check_f16:
             _f16_range_scan(save, M, False)
@@ -414,7 +408,7 @@ def _mlp_backward(ctx, g_raw):
         main = torch.cuda.current_stream(dev)
         # everything the side-stream kernels READ that was allocated on the main stream stays referenced until the join: freed
         # earlier, the main stream's allocator could hand the block to a kernel that runs while they are still reading
-        keep = [g_raw, ctx.save, ctx.flat, getattr(ctx, "blob", None), getattr(ctx, "blob_t", None), getattr(ctx, "blob_ts", None)]
+        keep = [g_raw, ctx.save, ctx.flat, ctx.blob, ctx.blob_t, ctx.blob_ts]
         side.wait_stream(main)
         with torch.cuda.stream(side):
             grads = _mlp_backward_on_stream(ctx, g_raw)
@@ -443,22 +437,19 @@ def _mlp_backward_on_stream(ctx, g_raw):
     dsave = torch.empty_like(ctx.save)
     Mp = _row_len(M)
     gt = torch.empty(Mp // 32, 4 + C, 32, dtype=torch.float32, device=g.device)   # d raw, block-major, written by the kernel
-    split = getattr(ctx, "blob_ts", None) is not None            # opt-in: split-bf16 backward kernels (args.mfma_split)
-    f16 = getattr(ctx, "mode", None) == "f16"
+    split = ctx.blob_ts is not None                              # opt-in: split-bf16 backward kernels (args.mfma_split)
+    f16 = ctx.mode == "f16"
     scale = _grad_scale_buffer(g.device) if f16 else None         # {2^s, 2^-s}: the f16 backward runs on 2^s dL/draw (f16 range)
     with _timed("mlp_bwd_data", M):
         if f16:
-            _lib.check(lib.dmnerf_grad_scale(_lib.ptr(g), g.numel(), _lib.ptr(scale), _lib.stream()), "dmnerf_grad_scale")
-            _lib.check(lib.dmnerf_mlp_bwd_data_f16(_lib.ptr(ctx.blob_ts), ins_num, _lib.ptr(ctx.save), _lib.ptr(g), M,
-                                                   _lib.ptr(dsave), _lib.ptr(gt), _lib.ptr(scale), _lib.stream()), "dmnerf_mlp_bwd_data_f16")
-            if getattr(ctx, "check_f16", None) if getattr(ctx, "check_f16", None) is not None else f16_check_enabled():
+            _lib.launch("dmnerf_grad_scale", g, g.numel(), scale)
+            _lib.launch("dmnerf_mlp_bwd_data_f16", ctx.blob_ts, ins_num, ctx.save, g, M, dsave, gt, scale)
+            if ctx.check_f16:
                 _f16_range_scan(dsave, M, True)
         elif split:
-            _lib.check(lib.dmnerf_mlp_bwd_data_split(_lib.ptr(ctx.blob_ts), ins_num, _lib.ptr(ctx.save), _lib.ptr(g), M,
-                                                     _lib.ptr(dsave), _lib.ptr(gt), _lib.stream()), "dmnerf_mlp_bwd_data_split")
+            _lib.launch("dmnerf_mlp_bwd_data_split", ctx.blob_ts, ins_num, ctx.save, g, M, dsave, gt)
         else:
-            _lib.check(lib.dmnerf_mlp_bwd_data(_lib.ptr(ctx.blob), _lib.ptr(ctx.blob_t), ins_num, _lib.ptr(ctx.save), _lib.ptr(g), M,
-                                               _lib.ptr(dsave), _lib.ptr(gt), _lib.stream()), "dmnerf_mlp_bwd_data")
+            _lib.launch("dmnerf_mlp_bwd_data", ctx.blob, ctx.blob_t, ins_num, ctx.save, g, M, dsave, gt)
     jobs, n_jobs, outs, n_outs, part_floats = wgrad_plan(ins_num, M, g.device, split="f16x2" if f16 else split)
     part = torch.empty(part_floats, dtype=torch.float32, device=g.device)
     flat = None
@@ -469,13 +460,10 @@ def _mlp_backward_on_stream(ctx, g_raw):
         flat = torch.empty(lib.dmnerf_param_count(ins_num), dtype=torch.float32, device=g.device)
     with _timed("mlp_bwd_weights", M):
         if f16:
-            _lib.check(lib.dmnerf_mlp_bwd_weights_f16(_lib.ptr(ctx.save), _lib.ptr(dsave), _lib.ptr(gt), M, _lib.ptr(jobs), n_jobs, _lib.ptr(outs),
-                                                               n_outs, _lib.ptr(ctx.flat), ins_num, _lib.ptr(part), _lib.ptr(flat), _lib.ptr(scale),
-                                                               _lib.stream()), "dmnerf_mlp_bwd_weights_f16")
+            _lib.launch("dmnerf_mlp_bwd_weights_f16", ctx.save, dsave, gt, M, jobs, n_jobs, outs, n_outs, ctx.flat, ins_num, part, flat, scale)
         else:
-            f_wgrad = lib.dmnerf_mlp_bwd_weights_split if split else lib.dmnerf_mlp_bwd_weights
-            _lib.check(f_wgrad(_lib.ptr(ctx.save), _lib.ptr(dsave), _lib.ptr(gt), M, _lib.ptr(jobs), n_jobs, _lib.ptr(outs), n_outs,
-                               _lib.ptr(ctx.flat), ins_num, _lib.ptr(part), _lib.ptr(flat), _lib.stream()), "dmnerf_mlp_bwd_weights")
+            f_wgrad = "dmnerf_mlp_bwd_weights_split" if split else "dmnerf_mlp_bwd_weights"
+            _lib.launch(f_wgrad, ctx.save, dsave, gt, M, jobs, n_jobs, outs, n_outs, ctx.flat, ins_num, part, flat)
     ctx.save = None
     return tuple(split_flat_grads(model, flat))
 
@@ -491,10 +479,10 @@ class MLPEmbeddedFunction(torch.autograd.Function):
         ins_num = model.ins_num
         raw = torch.empty(M, 4 + ins_num + 1, dtype=torch.float32, device=x.device)
         save = torch.empty(lib.dmnerf_train_save_floats(M), dtype=torch.float32, device=x.device)
-        _lib.check(lib.dmnerf_mlp_fwd_embedded_train(_lib.ptr(model.blob()), ins_num, _lib.ptr(x), M, _lib.ptr(raw), _lib.ptr(save),
-                                                     _lib.stream()), "dmnerf_mlp_fwd_embedded_train")
+        _lib.launch("dmnerf_mlp_fwd_embedded_train", model.blob(), ins_num, x, M, raw, save)
         ctx.model, ctx.M, ctx.save = model, M, save
         ctx.blob, ctx.blob_t, ctx.flat = model.blob(), model.blob_t(), model.flat()
+        ctx.mode, ctx.blob_ts, ctx.check_f16 = None, None, False      # what MLPRaysFunction sets: _mlp_backward reads all three
         return raw
 
     @staticmethod
@@ -533,21 +521,17 @@ class CompositeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, z, rays_d):
-        lib = _lib.load()
         N, S, C, rgb, w, depth, ins = _composite_outputs(raw)
-        _lib.check(lib.dmnerf_composite_fwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays_d), N, S, C, _lib.ptr(rgb), _lib.ptr(w),
-                                            _lib.ptr(depth), _lib.ptr(ins), _lib.stream()), "dmnerf_composite_fwd")
+        _lib.launch("dmnerf_composite_fwd", raw, z, rays_d, N, S, C, rgb, w, depth, ins)
         ctx.save_for_backward(raw, z, rays_d, ins)
         ctx.set_materialize_grads(False)                 # unused outputs (weights, depth) arrive as None, not as zero-filled tensors
         return rgb, w, depth, ins
 
     @staticmethod
     def backward(ctx, g_rgb, g_w, g_depth, g_ins):
-        lib = _lib.load()
         raw, z, rays_d, ins = ctx.saved_tensors
         N, S, C, g_rgb, g_w, g_depth, g_ins, d_raw = _composite_cotangents(raw, g_rgb, g_w, g_depth, g_ins)
-        _lib.check(lib.dmnerf_composite_bwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays_d), _lib.ptr(ins), _lib.ptr(g_rgb), _lib.ptr(g_ins),
-                                            _lib.ptr(g_depth), _lib.ptr(g_w), N, S, C, _lib.ptr(d_raw), _lib.stream()), "dmnerf_composite_bwd")
+        _lib.launch("dmnerf_composite_bwd", raw, z, rays_d, ins, g_rgb, g_ins, g_depth, g_w, N, S, C, d_raw)
         return d_raw, None, None
 
 
@@ -561,12 +545,10 @@ class CompositePenFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, z, rays_d, consts):
-        lib = _lib.load()
         N, S, C, rgb, w, depth, ins = _composite_outputs(raw)
         part = torch.empty(N, 4, dtype=torch.float64, device=raw.device)
         tol, k2w, kh = consts
-        _lib.check(lib.dmnerf_composite_pen_fwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays_d), N, S, C, tol, k2w, kh, _lib.ptr(rgb), _lib.ptr(w),
-                                                _lib.ptr(depth), _lib.ptr(ins), _lib.ptr(part), _lib.stream()), "dmnerf_composite_pen_fwd")
+        _lib.launch("dmnerf_composite_pen_fwd", raw, z, rays_d, N, S, C, tol, k2w, kh, rgb, w, depth, ins, part)
         ctx.save_for_backward(raw, z, rays_d, ins, depth)
         ctx.consts = consts
         ctx.set_materialize_grads(False)                 # unused outputs (weights, depth, part) arrive as None: no zero fills
@@ -574,18 +556,14 @@ class CompositePenFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb, g_w, g_depth, g_ins, g_part):
-        lib = _lib.load()
         raw, z, rays_d, ins, depth = ctx.saved_tensors
         N, S, C, g_rgb, g_w, g_depth, g_ins, d_raw = _composite_cotangents(raw, g_rgb, g_w, g_depth, g_ins)
         if g_part is None or N == 0:
-            _lib.check(lib.dmnerf_composite_bwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays_d), _lib.ptr(ins), _lib.ptr(g_rgb), _lib.ptr(g_ins),
-                                                _lib.ptr(g_depth), _lib.ptr(g_w), N, S, C, _lib.ptr(d_raw), _lib.stream()), "dmnerf_composite_bwd")
+            _lib.launch("dmnerf_composite_bwd", raw, z, rays_d, ins, g_rgb, g_ins, g_depth, g_w, N, S, C, d_raw)
         else:
             row = g_part[0].to(torch.float64).contiguous()          # (a view of the producer's 4 doubles: no copy)
             tol, k2w, kh = ctx.consts
-            _lib.check(lib.dmnerf_composite_pen_bwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays_d), _lib.ptr(ins), _lib.ptr(depth), _lib.ptr(g_rgb),
-                                                    _lib.ptr(g_ins), _lib.ptr(g_depth), _lib.ptr(g_w), _lib.ptr(row), N, S, C, tol, k2w, kh,
-                                                    _lib.ptr(d_raw), _lib.stream()), "dmnerf_composite_pen_bwd")
+            _lib.launch("dmnerf_composite_pen_bwd", raw, z, rays_d, ins, depth, g_rgb, g_ins, g_depth, g_w, row, N, S, C, tol, k2w, kh, d_raw)
         return d_raw, None, None, None
 
 
@@ -665,8 +643,7 @@ class ScatterRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw_c, raw, sel, n_sel):
         n_pad, width = raw_c.shape[0], raw.shape[-1]
-        _lib.check(_lib.load().dmnerf_rows_scatter(_lib.ptr(raw_c), n_pad, _lib.ptr(sel), n_sel, _lib.ptr(raw), raw.shape[0] * raw.shape[1],
-                                                   width, _lib.stream()), "dmnerf_rows_scatter")
+        _lib.launch("dmnerf_rows_scatter", raw_c, n_pad, sel, n_sel, raw, raw.shape[0] * raw.shape[1], width)
         ctx.sel, ctx.n_sel, ctx.shape_c = sel, n_sel, tuple(raw_c.shape)
         ctx.mark_dirty(raw)
         return raw
@@ -675,8 +652,7 @@ class ScatterRows(torch.autograd.Function):
     def backward(ctx, g_raw):
         g = _lib.f32(g_raw)
         g_c = torch.empty(ctx.shape_c, dtype=torch.float32, device=g.device)
-        _lib.check(_lib.load().dmnerf_rows_gather(_lib.ptr(g), g.shape[0] * g.shape[1], _lib.ptr(ctx.sel), ctx.n_sel, _lib.ptr(g_c),
-                                                  ctx.shape_c[0], g.shape[-1], _lib.stream()), "dmnerf_rows_gather")
+        _lib.launch("dmnerf_rows_gather", g, g.shape[0] * g.shape[1], ctx.sel, ctx.n_sel, g_c, ctx.shape_c[0], g.shape[-1])
         return g_c, None, None, None
 
 
@@ -714,15 +690,13 @@ def run_network_train_skip(model, rays_o, rays_d, z, grid, split=None, check_f16
     N, S = z.shape
     rays_o, rays_d, z, raw, sel, count = render.skip_select(who, TRAIN_SKIP_WORDS, grid, rays_o, rays_d, z, 4 + model.ins_num + 1, 0.0, counts)
     rays_o, rays_d, z, dev = rays_o.detach(), rays_d.detach(), z.detach(), z.device
-    lib = _lib.load()
     n_sel = 0 if count is None else int(count.item())              # the host read: one synchronisation per call
     n_pad = -(-n_sel // bucket) * bucket
     o_c = torch.empty(n_pad, 3, dtype=torch.float32, device=dev)
     d_c = torch.empty(n_pad, 3, dtype=torch.float32, device=dev)
     z_c = torch.empty(n_pad, 1, dtype=torch.float32, device=dev)
     with torch.no_grad():
-        _lib.check(lib.dmnerf_skip_gather_samples(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z), N, max(S, 1), _lib.ptr(sel), n_sel, n_pad,
-                                                  _lib.ptr(o_c), _lib.ptr(d_c), _lib.ptr(z_c), _lib.stream()), "dmnerf_skip_gather_samples")
+        _lib.launch("dmnerf_skip_gather_samples", rays_o, rays_d, z, N, max(S, 1), sel, n_sel, n_pad, o_c, d_c, z_c)
     mode = "f16" if split == "f16x2" else None
     raw_c = _run_network_train(model, o_c, d_c, z_c, mode, check_f16)     # [n_pad, 1, width]; n_pad = 0: no launch, zero gradients
     return ScatterRows.apply(raw_c, raw, sel, n_sel)

@@ -156,8 +156,7 @@ def edit_rays(H, W, K, poses, kinds, offsets=None, row0=0, nrows=None, device=No
         if tuple(off.shape) != (T, H):
             raise ValueError(f"edit_rays: offsets must be [T={T}, H={H}], got {tuple(off.shape)}")
     rays = torch.empty(T, 2, nrows * W, 3, dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().dmnerf_edit_rays(H, W, intr.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p), kind, T,
-                                            _lib.ptr(off), row0, nrows, _lib.ptr(rays), _lib.stream()), "dmnerf_edit_rays")
+    _lib.launch("dmnerf_edit_rays", H, W, intr, c, kind, T, off, row0, nrows, rays)
     return rays
 
 
@@ -200,8 +199,7 @@ def frame_products(rgb, ins=None, lut=None):
             if lut.dtype != torch.uint8 or tuple(lut.shape) != (C, 3):
                 raise ValueError(f"frame_products: lut must be uint8 [{C}, 3], got {lut.dtype} {tuple(lut.shape)}")
             ins_img = torch.empty(*lead, 3, dtype=torch.uint8, device=dev)
-    _lib.check(_lib.load().dmnerf_edit_products(_lib.ptr(r), rs, _lib.ptr(x), xs, C, _lib.ptr(lut), n, _lib.ptr(rgb8), _lib.ptr(label),
-                                                _lib.ptr(mask), _lib.ptr(ins_img), _lib.stream()), "dmnerf_edit_products")
+    _lib.launch("dmnerf_edit_products", r, rs, x, xs, C, lut, n, rgb8, label, mask, ins_img)
     return rgb8, label, mask, ins_img
 
 
@@ -224,9 +222,7 @@ def pick(label_grid, H, W, K, pose, pixels, near, far, labels=None):
     idx = torch.tensor([r * W + c for c, r in pixels], dtype=torch.int64).to(dev)
     rays = torch.empty(2, P, 3, dtype=torch.float32, device=dev)
     if P:
-        _lib.check(_lib.load().dmnerf_raygen_select(H, W, intr.ctypes.data_as(ctypes.c_void_p), c2w.ctypes.data_as(ctypes.c_void_p),
-                                                    _lib.ptr(idx), P, _lib.ptr(rays[0]), _lib.ptr(rays[1]), _lib.stream()),
-                   "dmnerf_raygen_select")
+        _lib.launch("dmnerf_raygen_select", H, W, intr, c2w, idx, P, rays[0], rays[1])
     out = label_grid.trace(rays[0], rays[1], near, far, labels)
     host = torch.cat([out["label"].double()[:, None], out["t"].double()[:, None], out["cell"].double()[:, None], rays[0].double(),
                       rays[1].double()], dim=1).cpu().numpy()                     # the one host read; every value is exact in float64

@@ -75,8 +75,7 @@ def query_density(model, points, voxel=None, fuse_heads=False):
     out = torch.empty(M, dtype=torch.float32, device=pts.device)
     if not model._fused_ok():
         return _generic_density(model, pts, voxel, out)
-    _lib.check(_lib.load().dmnerf_mlp_fwd_points_density(_lib.ptr(_blob(model, fuse_heads)), model.ins_num, _lib.ptr(pts), M,
-                                                         _lib.ptr(out), voxel, _lib.stream()), "dmnerf_mlp_fwd_points_density")
+    _lib.launch("dmnerf_mlp_fwd_points_density", _blob(model, fuse_heads), model.ins_num, pts, M, out, voxel)
     return out
 
 
@@ -134,11 +133,9 @@ def occupancy_grid(model_fine, transform, args, extents=(1.9, 7.0, 7.0), occ_ran
     blob = _blob(model_fine, bool(getattr(args, "fuse_heads", False)))
     c_scale = (ctypes.c_float * 3)(*scale.tolist())
     c_T = (ctypes.c_float * 12)(*T.reshape(-1).tolist())
-    fn, stream = _lib.load().dmnerf_occupancy_slab, _lib.stream()
     for m0 in range(0, total, slab):
         n = min(slab, total - m0)
-        _lib.check(fn(_lib.ptr(blob), model_fine.ins_num, _lib.ptr(t), dim, c_scale, c_T, m0, n, _lib.ptr(out[m0:m0 + n]), voxel, stream),
-                   "dmnerf_occupancy_slab")
+        _lib.launch("dmnerf_occupancy_slab", blob, model_fine.ins_num, t, dim, c_scale, c_T, m0, n, out[m0:m0 + n], voxel)
     return out.reshape(dim, dim, dim)
 
 
@@ -164,7 +161,6 @@ def label_points(vertices, normals, models, args, chunk=None):
     V = v.shape[0]
     label = torch.empty(V, dtype=torch.int64, device=v.device)
     conf = torch.empty(V, dtype=torch.float32, device=v.device)
-    lib = _lib.load()
     z = None
     with torch.no_grad():
         render = R.fine_renderer(model_coarse, model_fine, args)
@@ -174,8 +170,7 @@ def label_points(vertices, normals, models, args, chunk=None):
                 z = helpers.z_val_sample(e - s, 0.01, 15, args.N_samples, device=v.device)
             ins = render(torch.stack([rays_o[s:e], rays_d[s:e]], dim=0), None, None, model_coarse, model_fine, z, args)['ins_fine']
             ins = ins.contiguous()
-            _lib.check(lib.dmnerf_ins_label_conf(_lib.ptr(ins), e - s, ins.shape[-1], _lib.ptr(label[s:e]), _lib.ptr(conf[s:e]),
-                                                 _lib.stream()), "dmnerf_ins_label_conf")
+            _lib.launch("dmnerf_ins_label_conf", ins, e - s, ins.shape[-1], label[s:e], conf[s:e])
     return label, conf
 
 
@@ -222,10 +217,8 @@ def extract_surface(occ, level=0.45):
         raise ValueError(f"extract_surface expects occ [dx, dy, dz], got {tuple(occ.shape)}")
     dx, dy, dz = occ.shape
     n = occ.numel()
-    lib, stream = _lib.load(), _lib.stream()
     counts = torch.empty(2, max(n, 1), dtype=torch.uint8, device=occ.device)
-    _lib.check(lib.dmnerf_surface_count(_lib.ptr(occ), dx, dy, dz, float(level), _lib.ptr(counts[0]), _lib.ptr(counts[1]), stream),
-               "dmnerf_surface_count")
+    _lib.launch("dmnerf_surface_count", occ, dx, dy, dz, float(level), counts[0], counts[1])
     scans = torch.cumsum(counts, dim=1, dtype=torch.int64)
     V, F = scans[:, -1].tolist()
     if V >= 2 ** 31 or F >= 2 ** 31:
@@ -234,9 +227,7 @@ def extract_surface(occ, level=0.45):
         return _empty_surface(occ.device)
     vertices = torch.empty(V, 3, dtype=torch.float32, device=occ.device)
     faces = torch.empty(F, 3, dtype=torch.int32, device=occ.device)
-    _lib.check(lib.dmnerf_surface_emit(_lib.ptr(occ), dx, dy, dz, float(level), _lib.ptr(counts[0]), _lib.ptr(counts[1]),
-                                       _lib.ptr(scans[0]), _lib.ptr(scans[1]), V, F, _lib.ptr(vertices), _lib.ptr(faces), stream),
-               "dmnerf_surface_emit")
+    _lib.launch("dmnerf_surface_emit", occ, dx, dy, dz, float(level), counts[0], counts[1], scans[0], scans[1], V, F, vertices, faces)
     return vertices, faces
 
 
@@ -285,8 +276,7 @@ def vertex_normals(vertices, faces, occ_shape=None):
     if V == 0 or F == 0:
         return normals
     inc_vertex, inc_slot = torch.sort(faces.reshape(-1), stable=True)
-    _lib.check(_lib.load().dmnerf_surface_normals(_lib.ptr(v), V, _lib.ptr(faces), F, _lib.ptr(inc_vertex), _lib.ptr(inc_slot),
-                                                  _lib.ptr(normals), _lib.stream()), "dmnerf_surface_normals")
+    _lib.launch("dmnerf_surface_normals", v, V, faces, F, inc_vertex, inc_slot, normals)
     return normals
 
 
@@ -309,8 +299,7 @@ def _clusters(faces):
     a, b = faces.long(), faces[:, [1, 2, 0]].long()
     key, slot = torch.sort(((torch.minimum(a, b) << 32) | torch.maximum(a, b)).reshape(-1))
     parent = torch.arange(F, dtype=torch.int32, device=faces.device)
-    _lib.check(_lib.load().dmnerf_surface_clusters(_lib.ptr(key), _lib.ptr(slot), F, _lib.ptr(parent), _lib.ptr(rep), _lib.ptr(count),
-                                                   _lib.stream()), "dmnerf_surface_clusters")
+    _lib.launch("dmnerf_surface_clusters", key, slot, F, parent, rep, count)
     return rep, count
 
 
@@ -326,9 +315,7 @@ def clean_surface(vertices, normals, faces, min_triangles=400, keep_single_clust
     single = torch.argmax(count).reshape(1) if keep_single_cluster and F else None        # first maximum: the smallest representative
     keep = torch.zeros(F, dtype=torch.uint8, device=dev)
     used = torch.zeros(V, dtype=torch.uint8, device=dev)
-    lib, stream = _lib.load(), _lib.stream()
-    _lib.check(lib.dmnerf_surface_clean_mark(_lib.ptr(faces), F, V, _lib.ptr(rep), _lib.ptr(count), int(min_triangles), _lib.ptr(single),
-                                             _lib.ptr(keep), _lib.ptr(used), stream), "dmnerf_surface_clean_mark")
+    _lib.launch("dmnerf_surface_clean_mark", faces, F, V, rep, count, int(min_triangles), single, keep, used)
     fscan = torch.cumsum(keep, dim=0, dtype=torch.int32)
     vscan = torch.cumsum(used, dim=0, dtype=torch.int32)
     Fk, Vk = torch.stack([fscan[-1] if F else fscan.sum(), vscan[-1] if V else vscan.sum()]).tolist()
@@ -336,9 +323,7 @@ def clean_surface(vertices, normals, faces, min_triangles=400, keep_single_clust
     out_n = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
     out_f = torch.empty(Fk, 3, dtype=torch.int32, device=dev)
     kept = torch.empty(Vk, dtype=torch.int64, device=dev)
-    _lib.check(lib.dmnerf_surface_clean_compact(_lib.ptr(v), _lib.ptr(normals), _lib.ptr(faces), V, F, _lib.ptr(keep), _lib.ptr(used),
-                                                _lib.ptr(fscan), _lib.ptr(vscan), Vk, Fk, _lib.ptr(out_v), _lib.ptr(out_n), _lib.ptr(out_f),
-                                                _lib.ptr(kept), stream), "dmnerf_surface_clean_compact")
+    _lib.launch("dmnerf_surface_clean_compact", v, normals, faces, V, F, keep, used, fscan, vscan, Vk, Fk, out_v, out_n, out_f, kept)
     return out_v, out_n, out_f, kept
 
 
@@ -516,8 +501,7 @@ class SkipGrid:
             raise ValueError(f"SkipGrid.from_sigma expects sigma [dx, dy, dz], got {tuple(sigma.shape)}")
         g = cls.empty(lo, hi, tuple(sigma.shape), outside, sigma.device)
         dx, dy, dz = g.dims
-        _lib.check(_lib.load().dmnerf_skip_grid_build(_lib.ptr(sigma), dx, dy, dz, float(threshold), int(dilate), _lib.ptr(g.bits),
-                                                      _lib.stream()), "dmnerf_skip_grid_build")
+        _lib.launch("dmnerf_skip_grid_build", sigma, dx, dy, dz, float(threshold), int(dilate), g.bits)
         return g
 
     def cell_centres(self, i0=0, i1=None, device=None):
@@ -593,8 +577,7 @@ class SkipGrid:
         if N * S == 0:
             return self
         g = self.c_struct()
-        _lib.check(_lib.load().dmnerf_skip_grid_mark(ctypes.byref(g), _lib.ptr(self.bits), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z),
-                                                     _lib.ptr(weights), N, S, threshold, _lib.stream()), "dmnerf_skip_grid_mark")
+        _lib.launch("dmnerf_skip_grid_mark", g, self.bits, rays_o, rays_d, z, weights, N, S, threshold)
         return self
 
     def dilated(self, r):
@@ -602,8 +585,7 @@ class SkipGrid:
         is set here (``0 <= r <= 4``; ``dmnerf_skip_grid_dilate``).  ``from_sigma(s, dilate=0).dilated(r)`` is ``from_sigma(s, dilate=r)``."""
         out = SkipGrid.empty(self.lo, self.hi, self.dims, self.outside, self.bits.device)
         dx, dy, dz = self.dims
-        _lib.check(_lib.load().dmnerf_skip_grid_dilate(_lib.ptr(self.bits), dx, dy, dz, int(r), _lib.ptr(out.bits), _lib.stream()),
-                   "dmnerf_skip_grid_dilate")
+        _lib.launch("dmnerf_skip_grid_dilate", self.bits, dx, dy, dz, int(r), out.bits)
         return out
 
     @classmethod
@@ -748,17 +730,16 @@ def _label_loop(who, model_fine, occ, sigma_threshold, slab, split, bake):
     C = model_fine.ins_num + 1
     labels = torch.empty(dx, dy, dz, dtype=torch.uint8, device=occ.bits.device)
     cells = torch.empty(dx, dy, dz, 4, dtype=torch.float32, device=occ.bits.device) if bake else None
-    lib, step = _lib.load(), max(1, slab // (dy * dz))
+    step = max(1, slab // (dy * dz))
     for i0 in range(0, dx, step):
         i1 = min(i0 + step, dx)
         o, d, z = label_rays(occ, i0, i1)
         raw = R.run_network_skip(model_fine, o, d, z, occ, split=split)
         m = (i1 - i0) * dy * dz
         if bake:
-            _lib.check(lib.dmnerf_bake_cells(_lib.ptr(raw), m, C, sigma_threshold, _lib.ptr(labels[i0:i1]), _lib.ptr(cells[i0:i1]),
-                                             _lib.stream()), "dmnerf_bake_cells")
+            _lib.launch("dmnerf_bake_cells", raw, m, C, sigma_threshold, labels[i0:i1], cells[i0:i1])
         else:
-            _lib.check(lib.dmnerf_label_cells(_lib.ptr(raw), m, C, sigma_threshold, _lib.ptr(labels[i0:i1]), _lib.stream()), "dmnerf_label_cells")
+            _lib.launch("dmnerf_label_cells", raw, m, C, sigma_threshold, labels[i0:i1])
     return labels, cells, C
 
 
@@ -808,8 +789,7 @@ class LabelGrid:
         index_sum = torch.empty(C, 3, dtype=torch.int64, device=dev)
         lo_idx = torch.empty(C, 3, dtype=torch.int32, device=dev)
         hi_idx = torch.empty(C, 3, dtype=torch.int32, device=dev)
-        _lib.check(_lib.load().dmnerf_label_stats(_lib.ptr(self.labels), dx, dy, dz, C, _lib.ptr(count), _lib.ptr(index_sum),
-                                                  _lib.ptr(lo_idx), _lib.ptr(hi_idx), _lib.stream()), "dmnerf_label_stats")
+        _lib.launch("dmnerf_label_stats", self.labels, dx, dy, dz, C, count, index_sum, lo_idx, hi_idx)
         n = count.double()
         lo, cell = self.lo.astype(np.float64), self.cell.astype(np.float64)
         # (python scalars, not a host tensor: no host-to-device copy, so the call can be captured)
@@ -824,8 +804,7 @@ class LabelGrid:
         same box: ``dmnerf_skip_grid_from_labels``, then ``dilated(dilate)``.  An unlabelled cell is never set."""
         mask = (ctypes.c_uint32 * 4)(*label_mask_words(labels, self.C))
         g = SkipGrid.empty(self.lo, self.hi, self.dims, outside, self.labels.device)
-        _lib.check(_lib.load().dmnerf_skip_grid_from_labels(_lib.ptr(self.labels), g.n_cells, mask, _lib.ptr(g.bits), _lib.stream()),
-                   "dmnerf_skip_grid_from_labels")
+        _lib.launch("dmnerf_skip_grid_from_labels", self.labels, g.n_cells, mask, g.bits)
         return g.dilated(dilate) if int(dilate) else g
 
     # ---- rays through the volume (csrc/label_trace.hip; tests/_label_trace_restate.py states it in numpy)
@@ -859,11 +838,8 @@ class LabelGrid:
         out = {"label": torch.empty(N, dtype=torch.uint8, device=dev), "t": torch.empty(N, dtype=torch.float32, device=dev),
                "cell": torch.empty(N, dtype=torch.int32, device=dev), "source": torch.empty(N, dtype=torch.uint8, device=dev)}
         f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
-        _lib.check(_lib.load().dmnerf_label_trace(_lib.ptr(self.labels), f3(self.lo), f3(self.cell), f3(self.inv_cell),
-                                                  (ctypes.c_int * 3)(*self.dims), self.C, _lib.ptr(rays), R, N,
-                                                  (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), _lib.ptr(out["label"]),
-                                                  _lib.ptr(out["t"]), _lib.ptr(out["cell"]), _lib.ptr(out["source"]), _lib.stream()),
-                   "dmnerf_label_trace")
+        _lib.launch("dmnerf_label_trace", self.labels, f3(self.lo), f3(self.cell), f3(self.inv_cell), (ctypes.c_int * 3)(*self.dims), self.C, rays, R,
+                    N, (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), out["label"], out["t"], out["cell"], out["source"])
         return out
 
     def trace(self, rays_o, rays_d, near, far, labels=None):
@@ -934,12 +910,9 @@ class BakedGrid(LabelGrid):
                "acc": torch.empty(N, dtype=torch.float32, device=dev), "label": torch.empty(N, dtype=torch.uint8, device=dev),
                "source": torch.empty(N, dtype=torch.uint8, device=dev), "nseg": torch.empty(N, dtype=torch.int32, device=dev)}
         f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
-        _lib.check(_lib.load().dmnerf_baked_render(_lib.ptr(self.labels), _lib.ptr(self.cells), f3(self.lo), f3(self.cell), f3(self.inv_cell),
-                                                   (ctypes.c_int * 3)(*self.dims), self.C, _lib.ptr(rays), R, N,
-                                                   (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), stop, _lib.ptr(out["rgb"]),
-                                                   _lib.ptr(out["depth"]), _lib.ptr(out["acc"]), _lib.ptr(out["label"]),
-                                                   _lib.ptr(out["source"]), _lib.ptr(out["nseg"]), _lib.stream()),
-                   "dmnerf_baked_render")
+        _lib.launch("dmnerf_baked_render", self.labels, self.cells, f3(self.lo), f3(self.cell), f3(self.inv_cell), (ctypes.c_int * 3)(*self.dims),
+                    self.C, rays, R, N, (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), stop, out["rgb"], out["depth"], out["acc"],
+                    out["label"], out["source"], out["nseg"])
         return out
 
     def render(self, rays_o, rays_d, near, far, labels=None, stop=0.0):

@@ -23,12 +23,10 @@ from . import _lib
 
 
 def _gemm(A, sai, sak, B, sbk, sbj, C, ldc, I, J, K, bias=None, relu=False, mask=None, ldm=0, accumulate=False, splits=1):
-    lib = _lib.load()
     ws = None
     if splits > 1:
         ws = torch.empty(splits * I * J, dtype=torch.float32, device=C.device)
-    _lib.check(lib.dmnerf_gemm(_lib.ptr(A), sai, sak, _lib.ptr(B), sbk, sbj, _lib.ptr(C), ldc, I, J, K, _lib.ptr(bias), int(relu),
-                               _lib.ptr(mask), ldm, int(accumulate), _lib.ptr(ws), splits, _lib.stream()), "dmnerf_gemm")
+    _lib.launch("dmnerf_gemm", A, sai, sak, B, sbk, sbj, C, ldc, I, J, K, bias, int(relu), mask, ldm, int(accumulate), ws, splits)
 
 
 def _splits(I, J, K):
@@ -71,8 +69,7 @@ class _Packed:
         self.k0, self.k1, self.n = k0, k1, n_rows
         self.w = torch.empty(self.rows_pad * self.ldb, dtype=torch.float32, device=W.device)
         self.b = torch.empty(self.rows_pad, dtype=torch.float32, device=W.device) if bias is not None else None
-        _lib.check(lib.dmnerf_pack_nt(_lib.ptr(W), W.stride(0), n_rows, c0, k0, c1, k1, int(transposed), _lib.ptr(bias), _lib.ptr(self.w),
-                                      self.rows_pad, self.ldb, _lib.ptr(self.b), _lib.stream()), "dmnerf_pack_nt")
+        _lib.launch("dmnerf_pack_nt", W, W.stride(0), n_rows, c0, k0, c1, k1, int(transposed), bias, self.w, self.rows_pad, self.ldb, self.b)
 
 
 def _floats_from(t, col=0):
@@ -84,11 +81,9 @@ def _linear_nt(a0, pk, out, ldc, n_store, n_zero, M, a1=None, relu=False, mask=N
     """out[:, :n_store] = act(A W^T + b) with A = a0 (| a1: the second K range of a cat input), W packed (``_Packed``); columns
     [n_store, n_zero) of ``out`` are zeroed (its pad columns)."""
     assert pk.k0 == a0.cols and pk.k1 == (a1.cols if a1 is not None else 0)
-    _lib.check(_lib.load().dmnerf_gemm_nt(_lib.ptr(a0.buf), a0.ld, _floats_from(a0.buf), pk.k0,
-                                          _lib.ptr(a1.buf) if a1 is not None else None, a1.ld if a1 is not None else 0,
-                                          _floats_from(a1.buf) if a1 is not None else 0, pk.k1,
-                                          _lib.ptr(pk.w), pk.w.numel(), pk.ldb, _lib.ptr(pk.b), _lib.ptr(out), ldc, n_store, n_zero, M, int(relu),
-                                          _lib.ptr(mask), ldm, int(accumulate), _lib.stream()), "dmnerf_gemm_nt")
+    _lib.launch("dmnerf_gemm_nt", a0.buf, a0.ld, _floats_from(a0.buf), pk.k0, a1.buf if a1 is not None else None,
+                a1.ld if a1 is not None else 0, _floats_from(a1.buf) if a1 is not None else 0, pk.k1, pk.w, pk.w.numel(), pk.ldb, pk.b, out, ldc,
+                n_store, n_zero, M, int(relu), mask, ldm, int(accumulate))
 
 
 def _tn_ok(t):
@@ -105,8 +100,7 @@ def _wgrad_tn(dy, n_out, x, n_in, M, dW, ldw, want_bias):
     if n_ws < 0:
         raise RuntimeError("dmnerf_gemm_tn_ws_floats: " + _lib.last_error())
     ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
-    _lib.check(lib.dmnerf_gemm_tn(_lib.ptr(dy.buf), dy.ld, _floats_from(dy.buf), n_out, _lib.ptr(x.buf), x.ld, _floats_from(x.buf), n_in, M,
-                                  _lib.ptr(dW), ldw, _lib.ptr(db), _lib.ptr(ws), ws.numel(), _lib.stream()), "dmnerf_gemm_tn")
+    _lib.launch("dmnerf_gemm_tn", dy.buf, dy.ld, _floats_from(dy.buf), n_out, x.buf, x.ld, _floats_from(x.buf), n_in, M, dW, ldw, db, ws, ws.numel())
     return db
 
 
@@ -129,7 +123,7 @@ def _colsum(dy, n_out, M):
     db = torch.empty(n_out, dtype=torch.float32, device=dy.buf.device)
     slices = int(max(1, min(256, (M + 4095) // 4096)))
     ws = torch.empty(slices * n_out, dtype=torch.float32, device=dy.buf.device)
-    _lib.check(_lib.load().dmnerf_colsum(_lib.ptr(dy.buf), dy.ld, M, n_out, _lib.ptr(db), _lib.ptr(ws), slices, _lib.stream()), "dmnerf_colsum")
+    _lib.launch("dmnerf_colsum", dy.buf, dy.ld, M, n_out, db, ws, slices)
     return db
 
 
@@ -162,7 +156,7 @@ def _wgrad(dy, ldy, n_out, x, ldx, n_in, M):
 def _slice_act(src, ld_src, col, n, M):
     """Columns [col, col + n) of a row-major matrix as a gemm_nt operand: its own row-padded buffer, pad columns zero."""
     t = _Act.empty(M, n, src.device)
-    _lib.check(_lib.load().dmnerf_copy_cols_pad(_lib.ptr(src[:, col:]), ld_src, _lib.ptr(t.buf), t.ld, M, n, t.ld, _lib.stream()), "dmnerf_copy_cols_pad")
+    _lib.launch("dmnerf_copy_cols_pad", src[:, col:], ld_src, t.buf, t.ld, M, n, t.ld)
     return t
 
 
@@ -246,7 +240,6 @@ def forward_layers(net, x_pos, x_dir, save):
     pk = net.packed_forward()
     h = None
     hs = []                                                  # the ReLU output of every trunk layer
-    lib = _lib.load()
     chained = save is None and _chain_ok(W, net.inp, net.D) and os.environ.get("DMNERF_GENERIC_CHAIN", "1") != "0"
     if chained:
         # inference on a narrow network: the whole trunk as ONE launch, activations LDS-resident from layer to layer (csrc/gemm_chain.hip)
@@ -255,8 +248,7 @@ def forward_layers(net, x_pos, x_dir, save):
             p_ = pk[f"mlps.{i}"]
             arr[i] = _lib.ChainLayer(p_.w.data_ptr(), p_.b.data_ptr(), p_.ldb, int(i > 0), int(i == 0 or net.after_skip(i)), 1)
         h = _Act.empty(M, W, dev)
-        _lib.check(lib.dmnerf_mlp_chain(_lib.ptr(x_pos.buf), x_pos.ld, _floats_from(x_pos.buf), net.inp, arr, net.D, W, _lib.ptr(h.buf), h.ld, M,
-                                        _lib.stream()), "dmnerf_mlp_chain")
+        _lib.launch("dmnerf_mlp_chain", x_pos.buf, x_pos.ld, _floats_from(x_pos.buf), net.inp, arr, net.D, W, h.buf, h.ld, M)
     for i in range(net.D if not chained else 0):
         out = _Act.empty(M, W, dev)
         if i == 0:
@@ -394,7 +386,6 @@ def _run(model, x_pos, x_dir, train):
 def run_network(model, rays_o, rays_d, z, train=False):
     """pts = o + d z -> embed(pts) | embed(d/|d|) -> model, for any network shape: [N,3], [N,3], [N,S] -> raw [N,S,4+C]."""
     _check_shape(model)
-    lib = _lib.load()
     rays_o, rays_d, z = _lib.f32(rays_o.reshape(-1, 3)), _lib.f32(rays_d.reshape(-1, 3)), _lib.f32(z)
     _lib.require_gpu(rays_o, rays_d, z)
     N, S = z.shape
@@ -404,7 +395,6 @@ def run_network(model, rays_o, rays_d, z, train=False):
         raise NotImplementedError("dm_nerf: the encoders must be get_embedder(multires, 0) outputs (3 + 6 L channels)")
     # points, view directions and both encodings in one launch, straight into the row-padded operands of the first layers
     x_pos, x_dir = _Act.empty(M, model.input_ch_pts, z.device), _Act.empty(M, model.input_ch_views, z.device)
-    _lib.check(lib.dmnerf_ray_embed(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z), N, S, Lp, Lv, _lib.ptr(x_pos.buf), x_pos.ld,
-                                    _lib.ptr(x_dir.buf), x_dir.ld, _lib.stream()), "dmnerf_ray_embed")
+    _lib.launch("dmnerf_ray_embed", rays_o, rays_d, z, N, S, Lp, Lv, x_pos.buf, x_pos.ld, x_dir.buf, x_dir.ld)
     out = _run(model, x_pos, x_dir, train)
     return out.reshape(N, S, out.shape[-1])

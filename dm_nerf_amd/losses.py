@@ -41,9 +41,7 @@ class _TrainLosses(torch.autograd.Function):
             raise ValueError(f"train_losses: unsupported N={Nc} ins_num={ins_num} (ins_num <= 128)")
         work = torch.empty(2, nbytes, dtype=torch.uint8, device=dev)
         crit = torch.empty(2, 4, **f32)
-        _lib.check(lib.dmnerf_ins_criterion_fwd2(_lib.ptr(ins_f), _lib.ptr(ins_c), _lib.ptr(labels), Nc, ins_num, _lib.ptr(work[0]),
-                                                 _lib.ptr(work[1]), nbytes, _lib.ptr(crit[0]), _lib.ptr(crit[1]), _lib.stream()),
-                   "dmnerf_ins_criterion_fwd2")
+        _lib.launch("dmnerf_ins_criterion_fwd2", ins_f, ins_c, labels, Nc, ins_num, work[0], work[1], nbytes, crit[0], crit[1])
         # emptiness penalizer: per-ray partial sums of each level, the four batch sums of both in one launch
         sums = None
         consts = None
@@ -57,20 +55,17 @@ class _TrainLosses(torch.autograd.Function):
                 for raw, z, depth in ((raw_f, z_f, depth_f), (raw_c, z_c, depth_c)):
                     n, S, _ = raw.shape
                     part = torch.empty(n, 4, dtype=torch.float64, device=dev)
-                    _lib.check(lib.dmnerf_penalizer_fwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(depth), _lib.ptr(rays_d), n, S, C,
-                                                        consts[0], k2w, kh, _lib.ptr(part), _lib.stream()), "dmnerf_penalizer_fwd")
+                    _lib.launch("dmnerf_penalizer_fwd", raw, z, depth, rays_d, n, S, C, consts[0], k2w, kh, part)
                     parts.append(part)
             sums = torch.empty(2, 4, dtype=torch.float64, device=dev)
-            _lib.check(lib.dmnerf_penalizer_sums2(_lib.ptr(parts[0]), parts[0].shape[0], _lib.ptr(parts[1]), parts[1].shape[0],
-                                                  _lib.ptr(sums), _lib.stream()), "dmnerf_penalizer_sums2")
+            _lib.launch("dmnerf_penalizer_sums2", parts[0], parts[0].shape[0], parts[1], parts[1].shape[0], sums)
             if sharded:                                        # the sums are batch-global: ONE all-reduce for both levels
                 from . import distributed
                 distributed.allreduce_sums(sums)
         terms = torch.empty(8, **f32)
         inv = torch.empty(4, **f32)
-        _lib.check(lib.dmnerf_loss_tail_fwd(_lib.ptr(rgb_f), _lib.ptr(rgb_c), _lib.ptr(target), N, _lib.ptr(crit[0]), _lib.ptr(crit[1]),
-                                            _lib.ptr(None if sums is None else sums[0]), _lib.ptr(None if sums is None else sums[1]),
-                                            C, _lib.ptr(terms), _lib.ptr(inv), _lib.stream()), "dmnerf_loss_tail_fwd")
+        _lib.launch("dmnerf_loss_tail_fwd", rgb_f, rgb_c, target, N, crit[0], crit[1], None if sums is None else sums[0],
+                    None if sums is None else sums[1], C, terms, inv)
         keep_raw = penalize and part_f is None                  # (the per-ray backward kernels of this node need raw; the fused form does not)
         ctx.save_for_backward(rgb_f, rgb_c, ins_f, ins_c, raw_f if keep_raw else None, raw_c if keep_raw else None, z_f, z_c, depth_f, depth_c,
                               rays_d, target, labels, work, inv)
@@ -84,7 +79,6 @@ class _TrainLosses(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_total, _g_terms=None, _g_work=None):
-        lib = _lib.load()
         rgb_f, rgb_c, ins_f, ins_c, raw_f, raw_c, z_f, z_c, depth_f, depth_c, rays_d, target, labels, work, inv = ctx.saved_tensors
         ins_num, penalize, tol, deta_w, sharded = ctx.cfg
         C = ins_num + 1
@@ -97,12 +91,10 @@ class _TrainLosses(torch.autograd.Function):
         gout = torch.empty(8, dtype=torch.float32, device=dev)
         scales = torch.empty(4, dtype=torch.float32, device=dev)
         g_part = torch.empty(2, 4, dtype=torch.float64, device=dev) if ctx.from_parts is not None else None
-        _lib.check(lib.dmnerf_loss_tail_bwd(_lib.ptr(rgb_f), _lib.ptr(rgb_c), _lib.ptr(target), N, _lib.ptr(g), _lib.ptr(inv), _lib.ptr(d_rgb_f),
-                                            _lib.ptr(d_rgb_c), _lib.ptr(gout), _lib.ptr(scales), _lib.ptr(g_part), _lib.stream()), "dmnerf_loss_tail_bwd")
+        _lib.launch("dmnerf_loss_tail_bwd", rgb_f, rgb_c, target, N, g, inv, d_rgb_f, d_rgb_c, gout, scales, g_part)
         d_ins_f, d_ins_c = torch.empty_like(ins_f), torch.empty_like(ins_c)
-        _lib.check(lib.dmnerf_ins_criterion_bwd2(_lib.ptr(ins_f), _lib.ptr(ins_c), _lib.ptr(labels), ins_f.shape[0], ins_num, _lib.ptr(work[0]),
-                                                 _lib.ptr(work[1]), _lib.ptr(gout[:4]), _lib.ptr(gout[4:]), _lib.ptr(d_ins_f), _lib.ptr(d_ins_c),
-                                                 _lib.stream()), "dmnerf_ins_criterion_bwd2")
+        _lib.launch("dmnerf_ins_criterion_bwd2", ins_f, ins_c, labels, ins_f.shape[0], ins_num, work[0], work[1], gout[:4], gout[4:], d_ins_f,
+                    d_ins_c)
         d_raw_f = d_raw_c = d_part_f = d_part_c = None
         if penalize and ctx.from_parts is not None:
             # d raw is formed inside the compositing node's backward kernel from the gradient of its partial sums
@@ -113,8 +105,7 @@ class _TrainLosses(torch.autograd.Function):
             for lvl, (raw, z, depth) in enumerate(((raw_f, z_f, depth_f), (raw_c, z_c, depth_c))):
                 n, S, _ = raw.shape
                 d_raw = torch.empty_like(raw)
-                _lib.check(lib.dmnerf_penalizer_bwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(depth), _lib.ptr(rays_d), n, S, C, tolf, k2w, kh,
-                                                    _lib.ptr(scales[2 * lvl:2 * lvl + 2]), _lib.ptr(d_raw), _lib.stream()), "dmnerf_penalizer_bwd")
+                _lib.launch("dmnerf_penalizer_bwd", raw, z, depth, rays_d, n, S, C, tolf, k2w, kh, scales[2 * lvl:2 * lvl + 2], d_raw)
                 grads.append(d_raw)
             d_raw_f, d_raw_c = grads
         return (d_rgb_f, d_rgb_c, d_ins_f, d_ins_c, d_raw_f, d_raw_c, d_part_f, d_part_c) + (None,) * 8

@@ -32,7 +32,7 @@ class Embedder:
             raise ValueError("Embedder.embed expects [..., 3]")
         M = x.numel() // 3
         out = torch.empty(*x.shape[:-1], self.out_dim, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().dmnerf_embed(_lib.ptr(x), M, self.num_freqs, _lib.ptr(out), _lib.stream()), "dmnerf_embed")
+        _lib.launch("dmnerf_embed", x, M, self.num_freqs, out)
         return out
 
 
@@ -180,8 +180,7 @@ class DM_NeRF(nn.Module):
         if getattr(self, "_blob_hd", None) is None or self._blob_hd_src is not src:
             lib = _lib.load()
             out = torch.empty(int(lib.dmnerf_blob_f16_density_words(self.ins_num)), dtype=torch.float32, device=src.device)
-            _lib.check(lib.dmnerf_blob_f16_density_from_f16(_lib.ptr(src), self.ins_num, _lib.ptr(out), _lib.stream()),
-                       "dmnerf_blob_f16_density_from_f16")
+            _lib.launch("dmnerf_blob_f16_density_from_f16", src, self.ins_num, out)
             self._blob_hd, self._blob_hd_src = out, src
         return self._blob_hd
 
@@ -232,6 +231,5 @@ class DM_NeRF(nn.Module):
             raise ValueError(f"DM_NeRF.forward expects {self.input_ch_pts + self.input_ch_views} input channels")
         M = x2.shape[0]
         out = torch.empty(M, 4 + self.ins_num + 1, dtype=torch.float32, device=x2.device)
-        _lib.check(_lib.load().dmnerf_mlp_fwd_embedded(_lib.ptr(self.blob()), self.ins_num, _lib.ptr(x2), M,
-                                                       _lib.ptr(out), _lib.stream()), "dmnerf_mlp_fwd_embedded")
+        _lib.launch("dmnerf_mlp_fwd_embedded", self.blob(), self.ins_num, x2, M, out)
         return out.reshape(*x.shape[:-1], out.shape[-1])

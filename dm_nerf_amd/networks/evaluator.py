@@ -28,8 +28,7 @@ class _InsCriterion(torch.autograd.Function):
             raise ValueError(f"ins_criterion: unsupported N={N} ins_num={ins_num} (ins_num <= 128)")
         work = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
         out = torch.empty(4, dtype=torch.float32, device=pred.device)
-        _lib.check(lib.dmnerf_ins_criterion_fwd(_lib.ptr(pred), _lib.ptr(labels), N, ins_num, _lib.ptr(work), nbytes, _lib.ptr(out),
-                                                _lib.stream()), "dmnerf_ins_criterion_fwd")
+        _lib.launch("dmnerf_ins_criterion_fwd", pred, labels, N, ins_num, work, nbytes, out)
         ctx.save_for_backward(pred, labels, work)
         ctx.ins_num = ins_num
         ctx.mark_non_differentiable(work)
@@ -43,8 +42,7 @@ class _InsCriterion(torch.autograd.Function):
         pred, labels, work = ctx.saved_tensors
         grad = torch.empty_like(pred)
         g = _lib.f32(g_out)
-        _lib.check(_lib.load().dmnerf_ins_criterion_bwd(_lib.ptr(pred), _lib.ptr(labels), pred.shape[0], ctx.ins_num, _lib.ptr(work),
-                                                        _lib.ptr(g), _lib.ptr(grad), _lib.stream()), "dmnerf_ins_criterion_bwd")
+        _lib.launch("dmnerf_ins_criterion_bwd", pred, labels, pred.shape[0], ctx.ins_num, work, g, grad)
         return grad, None, None
 
 
@@ -93,8 +91,7 @@ def ins_label_conf(pred_ins):
     flat = x.reshape(-1, C)
     label = torch.empty(flat.shape[0], dtype=torch.int64, device=x.device)
     conf = torch.empty(flat.shape[0], dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().dmnerf_ins_label_conf(_lib.ptr(flat), flat.shape[0], C, _lib.ptr(label), _lib.ptr(conf), _lib.stream()),
-               "dmnerf_ins_label_conf")
+    _lib.launch("dmnerf_ins_label_conf", flat, flat.shape[0], C, label, conf)
     return label.reshape(x.shape[:-1]), conf.reshape(x.shape[:-1])
 
 
@@ -137,9 +134,8 @@ def _ins_eval_run(N, ins_num, gt_num, masked, device, prep_args):
     ap = torch.empty(6, dtype=torch.float32, device=device)
     matched = torch.empty(ins_num, dtype=torch.int64, device=device)
     args = prep_args(label)
-    _lib.check(lib.dmnerf_ins_eval_prep(*args, gt_num, N, ins_num, _lib.ptr(work), nbytes, _lib.stream()), "dmnerf_ins_eval_prep")
-    _lib.check(lib.dmnerf_ins_eval(N, ins_num, gt_num, 1 if masked else 0, _lib.ptr(work), nbytes, _lib.ptr(ap), _lib.ptr(matched),
-                                   _lib.stream()), "dmnerf_ins_eval")
+    _lib.launch("dmnerf_ins_eval_prep", *args, gt_num, N, ins_num, work, nbytes)
+    _lib.launch("dmnerf_ins_eval", N, ins_num, gt_num, 1 if masked else 0, work, nbytes, ap, matched)
     return label, ap, matched, work
 
 
@@ -166,7 +162,7 @@ def ins_eval_device(pred_label, pred_conf, gt_label, gt_rows, ins_num, mask=None
         raise ValueError("ins_eval_device: pred_label, pred_conf, gt_label (and mask) must have one entry per pixel")
     label, ap, matched, _ = _ins_eval_run(
         N, ins_num, rows.shape[0], m is not None, lab.device,
-        lambda out: (None, 0, _lib.ptr(lab), _lib.ptr(conf), _lib.ptr(out), _lib.ptr(m), None, 0, _lib.ptr(gl), _lib.ptr(rows)))
+        lambda out: (None, 0, lab, conf, out, m, None, 0, gl, rows))
     return label.reshape(shape), ap, matched
 
 
@@ -196,7 +192,7 @@ def ins_eval(pred_ins, gt_ins, gt_ins_num, ins_num, mask=None, check=None):
         raise ValueError("ins_eval: one mask entry per pixel")
     label, ap, matched, work = _ins_eval_run(
         N, ins_num, gt_num, m is not None, p.device,
-        lambda out: (_lib.ptr(p), ps, None, None, _lib.ptr(out), _lib.ptr(m), _lib.ptr(g), gs, None, None))
+        lambda out: (p, ps, None, None, out, m, g, gs, None, None))
     off = _lib.load().dmnerf_ins_eval_flags_offset(N, ins_num)
     host = torch.cat([ap.double(), matched[:gt_num].double(), work[off:off + 4].view(torch.int32).double()]).cpu()   # the one sync
     flags = int(host[-1])
@@ -227,8 +223,7 @@ def _img_metrics_run(pred, gt, with_channels=False):
     work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
     out = torch.empty(3, P, dtype=torch.float64, device=dev)
     ch = torch.empty(P, C, dtype=torch.float64, device=dev) if with_channels else None
-    _lib.check(lib.dmnerf_img_metrics(_lib.ptr(pred), _lib.ptr(gt), P, H, W, C, _lib.ptr(work), nbytes, _lib.ptr(out[0]), _lib.ptr(ch),
-                                      _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream()), "dmnerf_img_metrics")
+    _lib.launch("dmnerf_img_metrics", pred, gt, P, H, W, C, work, nbytes, out[0], ch, out[1], out[2])
     return out[0], out[2], out[1], ch
 
 
@@ -322,8 +317,7 @@ def conv3x3_pack(weight):
     ldb = (9 * cin + 31) // 32 * 32
     w = weight.detach().contiguous()
     out = torch.empty(cout, ldb, dtype=torch.float32, device=w.device)
-    lib = _lib.load()
-    _lib.check(lib.dmnerf_conv3x3_pack(_lib.ptr(w), cout, cin, _lib.ptr(out), ldb, _lib.stream()), "dmnerf_conv3x3_pack")
+    _lib.launch("dmnerf_conv3x3_pack", w, cout, cin, out, ldb)
     return out
 
 
@@ -346,9 +340,7 @@ def conv3x3(x_pf, packed, bias, n, h, w, relu=True, out=None):
     cin, cout = int(x_pf.shape[1]), int(packed.shape[0])
     if out is None:
         out = torch.empty(_pf_rows(n, h, w), cout, dtype=torch.float32, device=x_pf.device)
-    lib = _lib.load()
-    _lib.check(lib.dmnerf_conv3x3(_lib.ptr(x_pf), x_pf.numel(), _lib.ptr(packed), packed.numel(), _lib.ptr(bias), _lib.ptr(out), out.numel(),
-                                  n, h, w, cin, cout, 9, 1 if relu else 0, _lib.stream()), "dmnerf_conv3x3")
+    _lib.launch("dmnerf_conv3x3", x_pf, x_pf.numel(), packed, packed.numel(), bias, out, out.numel(), n, h, w, cin, cout, 9, 1 if relu else 0)
     return out
 
 
@@ -356,8 +348,7 @@ def maxpool2(x_pf, n, h, w):
     """``dmnerf_maxpool2``: padded-flat ``n`` images ``h x w`` -> padded-flat ``h // 2 x w // 2``."""
     c = int(x_pf.shape[1])
     out = torch.empty(_pf_rows(n, h // 2, w // 2), c, dtype=torch.float32, device=x_pf.device)
-    lib = _lib.load()
-    _lib.check(lib.dmnerf_maxpool2(_lib.ptr(x_pf), x_pf.numel(), _lib.ptr(out), out.numel(), n, h, w, c, _lib.stream()), "dmnerf_maxpool2")
+    _lib.launch("dmnerf_maxpool2", x_pf, x_pf.numel(), out, out.numel(), n, h, w, c)
     return out
 
 
@@ -443,32 +434,28 @@ class LPIPSVGG:
         out = torch.empty(P, dtype=torch.float64, device=self.device)
         if P == 0:
             return out
-        lib = _lib.load()
         ws = self._workspace(P, H, W)
         pred, gt = pred.contiguous(), gt.contiguous()       # (the crop of render_path is a view)
-        st = _lib.stream()
         N = 2 * P
-        _lib.check(lib.dmnerf_lpips_prologue(_lib.ptr(pred), _lib.ptr(gt), P, H, W, 1 if normalize else 0, _lib.ptr(ws["taps"]),
-                                             ws["taps"].numel(), st), "dmnerf_lpips_prologue")
+        _lib.launch("dmnerf_lpips_prologue", pred, gt, P, H, W, 1 if normalize else 0, ws["taps"], ws["taps"].numel())
         src, dst = ws["taps"], ws["a"]
         other = ws["b"]
         h, w, level = H, W, 0
         for i, (idx, sl, cin, cout) in enumerate(LPIPS_VGG_CONVS):
             if i > 0 and sl != LPIPS_VGG_CONVS[i - 1][1]:     # the pool in front of slices 2 .. 5
-                _lib.check(lib.dmnerf_maxpool2(_lib.ptr(src), src.numel(), _lib.ptr(dst), dst.numel(), N, h, w, cin, st), "dmnerf_maxpool2")
+                _lib.launch("dmnerf_maxpool2", src, src.numel(), dst, dst.numel(), N, h, w, cin)
                 h, w = h // 2, w // 2
                 src, dst = dst, src
             first = i == 0
-            _lib.check(lib.dmnerf_conv3x3(_lib.ptr(src), src.numel(), _lib.ptr(self.packed[i]), self.packed[i].numel(), _lib.ptr(self.bias[i]),
-                                          _lib.ptr(dst), dst.numel(), N, h, w, 32 if first else cin, cout, 1 if first else 9, 1, st),
-                       "dmnerf_conv3x3")
+            _lib.launch("dmnerf_conv3x3", src, src.numel(), self.packed[i], self.packed[i].numel(), self.bias[i], dst, dst.numel(), N, h, w,
+                        32 if first else cin, cout, 1 if first else 9, 1)
             if first:
                 src, dst = dst, other
             else:
                 src, dst = dst, src
             if i + 1 == len(LPIPS_VGG_CONVS) or LPIPS_VGG_CONVS[i + 1][1] != sl:      # the slice's last ReLU: a tap
-                _lib.check(lib.dmnerf_lpips_tail(_lib.ptr(src), src.numel(), _lib.ptr(self.lin[level]), P, h, w, cout, 1 if level == 0 else 0,
-                                                 _lib.ptr(ws["part"]), ws["part"].numel(), _lib.ptr(out), st), "dmnerf_lpips_tail")
+                _lib.launch("dmnerf_lpips_tail", src, src.numel(), self.lin[level], P, h, w, cout, 1 if level == 0 else 0, ws["part"],
+                            ws["part"].numel(), out)
                 if features is not None:
                     features.append(padded_flat_images(src[:_pf_rows(N, h, w) * cout].view(-1, cout), N, h, w)[:, 1:-1, 1:-1].clone())
                 level += 1

@@ -1,5 +1,4 @@
 """Drop-in for the hot-path functions of the reference's ``networks/helpers.py``."""
-import ctypes
 
 import numpy as np
 import torch
@@ -40,8 +39,7 @@ def get_rays_k(H, W, K, c2w, row0=0, nrows=None):
     rays_d = torch.empty(nrows, W, 3, dtype=torch.float32, device=dev)
     if nrows == 0:                                   # an empty band (more ranks than rows): nothing to generate
         return rays_o, rays_d
-    _lib.check(_lib.load().dmnerf_raygen(H, W, intr.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p),
-                                         int(row0), nrows, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.stream()), "dmnerf_raygen")
+    _lib.launch("dmnerf_raygen", H, W, intr, c, int(row0), nrows, rays_o, rays_d)
     return rays_o, rays_d
 
 
@@ -65,9 +63,7 @@ def get_select_full(rgb, pose, K, ins_target, N_train):
     idx = torch.from_numpy(selected_index).to(rgb.device)
     intr, c = _camera(K, pose)
     rays = torch.empty(2, N_train, 3, dtype=torch.float32, device=rgb.device)
-    _lib.check(_lib.load().dmnerf_raygen_select(int(H), int(W), intr.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p),
-                                                _lib.ptr(idx), int(N_train), _lib.ptr(rays[0]), _lib.ptr(rays[1]), _lib.stream()),
-               "dmnerf_raygen_select")
+    _lib.launch("dmnerf_raygen_select", int(H), int(W), intr, c, idx, int(N_train), rays[0], rays[1])
     target_c = rgb.reshape(-1, rgb.shape[-1])[idx]
     target_i = ins_target.reshape(-1)[idx]
     return target_c, target_i, rays
@@ -97,9 +93,7 @@ def get_select_crop(rgb, pose, K, ins_target, ins_index, crop_mask, N_train):
     idx = torch.from_numpy(flat).to(rgb.device)
     intr, c = _camera(K, pose)
     rays = torch.empty(2, N_train, 3, dtype=torch.float32, device=rgb.device)
-    _lib.check(_lib.load().dmnerf_raygen_select(int(H), int(W), intr.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p),
-                                                _lib.ptr(idx), int(N_train), _lib.ptr(rays[0]), _lib.ptr(rays[1]), _lib.stream()),
-               "dmnerf_raygen_select")
+    _lib.launch("dmnerf_raygen_select", int(H), int(W), intr, c, idx, int(N_train), rays[0], rays[1])
     target_c = rgb.reshape(-1, rgb.shape[-1])[idx]
     target_i = ins_target.reshape(-1)[idx[N_rgb:]]
     return target_c, target_i, rays, N_ins
@@ -119,8 +113,7 @@ def z_val_sample(N_rays, near, far, N_samples, device=None):
     dev = _device(device)
     t = linspace01(N_samples, dev)
     z = torch.empty(int(N_rays), int(N_samples), dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().dmnerf_z_val_sample(_lib.ptr(t), float(near), float(far), int(N_rays), int(N_samples),
-                                               _lib.ptr(z), _lib.stream()), "dmnerf_z_val_sample")
+    _lib.launch("dmnerf_z_val_sample", t, float(near), float(far), int(N_rays), int(N_samples), z)
     return z
 
 
@@ -137,8 +130,7 @@ def sample_pdf(bins, weights, N_samples, det=False, u=None, return_aux=False):
     samples = torch.empty(N, N_samples, dtype=torch.float32, device=bins.device)
     cdf = torch.empty(N, nb, dtype=torch.float32, device=bins.device) if return_aux else None
     inds = torch.empty(N, N_samples, dtype=torch.int64, device=bins.device) if return_aux else None
-    _lib.check(_lib.load().dmnerf_sample_pdf(_lib.ptr(bins), _lib.ptr(weights), _lib.ptr(u), stride, N, nb, int(N_samples),
-                                             _lib.ptr(samples), _lib.ptr(cdf), _lib.ptr(inds), _lib.stream()), "dmnerf_sample_pdf")
+    _lib.launch("dmnerf_sample_pdf", bins, weights, u, stride, N, nb, int(N_samples), samples, cdf, inds)
     if return_aux:
         return samples, cdf, inds
     return samples
@@ -155,8 +147,7 @@ def sample_from_cdf(bins, cdf, u):
         raise ValueError("sample_from_cdf: cdf and bins must both be [N, n_bins]")
     samples = torch.empty(N, ns, dtype=torch.float32, device=bins.device)
     inds = torch.empty(N, ns, dtype=torch.int64, device=bins.device)
-    _lib.check(_lib.load().dmnerf_sample_from_cdf(_lib.ptr(bins), _lib.ptr(cdf), _lib.ptr(u), stride, N, nb, ns,
-                                                  _lib.ptr(samples), _lib.ptr(inds), _lib.stream()), "dmnerf_sample_from_cdf")
+    _lib.launch("dmnerf_sample_from_cdf", bins, cdf, u, stride, N, nb, ns, samples, inds)
     return samples, inds
 
 
@@ -167,7 +158,7 @@ def stratify(z_vals, t_rand):
     if t.shape != z.shape:
         raise ValueError(f"stratify: t_rand must have z_vals' shape {tuple(z.shape)}, got {tuple(t.shape)}")
     out = torch.empty_like(z)
-    _lib.check(_lib.load().dmnerf_stratify(_lib.ptr(z), _lib.ptr(t), z.shape[0], z.shape[1], _lib.ptr(out), _lib.stream()), "dmnerf_stratify")
+    _lib.launch("dmnerf_stratify", z, t, z.shape[0], z.shape[1], out)
     return out
 
 
@@ -183,6 +174,5 @@ def importance_resample(z_coarse, weights_coarse, N_importance, det=True, u=None
         raise ValueError("importance_resample: weights must be [N, S] like z_coarse")
     z_fine = torch.empty(N, S + N_importance, dtype=torch.float32, device=z.device)
     zs = torch.empty(N, N_importance, dtype=torch.float32, device=z.device) if return_samples else None
-    _lib.check(_lib.load().dmnerf_importance_resample(_lib.ptr(z), _lib.ptr(w), _lib.ptr(u), stride, N, S, int(N_importance),
-                                                      _lib.ptr(z_fine), _lib.ptr(zs), _lib.stream()), "dmnerf_importance_resample")
+    _lib.launch("dmnerf_importance_resample", z, w, u, stride, N, S, int(N_importance), z_fine, zs)
     return (z_fine, zs) if return_samples else z_fine

@@ -16,7 +16,6 @@ from .render import run_network, run_network_skip
 
 def exchanger(ori_raw, tar_raws, ori_raw_pred, tar_raw_preds, move_labels):
     """``exchanger`` (networks/manipulator.py:18-83).  ``ori_raw`` is modified in place, as in the reference."""
-    lib = _lib.load()
     _lib.require_gpu(ori_raw, ori_raw_pred, *tar_raws, *tar_raw_preds)
     N, S, ch = ori_raw.shape
     C = ch - 4
@@ -29,8 +28,7 @@ def exchanger(ori_raw, tar_raws, ori_raw_pred, tar_raw_preds, move_labels):
     labels = (ctypes.c_int * T)(*[int(v) for v in move_labels])
     ori_label = torch.empty(N, S, dtype=torch.int64, device=ori_raw.device)
     tar_label = torch.empty(N, S, dtype=torch.int64, device=ori_raw.device)
-    _lib.check(lib.dmnerf_exchanger(_lib.ptr(ori_raw), raws, _lib.ptr(oa), accs, labels, T, N, S, C,
-                                    _lib.ptr(ori_label), _lib.ptr(tar_label), _lib.stream()), "dmnerf_exchanger")
+    _lib.launch("dmnerf_exchanger", ori_raw, raws, oa, accs, labels, T, N, S, C, ori_label, tar_label)
     return ori_raw, tar_raws, ori_label, tar_label
 
 
@@ -54,7 +52,6 @@ def edit_exchanger(ori_raw, tar_raws, ori_raw_pred, tar_raw_preds, move_labels, 
     the original is not; nothing is given up) or a ``REMOVE`` (the original's rows of the object times 0; ``tar_raws[e]`` and
     ``tar_raw_preds[e]`` are ``None``).  ``keep_labels``: afterwards every row whose OWN label is not in the set is zeroed.
     ``ori_raw`` is modified in place -> ``(ori_raw, ori_label [N,S] int64 or None)``."""
-    lib = _lib.load()
     E = len(move_labels)
     if len(kinds) != E or len(tar_raws) != E or len(tar_raw_preds) != E:
         raise ValueError(f"edit_exchanger: {E} labels, {len(kinds)} kinds, {len(tar_raws)} / {len(tar_raw_preds)} targets")
@@ -73,8 +70,7 @@ def edit_exchanger(ori_raw, tar_raws, ori_raw_pred, tar_raw_preds, move_labels, 
     kind = (ctypes.c_int * max(E, 1))(*[int(v) for v in kinds])
     keep = None if keep_labels is None else (ctypes.c_uint64 * 2)(*keep_words(keep_labels, C))
     ori_label = torch.empty(N, S, dtype=torch.int64, device=ori_raw.device) if want_label else None
-    _lib.check(lib.dmnerf_edit_exchange(_lib.ptr(ori_raw), raws, _lib.ptr(oa), accs, labels, kind, E, keep, N, S, C,
-                                        _lib.ptr(ori_label), _lib.stream()), "dmnerf_edit_exchange")
+    _lib.launch("dmnerf_edit_exchange", ori_raw, raws, oa, accs, labels, kind, E, keep, N, S, C, ori_label)
     return ori_raw, ori_label
 
 
@@ -86,8 +82,7 @@ def manipulator_render(raw, z_vals, rays_d):
     C = ch - 4
     f = dict(dtype=torch.float32, device=raw.device)
     rgb, w, depth, ins = torch.empty(N, 3, **f), torch.empty(N, S, **f), torch.empty(N, **f), torch.empty(N, C, **f)
-    _lib.check(_lib.load().dmnerf_manipulator_render(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(d), N, S, C, _lib.ptr(rgb), _lib.ptr(w),
-                                                     _lib.ptr(depth), _lib.ptr(ins), _lib.stream()), "dmnerf_manipulator_render")
+    _lib.launch("dmnerf_manipulator_render", raw, z, d, N, S, C, rgb, w, depth, ins)
     return rgb, w, depth, ins
 
 
@@ -96,8 +91,7 @@ def manipulator_z(N_rays, near, far, N_samples, device=None):
     dev = helpers._device(device)
     t = helpers.linspace01(N_samples, dev)
     z = torch.empty(int(N_rays), int(N_samples), dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().dmnerf_z_val_lerp(_lib.ptr(t), float(near), float(far), int(N_rays), int(N_samples), _lib.ptr(z),
-                                             _lib.stream()), "dmnerf_z_val_lerp")
+    _lib.launch("dmnerf_z_val_lerp", t, float(near), float(far), int(N_rays), int(N_samples), z)
     return z
 
 
@@ -144,7 +138,7 @@ def sort_rows(x):
     x = _lib.f32(x)
     _lib.require_gpu(x)
     out = torch.empty_like(x)
-    _lib.check(_lib.load().dmnerf_sort_rows(_lib.ptr(x), x.shape[0], x.shape[1], _lib.ptr(out), _lib.stream()), "dmnerf_sort_rows")
+    _lib.launch("dmnerf_sort_rows", x, x.shape[0], x.shape[1], out)
     return out
 
 

@@ -17,35 +17,31 @@ def _consts(deta_w):
 class _Penalizer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, z, depth, rays_d, tolerance, deta_w, sharded=False):
-        lib = _lib.load()
         N, S, ch = raw.shape
         C = ch - 4
         k2w, kh = _consts(deta_w)
         part = torch.empty(N, 4, dtype=torch.float64, device=raw.device)
-        _lib.check(lib.dmnerf_penalizer_fwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(depth), _lib.ptr(rays_d), N, S, C,
-                                            float(tolerance), k2w, kh, _lib.ptr(part), _lib.stream()), "dmnerf_penalizer_fwd")
+        _lib.launch("dmnerf_penalizer_fwd", raw, z, depth, rays_d, N, S, C, float(tolerance), k2w, kh, part)
         s = torch.empty(4, dtype=torch.float64, device=raw.device)    # the four batch sums; stay on the device
-        _lib.check(lib.dmnerf_penalizer_sums(_lib.ptr(part), N, _lib.ptr(s), _lib.stream()), "dmnerf_penalizer_sums")
+        _lib.launch("dmnerf_penalizer_sums", part, N, s)
         if sharded:                                                   # ray-sharded batch: the four sums are batch-global
             from .. import distributed
             distributed.allreduce_sums(s)
         loss = torch.empty(1, dtype=torch.float32, device=raw.device)  # the reference returns a 1-element tensor
         inv = torch.empty(2, dtype=torch.float32, device=raw.device)   # 1 / (C max(sum m_b, 1e-8)), 1 / max(sum m_m, 1e-8)
-        _lib.check(lib.dmnerf_penalizer_finish(_lib.ptr(s), C, _lib.ptr(loss), _lib.ptr(inv), _lib.stream()), "dmnerf_penalizer_finish")
+        _lib.launch("dmnerf_penalizer_finish", s, C, loss, inv)
         ctx.save_for_backward(raw, z, depth, rays_d, inv)
         ctx.consts = (float(tolerance), k2w, kh, C)
         return loss
 
     @staticmethod
     def backward(ctx, up):
-        lib = _lib.load()
         raw, z, depth, rays_d, inv = ctx.saved_tensors
         tol, k2w, kh, C = ctx.consts
         N, S, ch = raw.shape
         scales = (inv * up.reshape(()).to(torch.float32)).contiguous()
         d_raw = torch.empty_like(raw)
-        _lib.check(lib.dmnerf_penalizer_bwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(depth), _lib.ptr(rays_d), N, S, C, tol, k2w, kh,
-                                            _lib.ptr(scales), _lib.ptr(d_raw), _lib.stream()), "dmnerf_penalizer_bwd")
+        _lib.launch("dmnerf_penalizer_bwd", raw, z, depth, rays_d, N, S, C, tol, k2w, kh, scales, d_raw)
         return d_raw, None, None, None, None, None, None
 
 
@@ -56,16 +52,15 @@ class _PenalizerFromPartials(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, part, C, sharded):
-        lib = _lib.load()
         N = part.shape[0]
         s = torch.empty(4, dtype=torch.float64, device=part.device)
-        _lib.check(lib.dmnerf_penalizer_sums(_lib.ptr(part), N, _lib.ptr(s), _lib.stream()), "dmnerf_penalizer_sums")
+        _lib.launch("dmnerf_penalizer_sums", part, N, s)
         if sharded:
             from .. import distributed
             distributed.allreduce_sums(s)
         loss = torch.empty(1, dtype=torch.float32, device=part.device)
         inv = torch.empty(2, dtype=torch.float32, device=part.device)
-        _lib.check(lib.dmnerf_penalizer_finish(_lib.ptr(s), C, _lib.ptr(loss), _lib.ptr(inv), _lib.stream()), "dmnerf_penalizer_finish")
+        _lib.launch("dmnerf_penalizer_finish", s, C, loss, inv)
         ctx.save_for_backward(inv)
         ctx.N = N
         return loss

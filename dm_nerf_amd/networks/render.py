@@ -1,5 +1,4 @@
 """Drop-in for the reference's ``networks/render.py``: render_train, dm_nerf."""
-import ctypes
 from types import SimpleNamespace
 
 import torch
@@ -22,8 +21,7 @@ def render_train(raw, z_vals, rays_d):
     w = torch.empty(N, S, dtype=torch.float32, device=dev)
     depth = torch.empty(N, dtype=torch.float32, device=dev)
     ins = torch.empty(N, C - 1, dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().dmnerf_composite_fwd(_lib.ptr(raw), _lib.ptr(z), _lib.ptr(d), N, S, C, _lib.ptr(rgb), _lib.ptr(w),
-                                                _lib.ptr(depth), _lib.ptr(ins), _lib.stream()), "dmnerf_composite_fwd")
+    _lib.launch("dmnerf_composite_fwd", raw, z, d, N, S, C, rgb, w, depth, ins)
     return rgb, w, depth, ins
 
 
@@ -40,11 +38,9 @@ def run_network(model, rays_o, rays_d, z_vals, split=None):
     _lib.require_gpu(rays_o, rays_d, z)
     N, S = z.shape
     raw = torch.empty(N, S, 4 + model.ins_num + 1, dtype=torch.float32, device=z.device)
-    lib = _lib.load()
-    fn, blob, name = {None: (lib.dmnerf_mlp_fwd_rays, model.blob, "dmnerf_mlp_fwd_rays"),
-                      "bf16x3": (lib.dmnerf_mlp_fwd_rays_split, model.blob_split, "dmnerf_mlp_fwd_rays_split"),
-                      "f16x2": (lib.dmnerf_mlp_fwd_rays_f16, model.blob_f16, "dmnerf_mlp_fwd_rays_f16")}[split or None]
-    _lib.check(fn(_lib.ptr(blob()), model.ins_num, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z), N, S, _lib.ptr(raw), _lib.stream()), name)
+    blob, name = {None: (model.blob, "dmnerf_mlp_fwd_rays"), "bf16x3": (model.blob_split, "dmnerf_mlp_fwd_rays_split"),
+                  "f16x2": (model.blob_f16, "dmnerf_mlp_fwd_rays_f16")}[split or None]
+    _lib.launch(name, blob(), model.ins_num, rays_o, rays_d, z, N, S, raw)
     return raw
 
 
@@ -131,10 +127,7 @@ def skip_select(who, words, grid, rays_o, rays_d, z_vals, width, last, counts):
     sel, flag, work = select_buffers(N * S, dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     g = grid.c_struct()
-    _lib.check(_lib.load().dmnerf_skip_select_fill(ctypes.byref(g), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z), N, S, _lib.ptr(flag),
-                                                   _lib.ptr(sel), _lib.ptr(count), _lib.ptr(work), _lib.ptr(raw),
-                                                   _lib.ptr(fill_row(width, dev, last)), width, _lib.ptr(counts), _lib.stream()),
-               "dmnerf_skip_select_fill")
+    _lib.launch("dmnerf_skip_select_fill", g, rays_o, rays_d, z, N, S, flag, sel, count, work, raw, fill_row(width, dev, last), width, counts)
     return rays_o, rays_d, z, raw, sel, count
 
 
@@ -156,13 +149,10 @@ def run_network_skip(model, rays_o, rays_d, z_vals, grid, split=None, counts=Non
     if sel is None:
         return raw
     N, S = z.shape
-    lib, st = _lib.load(), _lib.stream()
     if split == "f16x2":
-        _lib.check(lib.dmnerf_mlp_fwd_rays_f16_sel(_lib.ptr(model.blob_f16()), model.ins_num, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z),
-                                                   N, S, _lib.ptr(sel), _lib.ptr(count), _lib.ptr(raw), st), "dmnerf_mlp_fwd_rays_f16_sel")
+        _lib.launch("dmnerf_mlp_fwd_rays_f16_sel", model.blob_f16(), model.ins_num, rays_o, rays_d, z, N, S, sel, count, raw)
     else:
-        _lib.check(lib.dmnerf_mlp_fwd_rays_sel(_lib.ptr(model.blob()), model.ins_num, 0, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z),
-                                               N, S, _lib.ptr(sel), _lib.ptr(count), _lib.ptr(raw), st), "dmnerf_mlp_fwd_rays_sel")
+        _lib.launch("dmnerf_mlp_fwd_rays_sel", model.blob(), model.ins_num, 0, rays_o, rays_d, z, N, S, sel, count, raw)
     return raw
 
 
@@ -315,7 +305,7 @@ def dm_nerf(rays, position_embedder, view_embedder, model_coarse, model_fine, z_
     a.d_z_coarse, a.d_raw_coarse = out['z_vals_coarse'].data_ptr(), out['raw_coarse'].data_ptr()
     a.d_rgb_coarse, a.d_depth_coarse = out['rgb_coarse'].data_ptr(), out['depth_coarse'].data_ptr()
     a.d_ins_coarse = out['ins_coarse'].data_ptr()
-    _lib.check(_lib.load().dmnerf_render_rays_fwd(ctypes.byref(a), _lib.stream()), "dmnerf_render_rays_fwd")
+    _lib.launch("dmnerf_render_rays_fwd", a)
     p.f16, p.z_c = split == "f16x2", out['z_vals_coarse']
     return _epilogue(p, out)
 
@@ -369,7 +359,7 @@ def _fine_prepare(who, modes, rays, position_embedder, view_embedder, model_coar
 
 def _fine(who, modes, rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args, t_rand, u, _events):
     p = _fine_prepare(who, modes, rays, position_embedder, view_embedder, model_coarse, model_fine, z_vals_coarse, args, t_rand, u, _events)
-    _lib.check(_lib.load().dmnerf_render_rays_fwd_fine(ctypes.byref(p.a), _lib.stream()), "dmnerf_render_rays_fwd_fine")
+    _lib.launch("dmnerf_render_rays_fwd_fine", p.a)
     return _epilogue(p, p.out)
 
 
@@ -431,7 +421,7 @@ def dm_nerf_fine_skip(rays, position_embedder, view_embedder, model_coarse, mode
     k.grid = grid.c_struct()
     k.d_sel, k.d_flag, k.d_select_ws, k.d_n_eval = sel.data_ptr(), flag.data_ptr(), work.data_ptr(), out['n_eval'].data_ptr()
     k.levels = sum(SKIP_LEVELS[l] for l in set(levels))
-    _lib.check(_lib.load().dmnerf_render_rays_fwd_fine_skip(ctypes.byref(k), _lib.stream()), "dmnerf_render_rays_fwd_fine_skip")
+    _lib.launch("dmnerf_render_rays_fwd_fine_skip", k)
     return _epilogue(p, out)
 
 
@@ -456,12 +446,10 @@ def dm_nerf_fine_mark(rays, position_embedder, view_embedder, model_coarse, mode
         raise RuntimeError("dm_nerf_fine_mark: the grid lives on another device than the rays")
     N, S = z_c.shape
     w_c = torch.empty(N, S, dtype=torch.float32, device=p.dev) if "coarse" in levels else None
-    lib = _lib.load()
-    _lib.check(lib.dmnerf_render_rays_fwd_fine(ctypes.byref(p.a), _lib.stream()), "dmnerf_render_rays_fwd_fine")
+    _lib.launch("dmnerf_render_rays_fwd_fine", p.a)
     if "fine" in levels:
         grid.mark(rays_o, rays_d, p.out['z_vals_fine'], p.ws, threshold)
     if w_c is not None and N:
-        _lib.check(lib.dmnerf_weights_from_sigma(_lib.ptr(p.sigma), _lib.ptr(z_c), _lib.ptr(rays_d), N, S, _lib.ptr(w_c), _lib.stream()),
-                   "dmnerf_weights_from_sigma")
+        _lib.launch("dmnerf_weights_from_sigma", p.sigma, z_c, rays_d, N, S, w_c)
         grid.mark(rays_o, rays_d, z_c, w_c, threshold)
     return _epilogue(p, p.out)

@@ -22,7 +22,6 @@ second moments within 8 ulp after 20 steps on identical gradients -- observed on
 operation; only the fused multiply-adds a compiler may or may not form inside ATen's kernels could differ).  The twin is torch's
 multi-tensor form: the second moment squares the gradient first, so a gradient beyond ~1.8e19 makes ``exp_avg_sq`` inf and
 freezes its element, where single-tensor Adam (``(value * g) * g``) would stay finite."""
-import ctypes
 
 import torch
 
@@ -145,7 +144,6 @@ class FlatAdam:
         return a.flat
 
     def step(self):
-        lib = _lib.load()
         autograd.join_side()                                         # a side-stream backward left in flight (join_on_exit=False) first
         g = self._grads()
         grp = self.param_groups[0]
@@ -156,15 +154,13 @@ class FlatAdam:
                 self.lr_t.copy_(lr)
             d_lr, lr = self.lr_t, 0.0
         b1, b2 = grp["betas"]
-        _lib.check(lib.dmnerf_adam_step(_lib.ptr(self.flat), _lib.ptr(g), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), self.flat.numel(),
-                                        float(lr), _lib.ptr(d_lr), float(b1), float(b2), float(grp["eps"]), _lib.ptr(self.state2), _lib.stream()),
-                   "dmnerf_adam_step")
+        _lib.launch("dmnerf_adam_step", self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat.numel(), float(lr), d_lr, float(b1), float(b2),
+                    float(grp["eps"]), self.state2)
         self.repack()
 
     def repack(self):
         """One launch: every model's flat copy, forward blob and W^T blob from the (updated) flat parameters; installed as the
         models' cached kernel-layout weights (NEW tensors each time: a backward pending across the step keeps what its forward used)."""
-        lib = _lib.load()
         n_models = len(self.models)
         arr = (_lib.RepackModel * n_models)()
         keep = []
@@ -179,7 +175,7 @@ class FlatAdam:
                                       self._idx[i][1].data_ptr(), blob_t.data_ptr(), None if self._f_pos[i] is None else self._f_pos[i].data_ptr())
             keep.append((m, flat_copy, blob, blob_t))
             o += size
-        _lib.check(lib.dmnerf_repack_train(arr, n_models, _lib.stream()), "dmnerf_repack_train")
+        _lib.launch("dmnerf_repack_train", arr, n_models)
         for m, flat_copy, blob, blob_t in keep:
             m.install_packed(flat_copy, blob, blob_t)
 

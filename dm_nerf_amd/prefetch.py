@@ -21,7 +21,6 @@ without touching global state (tests/test_prefetch.py pins this against batches 
 ``get_select_full`` / ``get_select_crop``).
 """
 import collections
-import ctypes
 import queue
 import threading
 
@@ -160,9 +159,7 @@ class TrainBatchPrefetcher:
         self.copied[slot] = ev
         rays = torch.empty(2, self.N, 3, dtype=torch.float32, device=self.device)
         c = self.poses[sel.img_i]
-        _lib.check(_lib.load().dmnerf_raygen_select(self.H, self.W, self.intr.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p),
-                                                    _lib.ptr(idx), self.N, _lib.ptr(rays[0]), _lib.ptr(rays[1]), _lib.stream()),
-                   "dmnerf_raygen_select")
+        _lib.launch("dmnerf_raygen_select", self.H, self.W, self.intr, c, idx, self.N, rays[0], rays[1])
         target_c = self.images[sel.img_i].reshape(-1, 3)[idx]
         lab = self.labels[sel.img_i].reshape(-1)
         target_i = lab[idx] if sel.n_ins is None else lab[idx[self.N - sel.n_ins:]]

@@ -1,5 +1,4 @@
 """Reference state_dict -> kernel weight blob (MFMA A-operand order)."""
-import ctypes
 
 import numpy as np
 import torch
@@ -22,7 +21,7 @@ def pack_index_host(ins_num):
     if n <= 0:
         raise ValueError(f"unsupported ins_num={ins_num}")
     idx = np.empty(n, dtype=np.int32)
-    _lib.check(lib.dmnerf_build_pack_index(ins_num, idx.ctypes.data_as(ctypes.c_void_p), n), "dmnerf_build_pack_index")
+    _lib.call("dmnerf_build_pack_index", ins_num, idx, n)
     return idx
 
 
@@ -33,7 +32,7 @@ def pack_index_t_host(ins_num):
     if n <= 0:
         raise ValueError(f"unsupported ins_num={ins_num}")
     idx = np.empty(n, dtype=np.int32)
-    _lib.check(lib.dmnerf_build_pack_index_t(ins_num, idx.ctypes.data_as(ctypes.c_void_p), n), "dmnerf_build_pack_index_t")
+    _lib.call("dmnerf_build_pack_index_t", ins_num, idx, n)
     return idx
 
 
@@ -44,7 +43,7 @@ def pack_index_fused_host(ins_num):
     if n <= 0:
         raise ValueError(f"unsupported ins_num={ins_num}")
     idx = np.empty(n, dtype=np.int32)
-    _lib.check(lib.dmnerf_build_pack_index_fused(ins_num, idx.ctypes.data_as(ctypes.c_void_p), n), "dmnerf_build_pack_index_fused")
+    _lib.call("dmnerf_build_pack_index_fused", ins_num, idx, n)
     return idx
 
 
@@ -61,7 +60,7 @@ def fused_flat(flat, ins_num):
     folded into the hidden layers that consume them -- formed on the device by ``dmnerf_fuse_heads`` (float64 accumulation,
     rounded once; csrc/heads.hip).  Inference only: the same function up to f32 re-association."""
     out = torch.empty_like(flat)
-    _lib.check(_lib.load().dmnerf_fuse_heads(_lib.ptr(flat), ins_num, _lib.ptr(out), _lib.stream()), "dmnerf_fuse_heads")
+    _lib.launch("dmnerf_fuse_heads", flat, ins_num, out)
     return out
 
 
@@ -84,13 +83,13 @@ def pack_blob_split(state, ins_num):
     if key not in _index_cache:
         n = (total - tab) * 2
         host = np.empty(n, dtype=np.int32)
-        _lib.check(lib.dmnerf_build_pack_index_split(ins_num, host.ctypes.data_as(ctypes.c_void_p), n), "dmnerf_build_pack_index_split")
+        _lib.call("dmnerf_build_pack_index_split", ins_num, host, n)
         _index_cache[key] = torch.from_numpy(host).to(flat.device)
     idx = _index_cache[key]
     blob = torch.empty(total, dtype=torch.float32, device=flat.device)
     idx_tab = pack_index(ins_num, flat.device, False, True)[:tab].contiguous()
-    _lib.check(lib.dmnerf_pack_weights(_lib.ptr(flat), _lib.ptr(idx_tab), _lib.ptr(blob), tab, _lib.stream()), "dmnerf_pack_weights")
-    _lib.check(lib.dmnerf_pack_split(_lib.ptr(flat), _lib.ptr(idx), _lib.ptr(blob[tab:]), total - tab, _lib.stream()), "dmnerf_pack_split")
+    _lib.launch("dmnerf_pack_weights", flat, idx_tab, blob, tab)
+    _lib.launch("dmnerf_pack_split", flat, idx, blob[tab:], total - tab)
     return blob
 
 
@@ -121,13 +120,12 @@ def pack_blob_f16(state, ins_num):
     if key not in _index_cache:
         n = (total - tab) * 2
         h_tab, h_str = np.empty(tab, dtype=np.int32), np.empty(n, dtype=np.int32)
-        _lib.check(lib.dmnerf_build_pack_index_f16(ins_num, h_tab.ctypes.data_as(ctypes.c_void_p), tab,
-                                                   h_str.ctypes.data_as(ctypes.c_void_p), n), "dmnerf_build_pack_index_f16")
+        _lib.call("dmnerf_build_pack_index_f16", ins_num, h_tab, tab, h_str, n)
         _index_cache[key] = (torch.from_numpy(h_tab).to(flat.device), torch.from_numpy(h_str).to(flat.device))
     idx_tab, idx = _index_cache[key]
     blob = torch.empty(total, dtype=torch.float32, device=flat.device)
-    _lib.check(lib.dmnerf_pack_weights(_lib.ptr(flat), _lib.ptr(idx_tab), _lib.ptr(blob), tab, _lib.stream()), "dmnerf_pack_weights")
-    _lib.check(lib.dmnerf_pack_f16(_lib.ptr(flat), _lib.ptr(idx), _lib.ptr(blob[tab:]), total - tab, _lib.stream()), "dmnerf_pack_f16")
+    _lib.launch("dmnerf_pack_weights", flat, idx_tab, blob, tab)
+    _lib.launch("dmnerf_pack_f16", flat, idx, blob[tab:], total - tab)
     return blob
 
 
@@ -144,18 +142,18 @@ def pack_blob_t_split(flat, ins_num):
         raise ValueError(f"unsupported ins_num={ins_num}")
     ext = torch.empty(flat.numel() + HEAD_F_FLOATS, dtype=torch.float32, device=flat.device)
     ext[:flat.numel()] = flat
-    _lib.check(lib.dmnerf_head_product(_lib.ptr(flat), ins_num, _lib.ptr(ext[flat.numel():]), _lib.stream()), "dmnerf_head_product")
+    _lib.launch("dmnerf_head_product", flat, ins_num, ext[flat.numel():])
     key = (ins_num, str(flat.device), "split_t")
     if key not in _index_cache:
         n = (total - TAB_T_FLOATS) * 2
         host = np.empty(n, dtype=np.int32)
-        _lib.check(lib.dmnerf_build_pack_index_t_split(ins_num, host.ctypes.data_as(ctypes.c_void_p), n), "dmnerf_build_pack_index_t_split")
+        _lib.call("dmnerf_build_pack_index_t_split", ins_num, host, n)
         _index_cache[key] = torch.from_numpy(host).to(flat.device)
     idx = _index_cache[key]
     blob = torch.empty(total, dtype=torch.float32, device=flat.device)
     idx_tab = pack_index(ins_num, flat.device, True)[:TAB_T_FLOATS].contiguous()
-    _lib.check(lib.dmnerf_pack_weights(_lib.ptr(ext), _lib.ptr(idx_tab), _lib.ptr(blob), TAB_T_FLOATS, _lib.stream()), "dmnerf_pack_weights")
-    _lib.check(lib.dmnerf_pack_split(_lib.ptr(ext), _lib.ptr(idx), _lib.ptr(blob[TAB_T_FLOATS:]), total - TAB_T_FLOATS, _lib.stream()), "dmnerf_pack_split")
+    _lib.launch("dmnerf_pack_weights", ext, idx_tab, blob, TAB_T_FLOATS)
+    _lib.launch("dmnerf_pack_split", ext, idx, blob[TAB_T_FLOATS:], total - TAB_T_FLOATS)
     return blob
 
 
@@ -168,18 +166,18 @@ def pack_blob_t_f16(flat, ins_num):
         raise ValueError(f"unsupported ins_num={ins_num}")
     ext = torch.empty(flat.numel() + HEAD_F_FLOATS, dtype=torch.float32, device=flat.device)
     ext[:flat.numel()] = flat
-    _lib.check(lib.dmnerf_head_product(_lib.ptr(flat), ins_num, _lib.ptr(ext[flat.numel():]), _lib.stream()), "dmnerf_head_product")
+    _lib.launch("dmnerf_head_product", flat, ins_num, ext[flat.numel():])
     key = (ins_num, str(flat.device), "f16_t")
     if key not in _index_cache:
         n = (total - TAB_T_FLOATS) * 2
         host = np.empty(n, dtype=np.int32)
-        _lib.check(lib.dmnerf_build_pack_index_t_f16(ins_num, host.ctypes.data_as(ctypes.c_void_p), n), "dmnerf_build_pack_index_t_f16")
+        _lib.call("dmnerf_build_pack_index_t_f16", ins_num, host, n)
         _index_cache[key] = torch.from_numpy(host).to(flat.device)
     idx = _index_cache[key]
     blob = torch.empty(total, dtype=torch.float32, device=flat.device)
     idx_tab = pack_index(ins_num, flat.device, True)[:TAB_T_FLOATS].contiguous()
-    _lib.check(lib.dmnerf_pack_weights(_lib.ptr(ext), _lib.ptr(idx_tab), _lib.ptr(blob), TAB_T_FLOATS, _lib.stream()), "dmnerf_pack_weights")
-    _lib.check(lib.dmnerf_pack_f16(_lib.ptr(ext), _lib.ptr(idx), _lib.ptr(blob[TAB_T_FLOATS:]), total - TAB_T_FLOATS, _lib.stream()), "dmnerf_pack_f16")
+    _lib.launch("dmnerf_pack_weights", ext, idx_tab, blob, TAB_T_FLOATS)
+    _lib.launch("dmnerf_pack_f16", ext, idx, blob[TAB_T_FLOATS:], total - TAB_T_FLOATS)
     return blob
 
 
@@ -200,11 +198,11 @@ def pack_blob(state, ins_num, out=None, transposed=False, fused=False, flat=None
         # formed on the device behind the flat parameters, gathered like any other weight
         ext = torch.empty(flat.numel() + HEAD_F_FLOATS, dtype=torch.float32, device=flat.device)
         ext[:flat.numel()] = flat
-        _lib.check(lib.dmnerf_head_product(_lib.ptr(flat), ins_num, _lib.ptr(ext[flat.numel():]), _lib.stream()), "dmnerf_head_product")
+        _lib.launch("dmnerf_head_product", flat, ins_num, ext[flat.numel():])
         flat = ext
     idx = pack_index(ins_num, flat.device, transposed, fused)
     n = idx.numel()
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=flat.device)
-    _lib.check(lib.dmnerf_pack_weights(_lib.ptr(flat), _lib.ptr(idx), _lib.ptr(out), n, _lib.stream()), "dmnerf_pack_weights")
+    _lib.launch("dmnerf_pack_weights", flat, idx, out, n)
     return out
