@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from .networks import helpers
+from .weights import VARIANTS
 
 W = 256
 HW = 128
@@ -94,7 +95,7 @@ def f16x2_probe(model, rays_o, rays_d, z):
     save = torch.empty(lib.dmnerf_train_save_floats(step * S), dtype=torch.float32, device=z.device)
     for s0 in range(0, N, step):
         n = min(step, N - s0)
-        _lib.launch("dmnerf_mlp_fwd_rays_train_f16", model.blob_f16(), model.ins_num, rays_o[s0:s0 + n], rays_d[s0:s0 + n], z[s0:s0 + n],
+        _lib.launch(VARIANTS["f16x2"].fwd_train, model.blob_f16(), model.ins_num, rays_o[s0:s0 + n], rays_d[s0:s0 + n], z[s0:s0 + n],
                     n, S, raw, save)
         _f16_range_scan(save, n * S, False)
 
@@ -158,12 +159,10 @@ def wgrad_plan(ins_num, M, device, max_wgs=None, split=False):
         # gradients summed in another order; tests/test_gpu_convergence.py uses it to measure how far two correct f32 trainings
         # drift apart)
         max_wgs = PLAN_MAX_WGS or torch.cuda.get_device_properties(device).multi_processor_count     # one workgroup per CU
-    kind = "f16x2" if split == "f16x2" else ("bf16x3" if split else None)
-    key = (ins_num, M, str(device), max_wgs, kind)
+    variant = "f16x2" if split == "f16x2" else ("bf16x3" if split else None)
+    key = (ins_num, M, str(device), max_wgs, variant)
     if key not in _plan_cache:
-        f_sizes, f_plan = {None: ("dmnerf_wgrad_plan_sizes", "dmnerf_wgrad_plan"),
-                           "bf16x3": ("dmnerf_wgrad_plan_sizes_split", "dmnerf_wgrad_plan_split"),
-                           "f16x2": ("dmnerf_wgrad_plan_sizes_f16", "dmnerf_wgrad_plan_f16")}[kind]
+        f_sizes, f_plan = VARIANTS[variant].plan
         jb, ob, pf = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         nj, no = ctypes.c_int(), ctypes.c_int()
         _lib.call(f_sizes, ins_num, M, max_wgs, ctypes.byref(jb), ctypes.byref(ob), ctypes.byref(pf), ctypes.byref(nj), ctypes.byref(no))
@@ -277,41 +276,28 @@ def grad_arena(models):
 
 class MLPRaysFunction(torch.autograd.Function):
     """raw[N,S,4+C] = DM_NeRF(embed(o + d z) | embed(d/|d|)); parameters are inputs 5.. in state_dict order.
-    ``mode``: None (default f32 kernels) | "fused" | "split" | "f16" (the opt-in variants of run_network_train); ``check_f16``: the
-    caller's ``args.check_f16`` for the range scans of this forward and its backward (None: the module flag / DMNERF_CHECK_F16)."""
+    ``variant``: a key of ``weights.VARIANTS`` (None: the default f32 kernels | "fused" | "bf16x3" | "f16x2", the opt-in variants of
+    run_network_train); ``check_f16``: the caller's ``args.check_f16`` for the range scans of this forward and its backward (None:
+    the module flag / DMNERF_CHECK_F16)."""
 
     @staticmethod
-    def forward(ctx, model, mode, check_f16, rays_o, rays_d, z, *params):
+    def forward(ctx, model, variant, check_f16, rays_o, rays_d, z, *params):
         lib = _lib.load()
         N, S = z.shape
         M = N * S
         ins_num = model.ins_num
+        v = VARIANTS[variant]
         raw = torch.empty(N, S, 4 + ins_num + 1, dtype=torch.float32, device=z.device)
         save = torch.empty(lib.dmnerf_train_save_floats(M), dtype=torch.float32, device=z.device)
-        blob = None if mode in ("split", "f16") else model.blob()  # (the f32 dgrad reads it; the split kernels have their own blobs)
-        if mode == "split":
-            fwd_blob, fn = model.blob_split(), "dmnerf_mlp_fwd_rays_train_split"
-        elif mode == "f16":
-            fwd_blob, fn = model.blob_f16(), "dmnerf_mlp_fwd_rays_train_f16"
-        elif mode == "fused":
-            fwd_blob, fn = model.blob_fused(), "dmnerf_mlp_fwd_rays_train_fused"
-        else:
-            fwd_blob, fn = blob, "dmnerf_mlp_fwd_rays_train"
+        blob = model.blob() if variant in (None, "fused") else None     # (the f32 dgrad reads it; the split dgrads read their W^T blob alone)
+        fwd_blob = blob if v.blob == "blob" else getattr(model, v.blob)()
         with _timed("mlp_fwd_train", M):
-            _lib.launch(fn, fwd_blob, ins_num, rays_o, rays_d, z, N, S, raw, save)
-        ctx.check_f16 = mode == "f16" and (check_f16 if check_f16 is not None else f16_check_enabled())
+            _lib.launch(v.fwd_train, fwd_blob, ins_num, rays_o, rays_d, z, N, S, raw, save)
+        ctx.check_f16 = variant == "f16x2" and (check_f16 if check_f16 is not None else f16_check_enabled())
         if ctx.check_f16:
             _f16_range_scan(save, M, False)
-        ctx.model, ctx.M, ctx.save = model, M, save
-        ctx.blob, ctx.flat = blob, model.flat()                                   # the weights this forward used
-        ctx.blob_t = ctx.blob_ts = None
-        if mode == "split":
-            ctx.blob_ts = model.blob_t_split()
-        elif mode == "f16":
-            ctx.blob_ts = model.blob_t_f16()
-        else:
-            ctx.blob_t = model.blob_t()
-        ctx.mode = mode
+        ctx.model, ctx.M, ctx.save, ctx.variant = model, M, save, variant
+        ctx.blob, ctx.flat, ctx.blob_t = blob, model.flat(), getattr(model, v.blob_t)()     # the weights this forward used
         return raw
 
     @staticmethod
@@ -408,7 +394,7 @@ def _mlp_backward(ctx, g_raw):
         main = torch.cuda.current_stream(dev)
         # everything the side-stream kernels READ that was allocated on the main stream stays referenced until the join: freed
         # earlier, the main stream's allocator could hand the block to a kernel that runs while they are still reading
-        keep = [g_raw, ctx.save, ctx.flat, ctx.blob, ctx.blob_t, ctx.blob_ts]
+        keep = [g_raw, ctx.save, ctx.flat, ctx.blob, ctx.blob_t]
         side.wait_stream(main)
         with torch.cuda.stream(side):
             grads = _mlp_backward_on_stream(ctx, g_raw)
@@ -437,20 +423,20 @@ def _mlp_backward_on_stream(ctx, g_raw):
     dsave = torch.empty_like(ctx.save)
     Mp = _row_len(M)
     gt = torch.empty(Mp // 32, 4 + C, 32, dtype=torch.float32, device=g.device)   # d raw, block-major, written by the kernel
-    split = ctx.blob_ts is not None                              # opt-in: split-bf16 backward kernels (args.mfma_split)
-    f16 = ctx.mode == "f16"
+    v = VARIANTS[ctx.variant]
+    f16 = ctx.variant == "f16x2"
     scale = _grad_scale_buffer(g.device) if f16 else None         # {2^s, 2^-s}: the f16 backward runs on 2^s dL/draw (f16 range)
     with _timed("mlp_bwd_data", M):
         if f16:
             _lib.launch("dmnerf_grad_scale", g, g.numel(), scale)
-            _lib.launch("dmnerf_mlp_bwd_data_f16", ctx.blob_ts, ins_num, ctx.save, g, M, dsave, gt, scale)
+            _lib.launch(v.dgrad, ctx.blob_t, ins_num, ctx.save, g, M, dsave, gt, scale)
             if ctx.check_f16:
                 _f16_range_scan(dsave, M, True)
-        elif split:
-            _lib.launch("dmnerf_mlp_bwd_data_split", ctx.blob_ts, ins_num, ctx.save, g, M, dsave, gt)
-        else:
-            _lib.launch("dmnerf_mlp_bwd_data", ctx.blob, ctx.blob_t, ins_num, ctx.save, g, M, dsave, gt)
-    jobs, n_jobs, outs, n_outs, part_floats = wgrad_plan(ins_num, M, g.device, split="f16x2" if f16 else split)
+        elif ctx.variant == "bf16x3":
+            _lib.launch(v.dgrad, ctx.blob_t, ins_num, ctx.save, g, M, dsave, gt)
+        else:                                                     # the f32 dgrad (None, "fused") reads W and W^T
+            _lib.launch(v.dgrad, ctx.blob, ctx.blob_t, ins_num, ctx.save, g, M, dsave, gt)
+    jobs, n_jobs, outs, n_outs, part_floats = wgrad_plan(ins_num, M, g.device, split=False if ctx.variant == "fused" else ctx.variant)
     part = torch.empty(part_floats, dtype=torch.float32, device=g.device)
     flat = None
     arena = arena_slot(model)                                    # data-parallel step: write into the shared all-reduce buffer
@@ -460,10 +446,9 @@ def _mlp_backward_on_stream(ctx, g_raw):
         flat = torch.empty(lib.dmnerf_param_count(ins_num), dtype=torch.float32, device=g.device)
     with _timed("mlp_bwd_weights", M):
         if f16:
-            _lib.launch("dmnerf_mlp_bwd_weights_f16", ctx.save, dsave, gt, M, jobs, n_jobs, outs, n_outs, ctx.flat, ins_num, part, flat, scale)
+            _lib.launch(v.wgrad, ctx.save, dsave, gt, M, jobs, n_jobs, outs, n_outs, ctx.flat, ins_num, part, flat, scale)
         else:
-            f_wgrad = "dmnerf_mlp_bwd_weights_split" if split else "dmnerf_mlp_bwd_weights"
-            _lib.launch(f_wgrad, ctx.save, dsave, gt, M, jobs, n_jobs, outs, n_outs, ctx.flat, ins_num, part, flat)
+            _lib.launch(v.wgrad, ctx.save, dsave, gt, M, jobs, n_jobs, outs, n_outs, ctx.flat, ins_num, part, flat)
     ctx.save = None
     return tuple(split_flat_grads(model, flat))
 
@@ -482,7 +467,7 @@ class MLPEmbeddedFunction(torch.autograd.Function):
         _lib.launch("dmnerf_mlp_fwd_embedded_train", model.blob(), ins_num, x, M, raw, save)
         ctx.model, ctx.M, ctx.save = model, M, save
         ctx.blob, ctx.blob_t, ctx.flat = model.blob(), model.blob_t(), model.flat()
-        ctx.mode, ctx.blob_ts, ctx.check_f16 = None, None, False      # what MLPRaysFunction sets: _mlp_backward reads all three
+        ctx.variant, ctx.check_f16 = None, False                      # what MLPRaysFunction sets: _mlp_backward reads both
         return raw
 
     @staticmethod
@@ -605,11 +590,11 @@ def run_network_train(model, rays_o, rays_d, z, fused=False, split=None, check_f
     weight gradients on the split-operand 16-bit MFMA kernels (fused heads + six bf16 / three f16 products per f32 product:
     f32-class values).  ``check_f16`` (``f16_check_enabled(args)``): scan what the f16x2 forward AND the
     backward of these launches convert for saturation (None: the module flag / DMNERF_CHECK_F16)."""
-    mode = {"bf16x3": "split", "f16x2": "f16", True: "split"}[split] if split else ("fused" if fused else None)
-    return _run_network_train(model, rays_o, rays_d, z, mode, check_f16)
+    variant = ("bf16x3" if split is True else split) if split else ("fused" if fused else None)
+    return _run_network_train(model, rays_o, rays_d, z, variant, check_f16)
 
 
-def _run_network_train(model, rays_o, rays_d, z, mode, check_f16=None):
+def _run_network_train(model, rays_o, rays_d, z, variant, check_f16=None):
     check_f16 = None if check_f16 is None else bool(check_f16)
     if not model._fused_ok():                              # another network shape: layer by layer, its own autograd Function
         from . import generic
@@ -619,12 +604,12 @@ def _run_network_train(model, rays_o, rays_d, z, mode, check_f16=None):
     N, S = z.shape
     max_rays = max(1, MAX_TRAIN_SAMPLES // S)
     if N <= max_rays:
-        return MLPRaysFunction.apply(model, mode, check_f16, rays_o, rays_d, z, *_params(model))
+        return MLPRaysFunction.apply(model, variant, check_f16, rays_o, rays_d, z, *_params(model))
     # a training launch addresses its saved-activation workspace with 32-bit byte offsets (DMNERF_MAX_TRAIN_SAMPLES in
     # include/dmnerf_hip.h): larger batches run as several launches, each with its own workspace; autograd adds the
     # parameter gradients of the pieces (rays are independent, so this is the same sum in a different order)
     params = _params(model)
-    return torch.cat([MLPRaysFunction.apply(model, mode, check_f16, rays_o[s:s + max_rays], rays_d[s:s + max_rays], z[s:s + max_rays], *params)
+    return torch.cat([MLPRaysFunction.apply(model, variant, check_f16, rays_o[s:s + max_rays], rays_d[s:s + max_rays], z[s:s + max_rays], *params)
                       for s in range(0, N, max_rays)], 0)
 
 
@@ -697,8 +682,7 @@ def run_network_train_skip(model, rays_o, rays_d, z, grid, split=None, check_f16
     z_c = torch.empty(n_pad, 1, dtype=torch.float32, device=dev)
     with torch.no_grad():
         _lib.launch("dmnerf_skip_gather_samples", rays_o, rays_d, z, N, max(S, 1), sel, n_sel, n_pad, o_c, d_c, z_c)
-    mode = "f16" if split == "f16x2" else None
-    raw_c = _run_network_train(model, o_c, d_c, z_c, mode, check_f16)     # [n_pad, 1, width]; n_pad = 0: no launch, zero gradients
+    raw_c = _run_network_train(model, o_c, d_c, z_c, split, check_f16)    # [n_pad, 1, width]; n_pad = 0: no launch, zero gradients
     return ScatterRows.apply(raw_c, raw, sel, n_sel)
 
 

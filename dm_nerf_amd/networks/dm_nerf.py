@@ -76,12 +76,7 @@ class DM_NeRF(nn.Module):
         self.density_linear = nn.Linear(W, 1)
         self.ins_linear = nn.Linear(W // 2, ins_num + 1)
         self.rgb_linear = nn.Linear(W // 2, 3)
-        self._blob = None
-        self._blob_key = None
-        self._blob_t = None
-        self._blob_t_key = None
-        self._blob_f = self._blob_s = self._flat = None
-        self._blob_f_key = self._blob_s_key = self._blob_ts_key = self._flat_key = None
+        self._packed = {}                                   # layout -> (key, tensor): see ``_cached`` (a plain attribute, no buffer)
 
     # -- kernel-layout weights --------------------------------------------------------------
     def _fused_ok(self):
@@ -97,122 +92,90 @@ class DM_NeRF(nn.Module):
                 "the packed weight blobs exist for the fused kernels' shape only (D=8, W=256, skips=[4], 63+27 input "
                 "channels); other shapes go through dm_nerf_amd.generic")
 
+    def _cached(self, layout):
+        """The kernel-layout copy ``layout`` of the weights ("flat", or a key of ``weights.LAYOUTS``): the one made last, or -- when
+        a parameter was updated in place or replaced since (see ``invalidate_blobs``) -- a NEW tensor, packed from ``flat()``.  Never
+        re-packed in place: a pending backward (two forwards around an optimizer step, ``retain_graph``) keeps the copies ITS forward
+        used, so its data gradients and its weight gradients see the same weights.  (``setdefault``: a module pickled whole before
+        the cache was one dict has no ``_packed``.)"""
+        if layout != "flat":
+            self._check_supported()
+        key = tuple((p.data_ptr(), p._version) for _, p in self.named_parameters())
+        cache = self.__dict__.setdefault("_packed", {})
+        ent = cache.get(layout)
+        if ent is None or ent[0] != key:
+            if layout == "flat":          # registration order: ``weights.PARAM_KEYS`` / ``flat_params`` for the fused kernels' shape
+                ent = (key, torch.cat([p.detach().reshape(-1).float() for _, p in self.named_parameters()]))
+            else:
+                ent = (key, weights.pack(layout, self.flat(), self.ins_num))
+            cache[layout] = ent
+        return ent[1]
+
     def invalidate_blobs(self):
         """Forget every cached kernel-layout copy of the weights; the next call re-packs from the parameters.
 
-        The caches are keyed on ``(data_ptr, tensor._version)`` of every parameter, which follows
+        The cache is keyed on ``(data_ptr, tensor._version)`` of every parameter, which follows
         ``optimizer.step()``, ``load_state_dict`` and any in-place op on the parameter itself.  Updates made THROUGH
         ``.data`` (``p.data.add_(...)``, hand-written optimizers, EMA / weight-clipping code) do not bump ``_version``:
         call this after them, or the kernels keep using the stale copy."""
-        self._blob_key = self._blob_t_key = self._flat_key = None
-        self._blob_f_key = self._blob_s_key = self._blob_ts_key = self._blob_h_key = self._blob_th_key = None
+        self._packed = {}
         self._generic_net = None                            # the generic path's packed weights (generic.py ``_run``)
 
     def install_packed(self, flat, blob, blob_t):
         """Adopt kernel-layout copies made elsewhere from the CURRENT parameters (dm_nerf_amd.optim.FlatAdam re-packs all of them
         in the launch that follows its update, csrc/optim.hip::repack_kernel): ``flat()``, ``blob()`` and ``blob_t()`` return them
-        until a parameter changes again.  The opt-in layouts (fused / split) are forgotten: an update THROUGH the flat storage
-        does not bump ``_version``, their keys could not tell."""
+        until a parameter changes again.  Every other layout is forgotten: an update THROUGH the flat storage does not bump
+        ``_version``, their keys could not tell."""
         key = tuple((p.data_ptr(), p._version) for _, p in self.named_parameters())
-        self._flat, self._blob, self._blob_t = flat, blob, blob_t
-        self._flat_key = self._blob_key = self._blob_t_key = key
-        self._blob_f_key = self._blob_s_key = self._blob_ts_key = self._blob_h_key = self._blob_th_key = None
+        self._packed = {"flat": (key, flat), "blob": (key, blob), "blob_t": (key, blob_t)}
         self._generic_net = None
 
     def flat(self):
         """The parameters as ONE flat f32 vector in state_dict order (what the packers gather from and what the backward's
         head kernels read, csrc/heads.hip); a NEW tensor whenever a parameter changed, so a pending backward keeps the
         vector its forward used."""
-        state = dict(self.named_parameters())
-        key = tuple((p.data_ptr(), p._version) for p in state.values())
-        if getattr(self, "_flat", None) is None or key != self._flat_key:
-            self._flat = weights.flat_params(state)
-            self._flat_key = key
-        return self._flat
+        return self._cached("flat")
 
     def blob(self):
-        """Kernel-layout weights, refreshed if any parameter was updated in place or replaced (see ``invalidate_blobs``): a NEW
-        tensor whenever a parameter changed, like ``flat`` -- a pending backward (two forwards around an optimizer step,
-        ``retain_graph``) keeps the blob ITS forward used, so its data gradients and its weight gradients see the same weights."""
-        self._check_supported()
-        state = dict(self.named_parameters())
-        key = tuple((p.data_ptr(), p._version) for p in state.values())
-        if self._blob is None or key != self._blob_key:
-            self._blob = weights.pack_blob(state, self.ins_num, flat=self.flat())
-            self._blob_key = key
-        return self._blob
+        """Kernel-layout weights of the default f32 kernels (refresh rule: ``_cached``)."""
+        return self._cached("blob")
 
     def blob_fused(self):
         """Inference blob with ``rgb_feature_linear`` / ``ins_feature_linear`` folded into the hidden layers
         (``dm_nerf(..., args)`` with ``args.fuse_heads = True``; same refresh rule as ``blob``)."""
-        self._check_supported()
-        state = dict(self.named_parameters())
-        key = tuple((p.data_ptr(), p._version) for p in state.values())
-        if getattr(self, "_blob_f", None) is None or key != self._blob_f_key:
-            self._blob_f = weights.pack_blob(state, self.ins_num, fused=True)
-            self._blob_f_key = key
-        return self._blob_f
+        return self._cached("blob_fused")
 
     def blob_split(self):
         """Split-bf16 inference blob (``args.mfma_split``; same refresh rule as ``blob``)."""
-        self._check_supported()
-        state = dict(self.named_parameters())
-        key = tuple((p.data_ptr(), p._version) for p in state.values())
-        if getattr(self, "_blob_s", None) is None or key != self._blob_s_key:
-            self._blob_s = weights.pack_blob_split(state, self.ins_num)
-            self._blob_s_key = key
-        return self._blob_s
+        return self._cached("blob_split")
 
     def blob_f16(self):
         """Split-f16 inference blob (``args.mfma_split = "f16x2"``; same refresh rule as ``blob``)."""
-        self._check_supported()
-        state = dict(self.named_parameters())
-        key = tuple((p.data_ptr(), p._version) for p in state.values())
-        if getattr(self, "_blob_h", None) is None or key != self._blob_h_key:
-            self._blob_h = weights.pack_blob_f16(state, self.ins_num)
-            self._blob_h_key = key
-        return self._blob_h
+        return self._cached("blob_f16")
 
     def blob_f16_density(self):
         """Split-f16 DENSITY blob (``dmnerf_mlp_fwd_rays_density_f16``): the table, the trunk groups and the ``density_linear`` groups of
-        ``blob_f16()``, copied on the device; same refresh rule as ``blob_f16`` (it is re-made whenever that blob is re-packed)."""
+        ``blob_f16()``, copied on the device; same refresh rule as ``blob_f16`` (it is keyed on that tensor: re-made whenever that
+        blob is re-packed)."""
         src = self.blob_f16()
-        if getattr(self, "_blob_hd", None) is None or self._blob_hd_src is not src:
-            lib = _lib.load()
-            out = torch.empty(int(lib.dmnerf_blob_f16_density_words(self.ins_num)), dtype=torch.float32, device=src.device)
+        ent = self._packed.get("blob_f16_density")
+        if ent is None or ent[0] is not src:
+            out = torch.empty(int(_lib.load().dmnerf_blob_f16_density_words(self.ins_num)), dtype=torch.float32, device=src.device)
             _lib.launch("dmnerf_blob_f16_density_from_f16", src, self.ins_num, out)
-            self._blob_hd, self._blob_hd_src = out, src
-        return self._blob_hd
+            ent = self._packed["blob_f16_density"] = (src, out)
+        return ent[1]
 
     def blob_t_f16(self):
         """Split-f16 W^T blob of the opt-in data-gradient kernel (training with ``args.mfma_split = "f16x2"``)."""
-        self._check_supported()
-        state = dict(self.named_parameters())
-        key = tuple((p.data_ptr(), p._version) for p in state.values())
-        if getattr(self, "_blob_th", None) is None or key != self._blob_th_key:
-            self._blob_th = weights.pack_blob_t_f16(self.flat(), self.ins_num)
-            self._blob_th_key = key
-        return self._blob_th
+        return self._cached("blob_t_f16")
 
     def blob_t_split(self):
         """Split-bf16 W^T blob of the opt-in data-gradient kernel (training with ``args.mfma_split``)."""
-        self._check_supported()
-        state = dict(self.named_parameters())
-        key = tuple((p.data_ptr(), p._version) for p in state.values())
-        if getattr(self, "_blob_ts", None) is None or key != self._blob_ts_key:
-            self._blob_ts = weights.pack_blob_t_split(self.flat(), self.ins_num)
-            self._blob_ts_key = key
-        return self._blob_ts
+        return self._cached("blob_t_split")
 
     def blob_t(self):
         """W^T blob for the backward data-gradient kernel (same refresh rule as ``blob``)."""
-        self._check_supported()
-        state = dict(self.named_parameters())
-        key = tuple((p.data_ptr(), p._version) for p in state.values())
-        if self._blob_t is None or key != self._blob_t_key:
-            self._blob_t = weights.pack_blob(state, self.ins_num, transposed=True, flat=self.flat())
-            self._blob_t_key = key
-        return self._blob_t
+        return self._cached("blob_t")
 
     def forward(self, x):
         """``[M, 63+27] -> [M, 4 + ins_num + 1]`` = cat[rgb, density, ins] (networks/dm_nerf.py:80-106)."""

@@ -38,9 +38,8 @@ def run_network(model, rays_o, rays_d, z_vals, split=None):
     _lib.require_gpu(rays_o, rays_d, z)
     N, S = z.shape
     raw = torch.empty(N, S, 4 + model.ins_num + 1, dtype=torch.float32, device=z.device)
-    blob, name = {None: (model.blob, "dmnerf_mlp_fwd_rays"), "bf16x3": (model.blob_split, "dmnerf_mlp_fwd_rays_split"),
-                  "f16x2": (model.blob_f16, "dmnerf_mlp_fwd_rays_f16")}[split or None]
-    _lib.launch(name, blob(), model.ins_num, rays_o, rays_d, z, N, S, raw)
+    v = weights.VARIANTS[split or None]
+    _lib.launch(v.fwd, getattr(model, v.blob)(), model.ins_num, rays_o, rays_d, z, N, S, raw)
     return raw
 
 
@@ -210,15 +209,16 @@ def _ray_inputs(rays, position_embedder, view_embedder, model_coarse, model_fine
 # hidden layers (-19 % MACs; results equal up to f32 re-association)
 # args.mfma_split (extension, default off): split-operand 16-bit MFMA inference (f32-class accuracy, not bitwise the f32
 # chain): True / "bf16x3" = three bf16 planes, six products; "f16x2" = two f16 planes, three products
-_KERNELS = {None: (0, "blob"), "fused": (1, "blob_fused"), "bf16x3": (2, "blob_split"), "f16x2": (3, "blob_f16")}   # fused_heads, blob
+# What each of them runs on (``fused_heads``, blob, entries): ``weights.VARIANTS``.
 
 
 def _fill_args(a, p, split, out, ws, _events, coarse_blob=None):
     """What ``RenderArgs`` and ``RenderFineArgs`` share: blobs / ``fused_heads`` by ``split`` or ``args.fuse_heads`` (``coarse_blob``:
     another one for the coarse model), rays, draws, sizes, the fine outputs, the weight workspace and the event pair."""
-    a.fused_heads, blob = _KERNELS[split or ("fused" if bool(getattr(p.args, "fuse_heads", False)) else None)]
-    a.d_blob_coarse = getattr(p.model_coarse, coarse_blob or blob)().data_ptr()
-    a.d_blob_fine = getattr(p.model_fine, blob)().data_ptr()
+    v = weights.VARIANTS[split or ("fused" if bool(getattr(p.args, "fuse_heads", False)) else None)]
+    a.fused_heads = v.fused_heads
+    a.d_blob_coarse = getattr(p.model_coarse, coarse_blob or v.blob)().data_ptr()
+    a.d_blob_fine = getattr(p.model_fine, v.blob)().data_ptr()
     a.ins_num = p.model_fine.ins_num
     a.d_rays_o, a.d_rays_d, a.d_z_in = p.rays_o.data_ptr(), p.rays_d.data_ptr(), p.z_in.data_ptr()
     a.d_t_rand = p.t_rand.data_ptr() if p.t_rand is not None else None

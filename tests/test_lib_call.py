@@ -109,6 +109,18 @@ def test_every_call_site_uses_the_helper_its_entry_needs():
                 assert takes_stream(params), f"{rel}: _lib.launch(\"{name}\") but its last parameter is not void* stream"
             else:
                 assert not takes_stream(params) and ret == "int", f"{rel}: _lib.call(\"{name}\") needs a host-only entry returning int"
+    # the entries that dm_nerf_amd/weights.py names in its tables instead of at a call site: index and plan entries go through
+    # _lib.call, stream packers and kernel entries through _lib.launch
+    from dm_nerf_amd import weights
+    by_table = [("call", f_index) for _, _, f_index, _, _ in weights.LAYOUTS.values()]
+    by_table += [("launch", f_stream) for _, _, _, _, f_stream in weights.LAYOUTS.values()]
+    for v in weights.VARIANTS.values():
+        by_table += [("launch", v.fwd), ("launch", v.fwd_train), ("launch", v.dgrad), ("launch", v.wgrad), ("call", v.plan[0]), ("call", v.plan[1])]
+    for helper, name in by_table:
+        assert name in decl, f"weights.py: {name} is not declared in include/dmnerf_hip.h"
+        ret, params = decl[name]
+        sites += 1
+        assert ret == "int" and takes_stream(params) == (helper == "launch"), f"weights.py: {name} is not an entry for _lib.{helper}"
     assert sites >= 100                                     # (the scan did see the package)
 
 

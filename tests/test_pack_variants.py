@@ -1,7 +1,6 @@
-"""Host-side checks (no GPU) of the two opt-in inference blobs: the fused-heads f32 blob and the split-bf16 blob
-are re-arrangements of the same parameters as the default blob (include/dmnerf_hip.h; csrc/layout.h, pack.cpp)."""
-import ctypes
-
+"""Host-side checks (no GPU) of the opt-in blobs: the fused-heads f32 blob and the split blobs are re-arrangements of the same
+parameters as the default blob (include/dmnerf_hip.h; csrc/layout.h, pack.cpp), and the layout table of dm_nerf_amd/weights.py
+builds, for every layout, the index the library's builder gives when called by hand."""
 import numpy as np
 import pytest
 
@@ -36,7 +35,7 @@ def test_split_index_addresses_the_right_parameters(ins_num):
     total = lib.dmnerf_blob_split_words(ins_num)
     n = (total - TAB) * 2
     idx = np.empty(n, dtype=np.int32)
-    _lib.check(lib.dmnerf_build_pack_index_split(ins_num, idx.ctypes.data_as(ctypes.c_void_p), n), "split index")
+    _lib.call("dmnerf_build_pack_index_split", ins_num, idx, n)
     C = ins_num + 1
     obx = {1: 1, 2: 2, 3: 4, 4: 4}[(C + 31) // 32]
     # parameter offsets in the flat vector (reference state_dict order)
@@ -82,7 +81,7 @@ def test_transposed_split_index_addresses_the_right_parameters(ins_num):
     total = lib.dmnerf_blob_t_split_words(ins_num)
     n = (total - TAB_T) * 2
     idx = np.empty(n, dtype=np.int32)
-    _lib.check(lib.dmnerf_build_pack_index_t_split(ins_num, idx.ctypes.data_as(ctypes.c_void_p), n), "split index (transposed)")
+    _lib.call("dmnerf_build_pack_index_t_split", ins_num, idx, n)
     C = ins_num + 1
     obi = (C + 31) // 32
     shapes = {"mlps.0": (256, 63), **{f"mlps.{i}": (256, 319 if i == 5 else 256) for i in range(1, 8)},
@@ -129,7 +128,7 @@ def test_f16_index_addresses_the_right_parameters(ins_num):
     assert total == TAB + (n_groups + 6) * 4096                    # + F16_LA landing groups
     n = (total - TAB) * 2
     tab, idx = np.empty(TAB, dtype=np.int32), np.empty(n, dtype=np.int32)
-    _lib.check(lib.dmnerf_build_pack_index_f16(ins_num, tab.ctypes.data_as(ctypes.c_void_p), TAB, idx.ctypes.data_as(ctypes.c_void_p), n), "f16 index")
+    _lib.call("dmnerf_build_pack_index_f16", ins_num, tab, TAB, idx, n)
     shapes = {"mlps.0": (256, 63), **{f"mlps.{i}": (256, 319 if i == 5 else 256) for i in range(1, 8)},
               "rgb_feature_linear": (256, 256), "ins_feature_linear": (256, 256), "rgb_feature_linears.0": (128, 283),
               "ins_feature_linears.0": (128, 256), "density_linear": (1, 256), "ins_linear": (C, 128), "rgb_linear": (3, 128)}
@@ -215,3 +214,76 @@ def test_fuse_heads_is_the_same_function():
     ins = hi @ sf["ins_linear.weight"].t() + sf["ins_linear.bias"]
     got = torch.cat([rgb, den, ins], -1)
     assert float(((got - want).abs() / (1 + want.abs())).max()) <= 2e-6
+
+
+# layout -> (size entry, index entry, table floats or None, the index entry also fills the table), written out by hand
+BUILDERS = {"blob": ("dmnerf_blob_floats", "dmnerf_build_pack_index", None, False),
+            "blob_fused": ("dmnerf_blob_fused_floats", "dmnerf_build_pack_index_fused", None, False),
+            "blob_t": ("dmnerf_blob_t_floats", "dmnerf_build_pack_index_t", None, False),
+            "blob_split": ("dmnerf_blob_split_words", "dmnerf_build_pack_index_split", TAB, False),
+            "blob_f16": ("dmnerf_blob_f16_words", "dmnerf_build_pack_index_f16", TAB, True),
+            "blob_t_split": ("dmnerf_blob_t_split_words", "dmnerf_build_pack_index_t_split", 1024, False),
+            "blob_t_f16": ("dmnerf_blob_t_f16_words", "dmnerf_build_pack_index_t_f16", 1024, False)}
+
+
+@pytest.mark.parametrize("ins_num", [13, 93])
+@pytest.mark.parametrize("layout", sorted(BUILDERS))
+def test_table_driven_index_is_the_librarys_builder_called_directly(layout, ins_num):
+    assert set(W.LAYOUTS) == set(BUILDERS)
+    f_size, f_index, tab_n, own_tab = BUILDERS[layout]
+    total = getattr(_lib.load(), f_size)(ins_num)
+    assert total > 0
+    n = total if tab_n is None else (total - tab_n) * 2
+    want, want_tab = np.full(n, -7, dtype=np.int32), None
+    if own_tab:
+        want_tab = np.full(tab_n, -7, dtype=np.int32)
+        _lib.call(f_index, ins_num, want_tab, tab_n, want, n)
+    else:
+        _lib.call(f_index, ins_num, want, n)
+    got_tab, got = W.index_host(layout, ins_num)
+    assert got.dtype == np.int32 and np.array_equal(got, want)
+    assert (got_tab is None) if want_tab is None else np.array_equal(got_tab, want_tab)
+
+
+def test_public_index_functions_are_the_tables():
+    for ins_num in (13, 93):
+        assert np.array_equal(W.pack_index_host(ins_num), W.index_host("blob", ins_num)[1])
+        assert np.array_equal(W.pack_index_t_host(ins_num), W.index_host("blob_t", ins_num)[1])
+        assert np.array_equal(W.pack_index_fused_host(ins_num), W.index_host("blob_fused", ins_num)[1])
+    with pytest.raises(ValueError, match="unsupported ins_num=0"):
+        W.pack_index_host(0)
+
+
+def _count_builds(monkeypatch):
+    built, real = [], W.index_host
+    monkeypatch.setattr(W, "_index_cache", {})
+    monkeypatch.setattr(W, "index_host", lambda layout, ins_num: built.append((layout, ins_num)) or real(layout, ins_num))
+    return built
+
+
+def test_index_cache_builds_each_host_index_once(monkeypatch):
+    import torch
+    built = _count_builds(monkeypatch)
+    for _ in range(2):
+        for layout in W.LAYOUTS:
+            tab, idx = W._index(layout, 13, torch.device("cpu"))
+            assert idx.dtype == torch.int32 and (tab is not None) == (layout == "blob_f16")
+        assert W.pack_index(13, "cpu") is W._index("blob", 13, "cpu")[1]
+        assert W.pack_index(13, "cpu", True) is W._index("blob_t", 13, "cpu")[1]
+        assert W.pack_index(13, "cpu", False, True) is W._index("blob_fused", 13, "cpu")[1]
+    assert sorted(built) == sorted((layout, 13) for layout in W.LAYOUTS)
+    assert set(W._index_cache) == {(13, "cpu", layout) for layout in W.LAYOUTS}
+
+
+@pytest.mark.gpu
+def test_index_cache_holds_one_entry_per_layout_after_two_packs(monkeypatch):
+    import torch
+    from oracle import ref_cpu as O
+    assert torch.cuda.is_available(), "GPU tests need a MI355X"
+    built = _count_builds(monkeypatch)
+    flat = W.flat_params({k: v.cuda() for k, v in O.make_weights(5, 13, gain=1.7, sigma_bias=0.3).items()})
+    for layout in W.LAYOUTS:
+        a, b = W.pack(layout, flat, 13), W.pack(layout, flat, 13)
+        assert a is not b and torch.equal(a, b), layout
+    assert sorted(built) == sorted((layout, 13) for layout in W.LAYOUTS)
+    assert set(W._index_cache) == {(13, str(flat.device), layout) for layout in W.LAYOUTS}
