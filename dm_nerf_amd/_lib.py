@@ -66,6 +66,11 @@ class ChainLayer(ctypes.Structure):
     _fields_ = [("d_B", c_vp), ("d_bias", c_vp), ("ldb", c_int), ("from_act", c_int), ("from_x", c_int), ("relu", c_int)]
 
 
+class VolumeEditEntry(ctypes.Structure):
+    """``dmnerf_volume_edit_entry`` (include/dmnerf_hip.h)."""
+    _fields_ = [("kind", c_int), ("label", c_int), ("m", c_float * 12)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/dmnerf_hip.h declares
 SIGNATURES = {
     "dmnerf_adam_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_double, c_vp, c_double, c_double, c_double, c_vp, c_vp]),
@@ -218,6 +223,9 @@ SIGNATURES = {
     "dmnerf_baked_render": (c_int, [c_vp, c_vp, ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_int),
                                     c_int, c_vp, c_int, c_i64, ctypes.POINTER(ctypes.c_uint32), c_float, c_float, c_float, c_vp, c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_vp]),
+    "dmnerf_volume_edit": (ctypes.c_int32, [c_vp, c_vp, ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_int),
+                                   c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(VolumeEditEntry), c_int, c_int, c_vp, c_vp, c_vp,
+                                   c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

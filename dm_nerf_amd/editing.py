@@ -6,6 +6,7 @@
     :233-339             the evaluation's pose loop with PSNR / SSIM / AP             ->  ``manipulate_eval_path``
     :472-488, :310-323   8-bit frame, label, label mask, coloured object image        ->  ``frame_products``, ``label_lut``
     (extension)          remove, duplicate, isolate: entries next to matrices / ``Deform``  ->  ``Remove``, ``Copy``, ``keep_labels=``
+    (extension)          the edit applied to a label / baked volume itself, with collision counts  ->  ``edit_volume``
     tools/pose_generator.py:67-77   a matrix about a centre; the centre from a ``field.LabelGrid``  ->  ``about``, ``object_centre``
 
 The frames are rendered by ``distributed.ManipulationFrameRenderer`` (rows sharded over the ranks, one all-gather per frame); the
@@ -324,6 +325,107 @@ def render_preview(baked, H, W, K, pose, trans_list=(), target_labels=(), keep_l
     return {"rgb": out["rgb"].reshape(H, W, 3), "depth": out["depth"].reshape(H, W), "acc": out["acc"].reshape(H, W), "label": label,
             "source": out["source"].reshape(H, W), "nseg": out["nseg"].reshape(H, W),
             "ins_img": _preview_colours("render_preview", label, lut, baked.C)}
+
+
+# ---- an edit applied to the volume itself (csrc/volume_edit.hip; tests/_volume_edit_restate.py states it in numpy)
+MAX_VOLUME_EDITS = 32           # DMNERF_VOLUME_EDIT_MAX (include/dmnerf_hip.h)
+VOLUME_RULES = {"first": 0, "densest": 1}
+
+
+def _overlaps(a, b):
+    """Two tensors share device memory."""
+    if a is None or b is None or a.device != b.device:
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def edit_volume(grid, trans_list, target_labels, keep_labels=None, rule="first", out=None):
+    """The edit applied to the volume itself: ``grid`` (a ``field.LabelGrid`` or a ``field.BakedGrid``) resampled under ``trans_list``
+    once -> ``{"grid", "source", "won", "claimed", "hits"}``, all on the device.  ``"grid"`` is a new object of ``grid``'s class over the
+    same box and ``C``: a scene like any other, so ``stats()``, ``skip_grid()``, ``pick``, ``preview_frame`` / ``render_preview`` with an
+    empty ``trans_list`` (ONE ray set per frame, for any number of edits) and a second ``edit_volume`` work on it unchanged.
+
+    ``trans_list`` / ``target_labels`` / ``keep_labels`` are the renderers': 4 x 4 matrices (``about(...)`` products as they are),
+    ``Remove()`` and ``Copy(matrix)``; at most 32 entries.  The target pose of an entry is ``trans @ pose``, so a point ``x`` of a pixel's
+    original ray corresponds to ``trans x`` on its target ray: the edited volume at ``x`` is the source volume at ``trans x``.  The matrix
+    (rounded to f32 once) maps the centre of a DESTINATION cell to its source point; no inverse is taken.  Per cell (``dmnerf_volume_edit``,
+    one launch): candidate 0 is the cell's own content unless its label is that of a MOVE or REMOVE entry (or not in ``keep_labels``);
+    candidate ``1 + e`` is the source cell of a MOVE / COPY entry ``e`` if it lies in the box and carries ``target_labels[e]``.
+    ``rule="first"``: the lowest candidate wins; ``rule="densest"`` (baked volumes only): the one with the largest source sigma, the
+    lowest on ties, a NaN sigma never beating a number.  Nearest-cell resampling, no interpolation; a rotated object keeps the colour
+    baked for the box's +z direction; what leaves the box is lost.
+
+    ``source`` uint8 ``[dx, dy, dz]``: the winner's candidate number, 255 for none.  Here ``1 + e`` is the index into ``trans_list``,
+    ``Remove`` entries INCLUDED -- unlike ``preview_frame``'s ``source``, which counts only the entries with rays.  ``won [1 + E]``,
+    ``claimed [E]``, ``hits [E, C]`` int64: cells per winner; cells where candidate ``1 + e`` exists, winner or not; and for every cell
+    with two or more candidates, every entry ``e`` among them and every OTHER candidate ``b`` there, ``hits[e, label(b)] += 1``
+    (``label(0)`` the cell's own label): ``hits[e, l] > 0`` reads "entry e lands on something that carries label l".  Integer atomics
+    only: the same numbers every run.
+
+    ``out``: an earlier result's ``"grid"`` (the same class, dims, ``C``, box and device) to write into (it must not share memory with ``grid``).
+    Nothing reaches the host: after one warm-up call, ``edit_volume(..., out=res["grid"])`` can be captured in a graph and follows
+    ``grid.labels`` / ``grid.cells`` on replay.
+
+    ``ValueError``, before anything touches a device: a ``Deform``, bare or inside ``Copy`` (its target rays depend on the image row:
+    there is no world-space map to resample under), more than 32 entries, a label outside ``[0, C)``, unequal list lengths,
+    ``rule="densest"`` on a plain ``LabelGrid``, an ``out`` of another class / dims / ``C`` / box / device or one that aliases ``grid``.  CPU tensors
+    raise as everywhere (``_lib.require_gpu``)."""
+    from . import field
+    who = "edit_volume"
+    if not isinstance(grid, field.LabelGrid):
+        raise TypeError(f"{who}: grid must be a field.LabelGrid or a field.BakedGrid")
+    baked = isinstance(grid, field.BakedGrid)
+    C = grid.C
+    trans_list, target_labels = list(trans_list), [int(l) for l in target_labels]
+    if len(trans_list) != len(target_labels):
+        raise ValueError(f"{who}: {len(target_labels)} target labels for {len(trans_list)} edits")
+    E = len(trans_list)
+    if E > MAX_VOLUME_EDITS:
+        raise ValueError(f"{who}: {E} edits, at most {MAX_VOLUME_EDITS} in one call (apply the rest to the result)")
+    if rule not in VOLUME_RULES:
+        raise ValueError(f"{who}: rule must be 'first' or 'densest', got {rule!r}")
+    if rule == "densest" and not baked:
+        raise ValueError(f"{who}: rule='densest' compares baked densities: it needs a field.BakedGrid, not a plain LabelGrid")
+    keep = range(C) if keep_labels is None else sorted({int(l) for l in keep_labels})
+    for l in target_labels + list(keep if keep_labels is not None else ()):
+        if not 0 <= l < C:
+            raise ValueError(f"{who}: label {l} outside [0, {C})")
+    entries = (_lib.VolumeEditEntry * E)() if E else None
+    for e, (trans, label) in enumerate(zip(trans_list, target_labels)):
+        matrix = trans.matrix if isinstance(trans, Copy) else trans
+        if isinstance(matrix, Deform):
+            raise ValueError(f"{who}: entry {e} is a {trans!r}: a deformation's target rays depend on the image row, so it has no "
+                             "world-space map to resample the volume under (preview_frame / render_preview take it)")
+        entries[e].kind, entries[e].label = edit_kind(trans), label
+        if not isinstance(trans, Remove):
+            m = (matrix.detach().cpu().numpy() if torch.is_tensor(matrix) else np.asarray(matrix)).astype(np.float64)
+            if m.shape != (4, 4):
+                raise ValueError(f"{who}: entry {e} must be a 4 x 4 matrix, a Remove() or a Copy(matrix), got shape {m.shape}")
+            entries[e].m[:] = [float(v) for v in m.astype(np.float32)[:3, :4].reshape(-1)]
+    src_cells = grid.cells if baked else None
+    if out is not None:
+        if out is not grid and (type(out) is not type(grid) or out.dims != grid.dims or out.C != C or not np.array_equal(out.lo, grid.lo)
+                                or not np.array_equal(out.hi, grid.hi) or out.labels.device != grid.labels.device):
+            raise ValueError(f"{who}: out must be a {type(grid).__name__} of dims {grid.dims}, C = {C} and the box {grid.lo} .. {grid.hi} on "
+                             f"{grid.labels.device} (an earlier result's 'grid')")
+        if out is grid or _overlaps(out.labels, grid.labels) or (baked and _overlaps(out.cells, grid.cells)):
+            raise ValueError(f"{who}: out shares memory with the source volume (the kernel reads other cells than the one it writes)")
+    _lib.require_gpu(grid.labels, src_cells)
+    dev = grid.labels.device
+    if out is None:
+        labels = torch.empty_like(grid.labels)
+        out = field.BakedGrid(labels, torch.empty_like(grid.cells), grid.lo, grid.hi, C) if baked else field.LabelGrid(labels, grid.lo, grid.hi, C)
+    else:
+        _lib.require_gpu(out.labels, out.cells if baked else None)
+    res = {"grid": out, "source": torch.empty(grid.dims, dtype=torch.uint8, device=dev),
+           "won": torch.empty(1 + E, dtype=torch.int64, device=dev), "claimed": torch.empty(E, dtype=torch.int64, device=dev),
+           "hits": torch.empty(E, C, dtype=torch.int64, device=dev)}
+    f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
+    _lib.launch("dmnerf_volume_edit", grid.labels, src_cells, f3(grid.lo), f3(grid.cell), f3(grid.inv_cell), (ctypes.c_int * 3)(*grid.dims), C,
+                (ctypes.c_uint32 * 4)(*field.label_mask_words(keep, C)), entries, E, VOLUME_RULES[rule], out.labels,
+                out.cells if baked else None, res["source"], res["won"], res["claimed"], res["hits"])
+    return res
 
 
 def _render(H, W, K, pose, edits, models, args, frame_kw):

@@ -823,6 +823,44 @@ int dmnerf_baked_render(const uint8_t* d_labels, const float* d_cells, const flo
                         float stop, float* d_rgb, float* d_depth, float* d_acc, uint8_t* d_label, uint8_t* d_source, int32_t* d_nseg,
                         void* stream);
 
+/* An edit applied to the volume itself (csrc/volume_edit.hip): the label / baked volume resampled under a list of moves, copies and
+ * removals into a volume of the same kind, with what the edit covers and what it collides with.  Additive (the ABI version stays).
+ *   dmnerf_volume_edit: d_labels [dx,dy,dz] uint8 and, for a baked volume, d_cells [dx,dy,dz,4] f32 (else null, with d_out_cells)
+ *     over the box of the HOST arrays lo, cell, inv_cell, dims (dmnerf_label_trace's); keep = the four HOST words of the labels that
+ *     exist at all (dmnerf_skip_grid_from_labels' mask); entries = E <= 32 HOST entries {kind, label, m[12]}: kind 0 MOVE / 1 COPY /
+ *     2 REMOVE (networks/manipulator.py), label in [0, C), m = rows 0..2 of the entry's 4 x 4 matrix in f32.  The target pose of an
+ *     entry is trans @ pose, so the edited volume at x is the source volume at trans x: m maps the centre of a DESTINATION cell to its
+ *     source point, no inverse is taken.  One lane per destination cell g = (i * dy + j) * dz + k, every f32 operation rounded on its
+ *     own (tests/_volume_edit_restate.py states it in numpy):
+ *     Centre: p_a = (float(idx_a) + 0.5) * cell_a + lo_a.
+ *     Candidate 0, the cell's own content: its label l0 < C, in keep, and not the label of a MOVE or REMOVE entry.
+ *     Candidate 1 + e, for a MOVE or COPY entry e: q_a = ((m_a0 p_x + m_a1 p_y) + m_a2 p_z) + m_a3, c_a = floor((q_a - lo_a) *
+ *       inv_cell_a); it exists iff 0 <= c_a < dims_a on all axes (false for NaN), the source label there equals the entry's label and
+ *       that label is in keep.  Nearest-cell resampling: no interpolation.
+ *     Winner: rule 0 ("first") the lowest candidate; rule 1 ("densest", baked only) the candidate with the largest source sigma
+ *       (d_cells[..., 3]), the lowest on equal sigma; a NaN sigma never beats a number and loses to any number.
+ *     Outputs per cell: d_out_labels = the winner's label or 255; d_out_source = the winner's candidate number or 255 (1 + e counts
+ *       REMOVE entries: it is the index into the list); d_out_cells = the winner's 16 bytes (one load, one store), zeros without one.
+ *     Counts, written whole by the call: d_won [1 + E] cells per winner; d_claimed [E] cells where candidate 1 + e exists; d_hits
+ *       [E, C]: for every cell with two or more candidates, every entry e among them and every OTHER candidate b there,
+ *       hits[e, label(b)] += 1, label(0) being the cell's own label.  Integer atomics only (per-wave popcounts into an LDS table, one
+ *       flush): the same numbers every run.
+ *     Returns the status as int32_t: 0 or a DMNERF_E_* code, with dmnerf_last_error() set, like every other entry.
+ *     E == 0 is legal (the volume filtered by keep; d_claimed and d_hits are empty and may be null).
+ *     Refused: bad dims / C / E / kind / label / rule, rule 1 without d_cells, d_cells without d_out_cells or the reverse, cells not
+ *     16-byte aligned, a destination (volume, source or count buffer) that overlaps a source or another destination.  No allocation,
+ *     no synchronisation, no host read: it can be captured in a graph and reads d_labels / d_cells anew on every replay. */
+#define DMNERF_VOLUME_EDIT_MAX 32
+typedef struct {
+    int kind;
+    int label;
+    float m[12];
+} dmnerf_volume_edit_entry;
+int32_t dmnerf_volume_edit(const uint8_t* d_labels, const float* d_cells, const float lo[3], const float cell[3], const float inv_cell[3],
+                           const int dims[3], int C, const uint32_t keep[4], const dmnerf_volume_edit_entry* entries, int E, int rule,
+                           uint8_t* d_out_labels, float* d_out_cells, uint8_t* d_out_source, int64_t* d_won, int64_t* d_claimed,
+                           int64_t* d_hits, void* stream);
+
 /* The two renders above on the OPT-IN split-f16 ("f16x2") kernels (csrc/mlp_f16_density.hip, csrc/mlp_f16_sparse.hip; the body of
  * csrc/mlp_f16_impl.h with template flags).  Additive (the ABI version stays).
  *   f16 density blob: dmnerf_blob_f16_density_words 32-bit words = [the f16 blob's 4096-float bias table | its 120 trunk groups
