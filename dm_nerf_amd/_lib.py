@@ -226,6 +226,10 @@ SIGNATURES = {
     "dmnerf_volume_edit": (ctypes.c_int32, [c_vp, c_vp, ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_int),
                                    c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(VolumeEditEntry), c_int, c_int, c_vp, c_vp, c_vp,
                                    c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_field_edit_select": (ctypes.c_int32, [c_vp, ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_int), c_int, c_int,
+                                         ctypes.POINTER(VolumeEditEntry), c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_field_edit_filter": (ctypes.c_int32, [c_vp, c_vp, c_i64, c_int, ctypes.POINTER(ctypes.c_uint32), c_int, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -672,6 +672,13 @@ def _skip_manipulate_chunk(ori_rays, tar_rays, models, args, us, grid=None, leve
                           keep_labels=getattr(args, "keep_labels", None), skip=grid, skip_levels=levels, skip_counts=counts)
 
 
+def _field_edit_chunk(ori_rays, tar_rays, models, args, us, edit=None, counts=None):
+    """The chunk of a ``field_edit=`` frame: ``manipulator.edited_field`` with the FIRST of the chunk's draws; no target side (zeros)."""
+    from .networks import manipulator as Mn
+    rgb, ins, _ = Mn.edited_field(models[0], models[1], ori_rays, args, edit, u=us[0], counts=counts)
+    return rgb, ins, torch.zeros_like(rgb), torch.zeros_like(ins)
+
+
 def _default_draws(n, n_imp, count, device):
     return [torch.rand([n, n_imp], device=device) for _ in range(count)]
 
@@ -734,11 +741,19 @@ class ManipulationFrameRenderer:
     not evaluate samples in empty cells and writes the empty row there.  The draws do not depend on the grid, so the assembled frame
     stays bit-identical whatever the world size.  ``self.n_eval``: int64 ``[2]`` on the device, the samples evaluated and the samples
     in all over the steps this rank rendered (zeros without ``skip=``); it never reaches the host.  ``skip=`` cannot be combined with
-    an injected ``manipulate_chunk=``."""
+    an injected ``manipulate_chunk=``.
+
+    ``field_edit=`` an ``editing.FieldEdit`` (opt-in): the frame is the FIELD-EDIT render -- every chunk goes through
+    ``manipulator.edited_field``, the trained field seen through the edited volume with one network evaluation per sample (two sparse
+    launches per chunk for any number of edits; a render with its own contract).  The edits live in the ``FieldEdit``:
+    ``trans_list`` must be empty, ``T = 0``, and it cannot be combined with ``skip=``, ``keep_labels=`` or ``manipulate_chunk=``
+    (``ValueError``).  ``step`` still makes its usual two draws per chunk on every rank and the route uses the first, so the frame stays
+    bit-identical whatever the world size; the ``tar_rgb | tar_ins`` columns of the band are zero; ``n_eval`` counts the samples
+    evaluated and the samples in all."""
 
     def __init__(self, H, W, K, ori_pose, trans_list, models, args, chunk=None, raygen=None, manipulate_chunk=None, draws=None,
                  ins_num=None, rank=None, world=None, dtype=torch.float32, target_rays=None, keep_labels=None, skip=None,
-                 skip_levels=("coarse", "fine")):
+                 skip_levels=("coarse", "fine"), field_edit=None):
         r_, w_ = world_info()
         self.rank, self.world = (r_ if rank is None else int(rank)), (w_ if world is None else int(world))
         self._collective = rank is None and world is None
@@ -752,6 +767,17 @@ class ManipulationFrameRenderer:
         if skip is not None and manipulate_chunk is not None:
             raise ValueError("ManipulationFrameRenderer: skip= routes the chunks through manipulator(skip=); it cannot be combined "
                              "with manipulate_chunk=")
+        if field_edit is not None:
+            from .editing import FieldEdit
+            who = "ManipulationFrameRenderer: field_edit="
+            if not isinstance(field_edit, FieldEdit):
+                raise TypeError(f"{who} must be an editing.FieldEdit")
+            if len(trans_list):
+                raise ValueError(f"{who} carries the edits itself (FieldEdit.from_volume(grid, trans_list, ...)); trans_list must be empty")
+            if skip is not None or manipulate_chunk is not None or keep_labels is not None:
+                raise ValueError(f"{who} routes the chunks through manipulator.edited_field; it cannot be combined with skip=, "
+                                 "manipulate_chunk= or keep_labels= (the keep set is the FieldEdit's)")
+            self.args.target_labels = []
         self._skip = None
         if skip is not None:
             from .networks import render
@@ -760,7 +786,7 @@ class ManipulationFrameRenderer:
         self.draws = draws or _default_draws
         from .editing import Copy, Deform, edit_kind
         kinds = [edit_kind(trans) for trans in trans_list]
-        if len(kinds) == 0 and keep_labels is None:
+        if len(kinds) == 0 and keep_labels is None and field_edit is None:
             raise ValueError("ManipulationFrameRenderer: at least one transformation")
         if any(kinds) or keep_labels is not None:                   # removals, copies, a keep set: manipulator()'s edit path
             if len(self.args.target_labels) != len(kinds):
@@ -815,6 +841,9 @@ class ManipulationFrameRenderer:
         if self._skip is not None:
             import functools
             self.manipulate_chunk = functools.partial(_skip_manipulate_chunk, grid=self._skip[0], levels=self._skip[1], counts=self.n_eval)
+        if field_edit is not None:
+            import functools
+            self.manipulate_chunk = functools.partial(_field_edit_chunk, edit=field_edit, counts=self.n_eval)
 
     def owned(self, c):
         """Rows of the band that chunk ``c`` of the frame covers: (first, last + 1) in band coordinates; empty if first >= last."""

@@ -235,6 +235,15 @@ def pick(label_grid, H, W, K, pose, pixels, near, far, labels=None):
     return label, t, point, cell
 
 
+def edit_label_sets(C, target_labels, kinds, keep_labels=None):
+    """The exchanger's per-sample rule as label sets -> ``(own, per_entry)``: ``own`` = what the original rays / a cell's own content
+    may show, every kept label but those of MOVE and REMOVE entries (not where they were); ``per_entry[e]`` = what entry ``e`` may show,
+    its own label if kept -- nothing for a REMOVE, which shows nothing anywhere."""
+    allowed = set(range(C)) if keep_labels is None else {int(l) for l in keep_labels}
+    gone = {int(l) for l, k in zip(target_labels, kinds) if k != 1}
+    return sorted(allowed - gone), [[int(l)] if (k != 2 and int(l) in allowed) else [] for l, k in zip(target_labels, kinds)]
+
+
 def _preview_sets(who, label_grid, H, W, K, pose, trans_list, target_labels, keep_labels, max_sets=None):
     """The rays and label sets of an edit preview (``preview_frame``'s docstring) -> ``(rays [R, 2, H W, 3], R label sets)``: set 0 the
     original rays of ``ManipulationFrameRenderer`` with every label but those of MOVE and REMOVE entries, set ``1 + e`` the target rays
@@ -259,9 +268,8 @@ def _preview_sets(who, label_grid, H, W, K, pose, trans_list, target_labels, kee
                                      keep_labels=keep if (keep is not None or trans_list) else ())
     if fr.ori.device != label_grid.labels.device:
         raise RuntimeError(f"{who}: the label volume lives on another device than the rays")
-    allowed = set(range(C)) if keep is None else set(keep)
-    gone = {l for l, k in zip(target_labels, kinds) if k != 1}                      # MOVE and REMOVE: not where it was
-    sets = [sorted(allowed - gone)] + [[l] if l in allowed else [] for l, k in zip(target_labels, kinds) if k != 2]
+    own, per_entry = edit_label_sets(C, target_labels, kinds, keep)
+    sets = [own] + [s for s, k in zip(per_entry, kinds) if k != 2]
     rays = torch.cat([fr.ori[None], fr.tar], dim=0) if fr.T else fr.ori[None]
     return rays, sets
 
@@ -340,6 +348,26 @@ def _overlaps(a, b):
     return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
+def pack_entries(who, trans_list, target_labels, what_for):
+    """``trans_list`` / ``target_labels`` (equal lengths, checked by the caller) as ``dmnerf_volume_edit_entry`` structs, ``None`` for an
+    empty list: kind, label, and rows 0..2 of the matrix rounded to f32 once.  A ``Deform``, bare or inside ``Copy``, and a matrix that
+    is not 4 x 4 raise ``ValueError`` in ``who``'s name; ``what_for`` ends the sentence about the missing world-space map."""
+    E = len(trans_list)
+    entries = (_lib.VolumeEditEntry * E)() if E else None
+    for e, (trans, label) in enumerate(zip(trans_list, target_labels)):
+        matrix = trans.matrix if isinstance(trans, Copy) else trans
+        if isinstance(matrix, Deform):
+            raise ValueError(f"{who}: entry {e} is a {trans!r}: a deformation's target rays depend on the image row, so it has no "
+                             f"world-space map to {what_for}")
+        entries[e].kind, entries[e].label = edit_kind(trans), label
+        if not isinstance(trans, Remove):
+            m = (matrix.detach().cpu().numpy() if torch.is_tensor(matrix) else np.asarray(matrix)).astype(np.float64)
+            if m.shape != (4, 4):
+                raise ValueError(f"{who}: entry {e} must be a 4 x 4 matrix, a Remove() or a Copy(matrix), got shape {m.shape}")
+            entries[e].m[:] = [float(v) for v in m.astype(np.float32)[:3, :4].reshape(-1)]
+    return entries
+
+
 def edit_volume(grid, trans_list, target_labels, keep_labels=None, rule="first", out=None):
     """The edit applied to the volume itself: ``grid`` (a ``field.LabelGrid`` or a ``field.BakedGrid``) resampled under ``trans_list``
     once -> ``{"grid", "source", "won", "claimed", "hits"}``, all on the device.  ``"grid"`` is a new object of ``grid``'s class over the
@@ -391,18 +419,7 @@ def edit_volume(grid, trans_list, target_labels, keep_labels=None, rule="first",
     for l in target_labels + list(keep if keep_labels is not None else ()):
         if not 0 <= l < C:
             raise ValueError(f"{who}: label {l} outside [0, {C})")
-    entries = (_lib.VolumeEditEntry * E)() if E else None
-    for e, (trans, label) in enumerate(zip(trans_list, target_labels)):
-        matrix = trans.matrix if isinstance(trans, Copy) else trans
-        if isinstance(matrix, Deform):
-            raise ValueError(f"{who}: entry {e} is a {trans!r}: a deformation's target rays depend on the image row, so it has no "
-                             "world-space map to resample the volume under (preview_frame / render_preview take it)")
-        entries[e].kind, entries[e].label = edit_kind(trans), label
-        if not isinstance(trans, Remove):
-            m = (matrix.detach().cpu().numpy() if torch.is_tensor(matrix) else np.asarray(matrix)).astype(np.float64)
-            if m.shape != (4, 4):
-                raise ValueError(f"{who}: entry {e} must be a 4 x 4 matrix, a Remove() or a Copy(matrix), got shape {m.shape}")
-            entries[e].m[:] = [float(v) for v in m.astype(np.float32)[:3, :4].reshape(-1)]
+    entries = pack_entries(who, trans_list, target_labels, "resample the volume under (preview_frame / render_preview take it)")
     src_cells = grid.cells if baked else None
     if out is not None:
         if out is not grid and (type(out) is not type(grid) or out.dims != grid.dims or out.C != C or not np.array_equal(out.lo, grid.lo)
@@ -428,6 +445,75 @@ def edit_volume(grid, trans_list, target_labels, keep_labels=None, rule="first",
     return res
 
 
+# ---- the trained field rendered through an edited volume (csrc/field_edit.hip; tests/_field_edit_restate.py states it in numpy)
+FIELD_POLICIES = {"evaluate": 0, "empty": 1}    # DMNERF_SKIP_OUTSIDE_* (include/dmnerf_hip.h)
+
+
+def field_edit_masks(C, target_labels, kinds, keep_labels=None):
+    """The accept masks of ``dmnerf_field_edit_filter`` -> ``4 (1 + E)`` 32-bit words (host integers): row 0 = ``own`` of
+    ``edit_label_sets``, row ``1 + e`` = ``per_entry[e]``, each packed by ``field.label_mask_words``."""
+    from . import field
+    own, per_entry = edit_label_sets(C, target_labels, kinds, keep_labels)
+    return [w for s in [own] + per_entry for w in field.label_mask_words(s, C)]
+
+
+class FieldEdit:
+    """What ``render.run_network_edited`` needs to render the TRAINED FIELD through an edited volume: ``source`` uint8 ``[dx, dy, dz]``
+    on the device (``edit_volume``'s: 0 the cell's own content, ``1 + e`` entry ``e`` of ``trans_list``, 255 nobody), its box (``lo``,
+    ``hi``, ``cell``, ``inv_cell``, ``dims``: ``field.LabelGrid``'s arithmetic), the entries, the accept masks and two policies.
+
+    A sample in a cell owned by 0 is evaluated at its own point, one owned by ``1 + e`` at the point entry ``e``'s matrix carries it back
+    to (the matrix maps the edited scene to the trained one, as in ``edit_volume``; no inverse is taken), one owned by nobody not at all.
+    ``outside`` / ``unowned`` (``"evaluate"``: owner 0, ``"empty"``: nobody) say what a sample outside the box and one in a cell of
+    byte 255 get.  Behind the network the per-sample label decides whether the row counts (``masks``, ``(1 + E) x 4`` words, the sets
+    of ``_preview_sets``): owner 0 accepts ``keep`` without the labels of MOVE and REMOVE entries, owner ``1 + e`` accepts
+    ``{target_labels[e]} & keep``.
+
+    ``source`` may be overwritten in place (an ``edit_volume`` of the same entries into it): a captured render follows it on replay.
+    ``C`` is the number of labels, ``ins_num + 1`` of the models it is rendered with."""
+
+    def __init__(self, source, lo, hi, trans_list, target_labels, C, keep_labels=None, outside="evaluate", unowned="evaluate", volume=None):
+        from . import field
+        who = "FieldEdit"
+        _lib.require_gpu(source)
+        if source.dtype != torch.uint8 or source.dim() != 3:
+            raise ValueError(f"{who}: source must be uint8 [dx, dy, dz], got {source.dtype} {tuple(source.shape)}")
+        self.C = int(C)
+        if not 1 <= self.C <= field.MAX_LABELS:
+            raise ValueError(f"{who}: C must be in [1, {field.MAX_LABELS}], got {self.C}")
+        for name, policy in (("outside", outside), ("unowned", unowned)):
+            if policy not in FIELD_POLICIES:
+                raise ValueError(f"{who}: {name} must be 'evaluate' or 'empty', got {policy!r}")
+        self.dims = field._dims3(tuple(source.shape))
+        self.lo, self.hi, self.cell, self.inv_cell = field._box(who, lo, hi, self.dims)
+        self.source, self.outside, self.unowned, self.volume = source, outside, unowned, volume
+        trans_list, self.target_labels = list(trans_list), [int(l) for l in target_labels]
+        if len(trans_list) != len(self.target_labels):
+            raise ValueError(f"{who}: {len(self.target_labels)} target labels for {len(trans_list)} edits")
+        self.E = len(trans_list)
+        if self.E > MAX_VOLUME_EDITS:
+            raise ValueError(f"{who}: {self.E} edits, at most {MAX_VOLUME_EDITS}")
+        self.keep_labels = None if keep_labels is None else sorted({int(l) for l in keep_labels})
+        for l in self.target_labels + (self.keep_labels or []):
+            if not 0 <= l < self.C:
+                raise ValueError(f"{who}: label {l} outside [0, {self.C})")
+        self.kinds = [edit_kind(trans) for trans in trans_list]
+        self.entries = pack_entries(who, trans_list, self.target_labels, "carry a sample back under")
+        self.masks = (ctypes.c_uint32 * (4 * (1 + self.E)))(*field_edit_masks(self.C, self.target_labels, self.kinds, self.keep_labels))
+
+    @classmethod
+    def from_volume(cls, grid, trans_list, target_labels, keep_labels=None, rule="first", outside="evaluate", unowned="evaluate"):
+        """``edit_volume(grid, trans_list, target_labels, keep_labels, rule)`` and its ``source``; the whole result stays as ``.volume``."""
+        res = edit_volume(grid, trans_list, target_labels, keep_labels=keep_labels, rule=rule)
+        return cls(res["source"], grid.lo, grid.hi, trans_list, target_labels, grid.C, keep_labels, outside, unowned, volume=res)
+
+    @classmethod
+    def from_source(cls, source, lo, hi, trans_list, target_labels, C=None, keep_labels=None, outside="evaluate", unowned="evaluate"):
+        """Wraps a given byte volume over the box ``[lo, hi)``.  ``C``: the number of labels (default: the most a byte volume names)."""
+        from . import field
+        return cls(source, lo, hi, trans_list, target_labels, field.MAX_LABELS if C is None else C, keep_labels, outside, unowned)
+
+
 def _render(H, W, K, pose, edits, models, args, frame_kw):
     fr = D.ManipulationFrameRenderer(H, W, K, pose, edits, models, args, **frame_kw)
     for c in range(fr.n_chunks):
@@ -439,7 +525,7 @@ MAP_NAMES = ("rgb", "ins", "tar_rgb", "tar_ins")
 
 
 def manipulate_demo_path(view_poses, hwk, models, args, objs, objs_trans, ins_rgbs, color_dict, ins_map, keep_maps=False,
-                         products=None, keep_labels=None, skip=None, skip_levels=("coarse", "fine"), **frame_kw):
+                         products=None, keep_labels=None, skip=None, skip_levels=("coarse", "fine"), field_edit=None, **frame_kw):
     """The pose loop of ``manipulator_demo`` (networks/manipulator.py:384-488) without its file output: per view ``i`` every
     object of ``objs`` is edited at once -- ``obj['mani_mode'] == 'deform'``: ``Deform(obj['deform_func'], i)``, otherwise the
     rigid ``objs_trans[obj['obj_name']][i]['transformation']`` -- with ``target_labels = [obj['tar_id'] ...]`` (:395, :437), one
@@ -453,8 +539,16 @@ def manipulate_demo_path(view_poses, hwk, models, args, objs, objs_trans, ins_rg
 
     Extension: a ``'transformation'`` of ``objs_trans`` may be a ``Remove()`` or a ``Copy(matrix)``, and ``keep_labels`` shows
     only the objects of that set (isolate); ``objs`` may then be empty.  ``skip=`` a ``field.SkipGrid`` / ``skip_levels=``: every
-    frame skips empty space (``ManipulationFrameRenderer(skip=)``); moves, ``Deform``, ``Remove``, ``Copy`` and ``keep_labels`` work with it."""
+    frame skips empty space (``ManipulationFrameRenderer(skip=)``); moves, ``Deform``, ``Remove``, ``Copy`` and ``keep_labels`` work with it.
+    ``field_edit=`` a ``FieldEdit``: every view is the field-edit render of that one edited volume (``ManipulationFrameRenderer(field_edit=)``);
+    the edits are the ``FieldEdit``'s, so ``objs`` must be empty, and it cannot be combined with ``keep_labels=`` or ``skip=``."""
     H, W, K = hwk
+    if field_edit is not None:
+        if len(objs):
+            raise ValueError("manipulate_demo_path: field_edit= carries the edits itself; objs must be empty")
+        if keep_labels is not None or skip is not None:
+            raise ValueError("manipulate_demo_path: field_edit= cannot be combined with keep_labels= (the keep set is the FieldEdit's) or skip=")
+        frame_kw = dict(frame_kw, field_edit=field_edit)
     if keep_labels is not None:
         frame_kw = dict(frame_kw, keep_labels=keep_labels)
     if skip is not None:

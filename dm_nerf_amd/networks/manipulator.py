@@ -247,3 +247,33 @@ def manipulator(position_embedder, view_embedder, model_coarse, model_fine, ori_
     ori_raw, _, _, _ = exchanger(ori_raw, tar_raws, p.ori_ins_accum, p.tar_ins_accums, args.target_labels)
     final_rgb, _, _, final_ins = manipulator_render(ori_raw, ori_z, ori_rays[1])
     return final_rgb, final_ins, p.tar_rgb, p.tar_ins_accum
+
+
+def edited_field(model_coarse, model_fine, rays, args, edit, u=None, counts=None):
+    """One chunk of the FIELD-EDIT render (extension; DESIGN.md 8a, "The field-edit route") -> ``(rgb [N,3], ins [N,C], depth [N])``:
+    the trained field seen through the edited volume of ``edit`` (an ``editing.FieldEdit``), one network evaluation per sample.
+
+    ``manipulator_z`` -> ``render.run_network_edited`` on ``model_coarse`` -> ``manipulator_render`` -> ``helpers.importance_resample``
+    with the ONE draw ``u [N, N_importance]`` (drawn here with ``torch.rand`` if not given) -> ``run_network_edited`` on ``model_fine``
+    over the merged depths -> ``manipulator_render``.  Two sparse network launches, whatever the number of edits.  Both compositing
+    calls use the ORIGINAL ray's ``z`` and ``|d|``, as the exchanger route does: a carried-back ray only says where the network is asked.
+
+    A render with its own contract, not ``manipulator()`` bit for bit: ownership is decided per cell by ``edit_volume`` (nearest cell, the
+    cell centre's label) and the exchanger's accumulated-label conditions are not applied.  ``args.mfma_split``: None or ``"f16x2"``
+    (``"bf16x3"`` and another network shape than 8 x 256 raise).  ``counts``: ``run_network_edited``'s.  Nothing reaches the host."""
+    from .. import weights
+    from .render import run_network_edited
+    split = weights.split_mode(args)
+    rays_o, rays_d = rays
+    dev = rays_d.device
+    N = rays_d.shape[0]
+    n_imp = int(args.N_importance)
+    u = torch.rand([N, n_imp], device=dev) if u is None else _lib.f32(u)
+    with torch.no_grad():
+        z = manipulator_z(N, args.near, args.far, args.N_samples, dev)
+        raw = run_network_edited(model_coarse, rays_o, rays_d, z, edit, split=split, counts=counts)
+        _, w, _, _ = manipulator_render(raw, z, rays_d)
+        z_full = helpers.importance_resample(z, w, n_imp, u=u)
+        raw = run_network_edited(model_fine, rays_o, rays_d, z_full, edit, split=split, counts=counts)
+        rgb, _, depth, ins = manipulator_render(raw, z_full, rays_d)
+    return rgb, ins, depth

@@ -155,6 +155,73 @@ def run_network_skip(model, rays_o, rays_d, z_vals, grid, split=None, counts=Non
     return raw
 
 
+EDITED_WORDS = ("no sparse network kernel", "the sparse network kernels exist", "render in smaller chunks")
+
+
+def run_network_edited(model, rays_o, rays_d, z_vals, edit, split=None, counts=None, _stages=None):
+    """The trained field seen through an edited volume: ``raw [N,S,4+C]`` with ONE network evaluation per sample, wherever ``edit`` (an
+    ``editing.FieldEdit``) says the sample's content comes from.
+
+    ``dmnerf_field_edit_select``: the owner of every sample's cell of ``edit.source`` -- 0: its own point, ``1 + e``: the point carried
+    back by entry ``e``'s matrix, 255: nobody, the row becomes the empty row ``E = (0, 0, 0, 0 | 0, .., 0, 1)`` -- with the ray of every
+    evaluated sample and the ascending selection; then ``dmnerf_mlp_fwd_rays_sel`` (``split`` None) or ``dmnerf_mlp_fwd_rays_f16_sel``
+    (``"f16x2"``) over the selection as ``N S`` one-sample rays; then ``dmnerf_field_edit_filter``: a row whose own label (first maximum
+    of its C logits) is not in its owner's accept set becomes the empty row too -- the exchanger's per-sample rule.  The rows keep the
+    ORIGINAL ray's place, so the compositing runs on the original ``z`` and ``|d|``.
+
+    There is no dense detour: ``split == "bf16x3"`` and a network shape other than 8 x 256 raise ``ValueError``, a volume on another
+    device ``RuntimeError``, ``N S >= 2^31`` ``ValueError``.  ``counts``: optional int64 ``[2]`` device tensor, += (samples evaluated,
+    samples), as in ``run_network_skip``.  Nothing reaches the host: after one warm-up call (``empty_row``) it can be captured in a
+    graph and follows ``edit.source`` on replay.  ``_stages`` (tests): a dict that receives ``owner``, ``o_w``, ``d_w``, ``sel``,
+    ``count``, ``kept`` and ``raw_net``, a copy of ``raw`` before the filter."""
+    from .. import editing
+    who = "run_network_edited"
+    if not isinstance(edit, editing.FieldEdit):
+        raise TypeError(f"{who}: edit must be an editing.FieldEdit")
+    split = split or None
+    if split not in (None, "f16x2"):
+        raise ValueError(f"{who}: {EDITED_WORDS[0]} for args.mfma_split = {split!r} (f32 and 'f16x2' only)")
+    if not model._fused_ok():
+        raise ValueError(f"{who}: {EDITED_WORDS[1]} for the 8 x 256 network only")
+    N, S = z_vals.shape
+    M, C = N * S, model.ins_num + 1
+    if M >= 2 ** 31:
+        raise ValueError(f"{who}: {M} samples do not fit the int32 selection; {EDITED_WORDS[2]}")
+    if edit.C != C:
+        raise ValueError(f"{who}: the FieldEdit was made for C = {edit.C} labels, the model has ins_num + 1 = {C} (FieldEdit.from_source(..., C=))")
+    rays_o, rays_d, z = _lib.f32(rays_o.reshape(-1, 3)), _lib.f32(rays_d.reshape(-1, 3)), _lib.f32(z_vals)
+    _lib.require_gpu(rays_o, rays_d, z)
+    dev = z.device
+    if edit.source.device != dev:
+        raise RuntimeError(f"{who}: the source volume lives on another device than the rays")
+    if counts is not None:
+        _lib.require_gpu(counts)
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (2,) or counts.device != dev or not counts.is_contiguous():
+            raise ValueError(f"{who}: counts must be a contiguous int64 [2] tensor on the rays' device")
+    raw = torch.empty(N, S, 4 + C, dtype=torch.float32, device=dev)
+    if M == 0:
+        return raw
+    import ctypes
+    sel, owner, work = select_buffers(M, dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    o_w, d_w = torch.empty(M, 3, dtype=torch.float32, device=dev), torch.empty(M, 3, dtype=torch.float32, device=dev)
+    fill = empty_row(C, dev)
+    f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
+    _lib.launch("dmnerf_field_edit_select", edit.source, f3(edit.lo), f3(edit.inv_cell), (ctypes.c_int * 3)(*edit.dims),
+                editing.FIELD_POLICIES[edit.outside], editing.FIELD_POLICIES[edit.unowned], edit.entries, edit.E, C, rays_o, rays_d, z, N, S,
+                owner, o_w, d_w, sel, count, work, raw, fill, counts)
+    if split == "f16x2":
+        _lib.launch("dmnerf_mlp_fwd_rays_f16_sel", model.blob_f16(), model.ins_num, o_w, d_w, z, M, 1, sel, count, raw)
+    else:
+        _lib.launch("dmnerf_mlp_fwd_rays_sel", model.blob(), model.ins_num, 0, o_w, d_w, z, M, 1, sel, count, raw)
+    kept = None
+    if _stages is not None:
+        kept = torch.empty(1 + edit.E, dtype=torch.int64, device=dev)
+        _stages.update(owner=owner, o_w=o_w, d_w=d_w, sel=sel, count=count, kept=kept, raw_net=raw.clone())
+    _lib.launch("dmnerf_field_edit_filter", raw, owner, M, C, edit.masks, edit.E, fill, kept)
+    return raw
+
+
 def check_draws(t_rand, u, N, S, n_imp, perturb, dev):
     """The two random tensors of one ``dm_nerf`` call, validated before raw pointers reach the kernels.
     ``perturb > 0``: ``t_rand [N,S]`` (render.py:46) then ``u [N,n_imp]`` (helpers.py:135), drawn here in the reference's

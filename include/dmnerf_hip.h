@@ -861,6 +861,41 @@ int32_t dmnerf_volume_edit(const uint8_t* d_labels, const float* d_cells, const 
                            uint8_t* d_out_labels, float* d_out_cells, uint8_t* d_out_source, int64_t* d_won, int64_t* d_claimed,
                            int64_t* d_hits, void* stream);
 
+/* The trained field rendered through an edited volume (csrc/field_edit.hip; networks/render.py run_network_edited): the `source`
+ * volume of dmnerf_volume_edit says whose content stands in every cell of the edited scene, so every sample needs ONE network
+ * evaluation at a known place.  The network between the two entries is dmnerf_mlp_fwd_rays_sel / .._f16_sel called with
+ * (d_o_w, d_d_w, d_z, N = N * S, S = 1, d_sel, d_count).  Additive (the ABI version stays).
+ *   dmnerf_field_edit_select: dmnerf_skip_select_fill over the byte volume d_source [dx,dy,dz] instead of a bit grid.  lo, inv_cell,
+ *     dims: HOST arrays of the box (dmnerf_skip_grid's values); entries: E <= 32 HOST dmnerf_volume_edit_entry, the list the volume
+ *     was edited with.  Sample m = n * S + s: p = o + d * z and c_a = floorf((p_a - lo_a) * inv_cell_a) with dmnerf_skip_select's
+ *     arithmetic, operation for operation (a NaN point is outside).  Its owner: inside the box the byte b = d_source[cell], read as 255
+ *     if b > E or entry b - 1 is a REMOVE; b == 255 gives the `unowned` policy, a point outside the box the `outside` policy
+ *     (DMNERF_SKIP_OUTSIDE_EVALUATE: owner 0, DMNERF_SKIP_OUTSIDE_EMPTY: owner 255).
+ *       owner 255: not evaluated; row m of d_rows [N*S, 4 + C] becomes d_fill_row [4 + C] (d_rows may be NULL: no fill).
+ *       owner 0: evaluated on its own ray: d_o_w[m] = o, d_d_w[m] = d, copied bit for bit.
+ *       owner 1 + e: evaluated on the ray carried back into the trained scene, every f32 operation rounded on its own:
+ *         d_o_w[m]_a = ((m_a0 o_x + m_a1 o_y) + m_a2 o_z) + m_a3,  d_d_w[m]_a = (m_a0 d_x + m_a1 d_y) + m_a2 d_z (no translation).
+ *     Outputs: d_owner [N*S] uint8; d_o_w, d_d_w [N*S,3], written for evaluated samples only; d_sel = the evaluated m in ascending
+ *     order (prefix sums: the same list every run), d_count [1] their number, on the device; d_work: scratch of
+ *     dmnerf_skip_select_work_ints(N * S) int32; d_totals (may be NULL): [2] int64, += (*d_count, N * S), as in
+ *     dmnerf_skip_select_fill.  tests/_field_edit_restate.py states it in numpy.
+ *   dmnerf_field_edit_filter: one lane per row of d_raw [M, 4 + C].  A row whose d_owner[m] is 255 is left alone.  Otherwise its label
+ *     is the first maximum over its C logits (dmnerf_label_cells' argmax with its tie and NaN rules, no sigma threshold); if bit
+ *     label & 31 of masks[4 * owner + (label >> 5)] is clear the row is overwritten with d_fill_row [4 + C].  masks: (1 + E) x 4 HOST
+ *     words (dmnerf_skip_grid_from_labels' packing).  d_kept (may be NULL): [1 + E] int64, written whole by the call: the rows kept per
+ *     owner (ballots and popcounts into an LDS table, integer atomics: the same numbers every run).  Rows need no alignment.
+ *   Refused with DMNERF_E_ARG before anything is launched: a null pointer, N < 0, S < 1, N * S (M) >= 2^31, dims < 1 or dx dy dz >= 2^31,
+ *   C outside 1..128, E outside 0..32, an unknown policy, an entry whose kind is not 0..2 or whose label is outside [0, C).  N * S == 0
+ *   (M == 0) returns 0 without a launch (nothing is written, *d_count included).  No float atomics, no allocation, no synchronisation: the chain can be
+ *   captured in a graph and reads d_source anew on every replay.  Both return the status as int32_t, as dmnerf_volume_edit does. */
+int32_t dmnerf_field_edit_select(const uint8_t* d_source, const float lo[3], const float inv_cell[3], const int dims[3], int outside,
+                                 int unowned, const dmnerf_volume_edit_entry* entries, int E, int C, const float* d_rays_o,
+                                 const float* d_rays_d, const float* d_z, int64_t N, int S, uint8_t* d_owner, float* d_o_w,
+                                 float* d_d_w, int* d_sel, int* d_count, int* d_work, float* d_rows, const float* d_fill_row,
+                                 int64_t* d_totals, void* stream);
+int32_t dmnerf_field_edit_filter(float* d_raw, const uint8_t* d_owner, int64_t M, int C, const uint32_t* masks, int E,
+                                 const float* d_fill_row, int64_t* d_kept, void* stream);
+
 /* The two renders above on the OPT-IN split-f16 ("f16x2") kernels (csrc/mlp_f16_density.hip, csrc/mlp_f16_sparse.hip; the body of
  * csrc/mlp_f16_impl.h with template flags).  Additive (the ABI version stays).
  *   f16 density blob: dmnerf_blob_f16_density_words 32-bit words = [the f16 blob's 4096-float bias table | its 120 trunk groups
