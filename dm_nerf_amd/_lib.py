@@ -290,6 +290,14 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def box_args(grid):
+    """The box of a grid volume (anything with ``lo``, ``cell``, ``inv_cell [3]`` and ``dims``: ``field.SkipGrid`` / ``LabelGrid`` /
+    ``BakedGrid``, ``editing.FieldEdit``) as the host arrays the entries take -> ``(lo, cell, inv_cell, dims)``, ctypes ``float[3]`` x 3
+    and ``int[3]``."""
+    f3 = lambda v: (c_float * 3)(*[float(x) for x in v])
+    return f3(grid.lo), f3(grid.cell), f3(grid.inv_cell), (c_int * 3)(*grid.dims)
+
+
 def _arg(a):
     """One argument as ctypes takes it: a tensor's / host array's address, a struct by reference, anything else (numbers,
     None = null, ``byref`` of a scalar, ctypes arrays) as it is.  No validation: that is the caller's."""

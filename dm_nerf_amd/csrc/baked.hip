@@ -7,7 +7,7 @@
 //                         segment, and the number of segments.
 //
 // One lane per pixel.  Every set walks the volume exactly as label_trace_kernel does (the same clip, start cell, cell sequence and t
-// values: label_walk.h and the same statements, f32 operations rounded one by one), but does not stop at its first counted cell:
+// values: the walk of grid_volume.h, f32 operations rounded one by one), but does not stop at its first counted cell:
 //
 //   segment    a counted cell of set r gives t_in = the walk's current t, t_out = the next plane crossing tmax_a if tmax_a < t_exit,
 //              else t_exit, and len = (t_out - t_in) * |d_r| with |d| = sqrtf(d0 d0 + d1 d1 + d2 d2), summed in that order.  The
@@ -32,7 +32,7 @@
 
 #include "../../include/dmnerf_hip.h"
 #include "common.h"
-#include "label_walk.h"
+#include "grid_volume.h"
 
 namespace {
 
@@ -48,91 +48,60 @@ struct BakedMasks {
 // cells visited and is set to the bound when the walk ends; `label` is UNLABELLED while nothing is pending.  (Integers in vector
 // registers, not flags: a flag per set and lane is a pair of scalar registers, and four sets of them do not fit.)
 struct Walk {
-    float o0, o1, o2, d0, d1, d2, inv0, inv1, inv2, t_exit, t, norm;
+    WalkRay ray;
+    float t_exit, t, norm;
     int c0, c1, c2, it;
     float t_in, t_out;
     int g, label;
 };
 
-__device__ __forceinline__ void clip_axis(float lo, float hi, float o, float d, float& inv, float& t_enter, float& t_exit, bool& miss) {
-    if (d == 0.f) {
-        miss = miss || !(lo <= o && o < hi);
-    } else {
-        inv = __fdiv_rn(1.f, d);
-        const float t0 = __fmul_rn(__fsub_rn(lo, o), inv), t1 = __fmul_rn(__fsub_rn(hi, o), inv);
-        t_enter = nan_max(t_enter, nan_min(t0, t1));
-        t_exit = nan_min(t_exit, nan_max(t0, t1));
-    }
-}
-
-__device__ __forceinline__ int start_cell(float o, float d, float t_enter, float lo, float inv_cell, int dim) {
-    const float f = floorf(__fmul_rn(__fsub_rn(__fadd_rn(o, __fmul_rn(d, t_enter)), lo), inv_cell));
-    return f >= 0.f ? (f < (float)dim ? (int)f : dim - 1) : 0;                       // (a NaN: 0)
-}
-
-// label_trace_kernel's clip and start cell
-__device__ __forceinline__ void walk_init(Walk& S, const TraceGrid& G, const float* __restrict__ o, const float* __restrict__ d,
+// the trace's clip and start cell (grid_volume.h)
+__device__ __forceinline__ void walk_init(Walk& S, const GridBox& G, const float* __restrict__ o, const float* __restrict__ d,
                                           float t_near, float t_far, int max_cells) {
     const float inf = __builtin_huge_valf();
-    S.o0 = o[0]; S.o1 = o[1]; S.o2 = o[2];
-    S.d0 = d[0]; S.d1 = d[1]; S.d2 = d[2];
-    S.norm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(S.d0, S.d0), __fmul_rn(S.d1, S.d1)), __fmul_rn(S.d2, S.d2)));
+    WalkRay& r = S.ray;
+    r.o0 = o[0]; r.o1 = o[1]; r.o2 = o[2];
+    r.d0 = d[0]; r.d1 = d[1]; r.d2 = d[2];
+    S.norm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(r.d0, r.d0), __fmul_rn(r.d1, r.d1)), __fmul_rn(r.d2, r.d2)));
     const float hi0 = plane_of(G.lo[0], G.cell[0], G.dims[0]), hi1 = plane_of(G.lo[1], G.cell[1], G.dims[1]),
                 hi2 = plane_of(G.lo[2], G.cell[2], G.dims[2]);
     float t_enter = t_near;
     bool miss = false;
     S.t_exit = t_far;
-    S.inv0 = inf; S.inv1 = inf; S.inv2 = inf;
-    clip_axis(G.lo[0], hi0, S.o0, S.d0, S.inv0, t_enter, S.t_exit, miss);
-    clip_axis(G.lo[1], hi1, S.o1, S.d1, S.inv1, t_enter, S.t_exit, miss);
-    clip_axis(G.lo[2], hi2, S.o2, S.d2, S.inv2, t_enter, S.t_exit, miss);
-    S.c0 = start_cell(S.o0, S.d0, t_enter, G.lo[0], G.inv_cell[0], G.dims[0]);
-    S.c1 = start_cell(S.o1, S.d1, t_enter, G.lo[1], G.inv_cell[1], G.dims[1]);
-    S.c2 = start_cell(S.o2, S.d2, t_enter, G.lo[2], G.inv_cell[2], G.dims[2]);
+    r.inv0 = inf; r.inv1 = inf; r.inv2 = inf;
+    walk_clip_axis(G.lo[0], hi0, r.o0, r.d0, r.inv0, t_enter, S.t_exit, miss);
+    walk_clip_axis(G.lo[1], hi1, r.o1, r.d1, r.inv1, t_enter, S.t_exit, miss);
+    walk_clip_axis(G.lo[2], hi2, r.o2, r.d2, r.inv2, t_enter, S.t_exit, miss);
+    S.c0 = walk_start_cell(r.o0, r.d0, t_enter, G.lo[0], G.inv_cell[0], G.dims[0]);
+    S.c1 = walk_start_cell(r.o1, r.d1, t_enter, G.lo[1], G.inv_cell[1], G.dims[1]);
+    S.c2 = walk_start_cell(r.o2, r.d2, t_enter, G.lo[2], G.inv_cell[2], G.dims[2]);
     S.t = t_enter;
     S.it = (miss || !(t_enter < S.t_exit)) ? max_cells : 0;
     S.t_in = 0.f; S.t_out = 0.f;
     S.g = 0; S.label = UNLABELLED;
 }
 
-// label_trace_kernel's walk from where the set stands to its next counted cell, which becomes the pending segment; the set is then
-// already one step further.  Without a further counted cell the set ends with nothing pending.
-__device__ __forceinline__ void walk_advance(Walk& S, const TraceGrid& G, const uint8_t* __restrict__ labels, int C, uint32_t m0, uint32_t m1,
+// The trace's walk from where the set stands to its next counted cell, which becomes the pending segment; the set is then already
+// one step further.  Without a further counted cell the set ends with nothing pending.
+__device__ __forceinline__ void walk_advance(Walk& S, const GridBox& G, const uint8_t* __restrict__ labels, int C, uint32_t m0, uint32_t m1,
                                              uint32_t m2, uint32_t m3, int max_cells) {
-    const float inf = __builtin_huge_valf();
-    const int dx = G.dims[0], dy = G.dims[1], dz = G.dims[2];
-    const int up0 = S.d0 > 0.f, up1 = S.d1 > 0.f, up2 = S.d2 > 0.f;
     S.label = UNLABELLED;
     while (S.it < max_cells) {
         ++S.it;
-        const int g = (S.c0 * dy + S.c1) * dz + S.c2;                            // 0 <= c_a < dims_a: always inside the volume
+        const int g = (S.c0 * G.dims[1] + S.c1) * G.dims[2] + S.c2;             // 0 <= c_a < dims_a: always inside the volume
         const uint32_t l = labels[g];
-        const uint32_t q = l >> 5;
-        const uint32_t word = q == 0 ? m0 : q == 1 ? m1 : q == 2 ? m2 : q == 3 ? m3 : 0u;
-        const bool counted = l < (uint32_t)C && ((word >> (l & 31)) & 1u);
-        const float tm0 = S.d0 == 0.f ? inf : __fmul_rn(__fsub_rn(plane_of(G.lo[0], G.cell[0], S.c0 + up0), S.o0), S.inv0);
-        const float tm1 = S.d1 == 0.f ? inf : __fmul_rn(__fsub_rn(plane_of(G.lo[1], G.cell[1], S.c1 + up1), S.o1), S.inv1);
-        const float tm2 = S.d2 == 0.f ? inf : __fmul_rn(__fsub_rn(plane_of(G.lo[2], G.cell[2], S.c2 + up2), S.o2), S.inv2);
-        int axis = 0;
-        float tm = tm0;
-        if (tm1 < tm) { axis = 1; tm = tm1; }
-        if (tm2 < tm) { axis = 2; tm = tm2; }
-        const bool on = tm < S.t_exit;
+        const bool in_set = mask_bit(m0, m1, m2, m3, l);
+        const bool counted = l < (uint32_t)C && in_set;
+        int axis;
+        float tm;
+        const bool on = walk_step(G, S.ray, S.c0, S.c1, S.c2, S.t_exit, &axis, &tm);
         if (counted) {
             S.t_in = S.t;
             S.t_out = on ? tm : S.t_exit;
             S.g = g;
             S.label = (int)l;
         }
-        if (on) {
-            S.t = tm > S.t ? tm : S.t;
-            S.c0 += axis == 0 ? (up0 ? 1 : -1) : 0;
-            S.c1 += axis == 1 ? (up1 ? 1 : -1) : 0;
-            S.c2 += axis == 2 ? (up2 ? 1 : -1) : 0;
-            if (S.c0 < 0 || S.c0 >= dx || S.c1 < 0 || S.c1 >= dy || S.c2 < 0 || S.c2 >= dz) S.it = max_cells;
-        } else {
-            S.it = max_cells;
-        }
+        if (!on || walk_apply(G, S.ray, axis, tm, S.c0, S.c1, S.c2, S.t)) S.it = max_cells;
         if (counted) break;
     }
 }
@@ -140,7 +109,7 @@ __device__ __forceinline__ void walk_advance(Walk& S, const TraceGrid& G, const 
 __device__ __forceinline__ float sigmoid_of(float x) { return __fdiv_rn(1.f, __fadd_rn(1.f, expf(-x))); }
 
 template <int R>
-__global__ __launch_bounds__(BLOCK) void baked_render_kernel(const uint8_t* __restrict__ labels, const float4* __restrict__ cells, TraceGrid G,
+__global__ __launch_bounds__(BLOCK) void baked_render_kernel(const uint8_t* __restrict__ labels, const float4* __restrict__ cells, GridBox G,
                                                              int C, const float* __restrict__ rays, int64_t N, BakedMasks M, float t_near,
                                                              float t_far, float stop, float* __restrict__ out_rgb,
                                                              float* __restrict__ out_depth, float* __restrict__ out_acc,
@@ -202,23 +171,20 @@ extern "C" int dmnerf_baked_render(const uint8_t* d_labels, const float* d_cells
                                    const float inv_cell[3], const int dims[3], int C, const float* d_rays, int R, int64_t N,
                                    const uint32_t* masks, float t_near, float t_far, float stop, float* d_rgb, float* d_depth, float* d_acc,
                                    uint8_t* d_label, uint8_t* d_source, int32_t* d_nseg, void* stream) {
-    if (!lo || !cell || !inv_cell || !dims || !masks) return dmn_fail(DMNERF_E_ARG, "baked_render: null pointer");
+    if (!lo || !cell || !inv_cell || !dims || !masks) return dmn_fail(DMNERF_E_ARG, "baked_render: null pointer");     // (the host arrays: before N, as ever)
     if (N < 0) return dmn_fail(DMNERF_E_ARG, "baked_render: bad N=%lld", (long long)N);
     if (R < 1 || R > MAX_SETS) return dmn_fail(DMNERF_E_ARG, "baked_render: R=%d outside 1..%d", R, MAX_SETS);
-    if (C < 1 || C > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "baked_render: C=%d outside 1..%d", C, DMNERF_MAX_LOGITS);
+    if (int rc = dmn_check_labels("baked_render", C)) return rc;
     if (!(stop >= 0.f)) return dmn_fail(DMNERF_E_ARG, "baked_render: stop %g must be >= 0", (double)stop);
-    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1)
-        return dmn_fail(DMNERF_E_ARG, "baked_render: bad dims %d x %d x %d", dims[0], dims[1], dims[2]);
-    const int64_t total = (int64_t)dims[0] * dims[1] * dims[2];
-    if (total >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "baked_render: %lld cells do not fit int32", (long long)total);
+    GridBox G;
+    int64_t total;
+    if (int rc = dmn_grid_given("baked_render", lo, cell, inv_cell, dims, &G, &total)) return rc;
     const int64_t nb = (N + BLOCK - 1) / BLOCK;
     if (nb > 0x7fffffffLL) return dmn_fail(DMNERF_E_ARG, "baked_render: %lld rays is too many for one launch", (long long)N);
     if (N == 0) return DMNERF_OK;
     if (!d_labels || !d_cells || !d_rays || !d_rgb || !d_depth || !d_acc || !d_label || !d_source || !d_nseg)
         return dmn_fail(DMNERF_E_ARG, "baked_render: null pointer");
     if ((uintptr_t)d_cells & 15) return dmn_fail(DMNERF_E_ARG, "baked_render: d_cells must be 16-byte aligned");
-    TraceGrid G;
-    for (int a = 0; a < 3; ++a) { G.lo[a] = lo[a]; G.cell[a] = cell[a]; G.inv_cell[a] = inv_cell[a]; G.dims[a] = dims[a]; }
     BakedMasks M;
     for (int q = 0; q < MAX_SETS * 4; ++q) M.w[q] = q < R * 4 ? masks[q] : 0u;
     const float4* cells4 = reinterpret_cast<const float4*>(d_cells);

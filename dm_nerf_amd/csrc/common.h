@@ -1,7 +1,7 @@
 // common.h -- what the host side of every translation unit shares: error plumbing, the launch of kernels with large dynamic
-// LDS, and the two ends of a ray / sample MLP entry: its preamble (range checks, the empty batch, the null-pointer test) and its
-// tail (the grid of the MLP kernels and the launch of the kernel instantiation that the network's logit count selects).  An
-// entry is: preamble, fill the kernel's argument struct, tail.
+// LDS, the checks of a grid volume and of an edit list, and the two ends of a ray / sample MLP entry: its preamble (range
+// checks, the empty batch, the null-pointer test) and its tail (the grid of the MLP kernels and the launch of the kernel
+// instantiation that the network's logit count selects).  An entry is: preamble, fill the kernel's argument struct, tail.
 #pragma once
 #include <atomic>
 #include <cstdarg>
@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/dmnerf_hip.h"
+#include "grid_volume.h"
 
 // Records a printf-style message for dmnerf_last_error() and returns `code`.
 int dmn_fail(int code, const char* fmt, ...);
@@ -86,6 +87,55 @@ inline bool dmn_batch_given(int* rc, const char* who, int64_t n, std::initialize
 inline bool dmn_rays_given(int* rc, const char* who, int ins_num, int64_t N, int S, bool sel, std::initializer_list<const void*> ptrs) {
     return !(*rc = dmn_check_rays(who, ins_num, N, S, sel)) && dmn_batch_given(rc, who, N, ptrs);
 }
+// ---- argument checks of the entries that take a grid volume (grid_volume.h) or a list of volume edits ----------------
+// Every refusal is "<who>: ..." in the entry's name.  The label count of a volume: 1 .. DMNERF_MAX_LOGITS.
+inline int dmn_check_labels(const char* who, int C) {
+    return C >= 1 && C <= DMNERF_MAX_LOGITS ? DMNERF_OK : dmn_fail(DMNERF_E_ARG, "%s: C=%d outside 1..%d", who, C, DMNERF_MAX_LOGITS);
+}
+// The two checks of dims, apart for the entries that check something else in between: every dim >= 1 ...
+inline int dmn_grid_dims(const char* who, const int dims[3]) {
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return dmn_fail(DMNERF_E_ARG, "%s: bad dims %d x %d x %d", who, dims[0], dims[1], dims[2]);
+    return DMNERF_OK;
+}
+// ... and fewer than 2^31 cells (a cell index is an int32 on the device); -> *total.
+inline int dmn_grid_cells(const char* who, const int dims[3], int64_t* total) {
+    *total = (int64_t)dims[0] * dims[1] * dims[2];
+    if (*total >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: %lld cells do not fit int32", who, (long long)*total);
+    return DMNERF_OK;
+}
+// A box given as host arrays: none of them null (cell may be, for an entry that takes none: the box then carries 0), dims, cells, and
+// the kernel argument filled in.
+inline int dmn_grid_given(const char* who, const float* lo, const float* cell, const float* inv_cell, const int* dims, GridBox* box, int64_t* total) {
+    if (!lo || !inv_cell || !dims) return dmn_fail(DMNERF_E_ARG, "%s: null host array", who);
+    if (int rc = dmn_grid_dims(who, dims)) return rc;
+    if (int rc = dmn_grid_cells(who, dims, total)) return rc;
+    for (int a = 0; a < 3; ++a) {
+        box->lo[a] = lo[a];
+        box->cell[a] = cell ? cell[a] : 0.f;
+        box->inv_cell[a] = inv_cell[a];
+        box->dims[a] = dims[a];
+    }
+    return DMNERF_OK;
+}
+// A list of E volume edits: its length (entries == NULL with E > 0 is refused where need_entries) ...
+inline int dmn_edit_count_given(const char* who, int E, const dmnerf_volume_edit_entry* entries, bool need_entries = true) {
+    if (E < 0 || E > DMNERF_VOLUME_EDIT_MAX) return dmn_fail(DMNERF_E_ARG, "%s: E=%d outside 0..%d", who, E, DMNERF_VOLUME_EDIT_MAX);
+    if (need_entries && E > 0 && !entries) return dmn_fail(DMNERF_E_ARG, "%s: null entries", who);
+    return DMNERF_OK;
+}
+// ... and, entry by entry, kind 0..2 and label in [0, C); out[0 .. E) = the entries (the kernel argument).
+inline int dmn_edit_entries_given(const char* who, const dmnerf_volume_edit_entry* entries, int E, int C, dmnerf_volume_edit_entry* out) {
+    for (int e = 0; e < E; ++e) {
+        const dmnerf_volume_edit_entry& s = entries[e];
+        if (s.kind < 0 || s.kind > 2) return dmn_fail(DMNERF_E_ARG, "%s: entry %d has kind %d (0 move, 1 copy, 2 remove)", who, e, s.kind);
+        if (s.label < 0 || s.label >= C) return dmn_fail(DMNERF_E_ARG, "%s: entry %d has label %d outside [0, %d)", who, e, s.label, C);
+        out[e] = s;
+    }
+    return DMNERF_OK;
+}
+// skip.hip: passes 2 and 3 of a selection by byte (the scan of the per-block counts, the scatter, *d_count, the running sums)
+void dmn_select_finish(const uint8_t* d_byte, int none, int64_t M, int* d_work, int* d_sel, int* d_count, int64_t* d_totals, hipStream_t st);
+
 // Grid of the MLP kernels: workgroups of 4 waves x 32 samples for M samples, refused beyond one launch's 2^31 - 1
 // (brief: the wording of the split-operand entries).
 inline int dmn_mlp_grid(const char* who, int64_t M, unsigned* grid, bool brief = false) {

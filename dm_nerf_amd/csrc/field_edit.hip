@@ -2,8 +2,8 @@
 // sample falls into decides WHERE the network is asked (networks/render.py run_network_edited; DESIGN.md 8a, "The field-edit route").
 //
 //   dmnerf_field_edit_select   dmnerf_skip_select_fill with the byte volume `source` of dmnerf_volume_edit in place of the bit grid.
-//                              Sample m = n S + s has the point p = o + d z and the cell floorf((p_a - lo_a) inv_cell_a): the select's
-//                              arithmetic, statement for statement.  Its OWNER is source[cell] inside the box (a byte that names a
+//                              Sample m = n S + s has the point p = o + d z and the cell of grid_cell_of_sample (grid_volume.h): the
+//                              select's cell, one function.  Its OWNER is source[cell] inside the box (a byte that names a
 //                              REMOVE entry or is > E reads as 255), the `outside` policy outside it and the `unowned` policy where
 //                              the byte is 255: EVALUATE gives owner 0, EMPTY gives 255.  Owner 255: not evaluated, the row of
 //                              `rows` becomes fill_row.  Owner 0: evaluated on its own ray, (o, d) copied bit for bit.  Owner 1 + e:
@@ -18,14 +18,16 @@
 // The entry that owns a sample differs from lane to lane.  The table is a kernel argument and is walked with a wave-uniform counter
 // (scalar loads); a lane takes the entry whose number equals its owner, and a wave skips the entries none of its lanes has: no
 // per-lane index into the argument, no register array, no scratch.  The accept masks are walked the same way.  The selection is
-// skip.hip's three passes (per-block counts, one scan, scatter by prefix sums): ascending, the same list every run.  The kept counts
-// are ballots and popcounts into the workgroup's LDS table and one flush with integer atomics.  No float atomics.
+// the select's three passes (per-block counts here, then skip.hip's scan and scatter by prefix sums): ascending, the same list every
+// run.  The kept counts are ballots and popcounts into the workgroup's LDS table and one flush with integer atomics.  No float
+// atomics.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/dmnerf_hip.h"
 #include "common.h"
+#include "grid_volume.h"
 
 namespace {
 
@@ -39,48 +41,14 @@ struct FieldEntries {
 };
 
 struct FieldBox {
-    float lo[3], inv_cell[3];
-    int dims[3];
+    GridBox box;
     int outside_owner, unowned_owner;          // 0 ("evaluate") or 255 ("empty")
     unsigned long long evaluable;              // bit b: a source byte b <= E is an owner (bit 0; bit 1 + e for a MOVE / COPY entry e)
 };
 
 struct FieldMasks {
-    uint32_t w[1 + MAX_E][4];
+    LabelMask128 m[1 + MAX_E];
 };
-
-// (skip.hip's block_count_and_rank)
-__device__ __forceinline__ int block_count_and_rank(bool f, int* rank_out) {
-    __shared__ int wave_n[BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(f);
-    if (lane == 0) wave_n[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        if (w < wave) before += wave_n[w];
-        total += wave_n[w];
-    }
-    *rank_out = before + __popcll(b & ((1ull << lane) - 1ull));
-    return total;
-}
-
-// The block's run of rows [m0, m0 + nrows) of `rows`, one float per lane and step: fill_row[column] into the rows whose byte of
-// `fill` (LDS, published by the caller's barrier) is set.  (skip_flag_fill_kernel's loop: rows have no alignment.)
-__device__ __forceinline__ void fill_block_rows(const uint8_t* fill, float* __restrict__ rows, const float* __restrict__ fill_row,
-                                                int64_t m0, int64_t M, int width) {
-    const int nrows = (int)(M - m0 < BLOCK ? M - m0 : BLOCK);
-    const int run = nrows * width;                                 // <= 256 * 132 floats
-    float* out = rows + m0 * width;
-    const int dr = BLOCK / width, dc = BLOCK - dr * width;
-    int r = threadIdx.x / width, c = threadIdx.x - r * width;
-    for (int i = threadIdx.x; i < run; i += BLOCK) {
-        if (fill[r]) out[i] = fill_row[c];
-        r += dr; c += dc;
-        if (c >= width) { c -= width; ++r; }
-    }
-}
 
 // ---- select, pass 1: owner, the ray of every evaluated sample, the block's count, the fill of the rows nobody evaluates
 __global__ __launch_bounds__(BLOCK) void field_edit_owner_kernel(FieldBox G, const uint8_t* __restrict__ source, FieldEntries ent, int E,
@@ -96,20 +64,13 @@ __global__ __launch_bounds__(BLOCK) void field_edit_owner_kernel(FieldBox G, con
     float o[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
     if (m < M) {
         const int64_t n = m / S;
-        const float zv = z[m];
-        bool inside = true;
-        int64_t g = 0;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             o[a] = rays_o[n * 3 + a];
             d[a] = rays_d[n * 3 + a];
-            // (skip_flag_kernel's statements: separate multiply and add, every operation rounded on its own, the test on the float)
-            const float p = __fadd_rn(o[a], __fmul_rn(d[a], zv));
-            const float c = floorf(__fmul_rn(__fsub_rn(p, G.lo[a]), G.inv_cell[a]));
-            inside = inside && (c >= 0.f) && (c < (float)G.dims[a]);
-            g = g * G.dims[a] + (inside ? (int)c : 0);
         }
-        if (inside) {
+        int64_t g;
+        if (grid_cell_of_sample(G.box, rays_o, rays_d, n, z[m], &g)) {        // (the select's cell rule)
             int b = source[g];
             if (b > E || ((G.evaluable >> b) & 1ull) == 0) b = NOBODY;          // (b <= E <= 32: the shift is defined)
             own = b == NOBODY ? G.unowned_owner : b;
@@ -143,57 +104,14 @@ __global__ __launch_bounds__(BLOCK) void field_edit_owner_kernel(FieldBox G, con
     }
     block_fill[threadIdx.x] = f ? 0 : 1;
     int rank;
-    const int total = block_count_and_rank(f, &rank);              // (its barrier also publishes block_fill)
+    const int total = block_count_and_rank<BLOCK>(f, &rank);       // (its barrier also publishes block_fill)
     if (threadIdx.x == 0) block_n[blockIdx.x] = total;
-    if (rows) fill_block_rows(block_fill, rows, fill_row, m0, M, width);
+    if (rows) fill_block_rows<BLOCK>(block_fill, rows, fill_row, m0, M, width);
 }
 
-// ---- pass 2 and 3: skip.hip's scan of the block counts (one workgroup, 1024 at a time) and its scatter, with owner != 255 as the flag
-__global__ __launch_bounds__(1024) void field_edit_scan_kernel(int* __restrict__ block_n, int64_t nb, int* __restrict__ count) {
-    __shared__ int buf[1024];
-    const int tid = threadIdx.x;
-    int carry = 0;                                                 // the same in every thread
-    for (int64_t base = 0; base < nb; base += 1024) {
-        const int64_t i = base + tid;
-        const int v = i < nb ? block_n[i] : 0;
-        buf[tid] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const int t = tid >= off ? buf[tid - off] : 0;
-            __syncthreads();
-            buf[tid] += t;
-            __syncthreads();
-        }
-        if (i < nb) block_n[i] = carry + buf[tid] - v;
-        carry += buf[1023];
-        __syncthreads();
-    }
-    if (tid == 0) *count = carry;
-}
-
-__global__ __launch_bounds__(BLOCK) void field_edit_scatter_kernel(const uint8_t* __restrict__ owner, const int* __restrict__ block_off,
-                                                                   int64_t M, int* __restrict__ sel) {
-    const int64_t m = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const bool f = m < M && owner[m] != NOBODY;
-    int rank;
-    (void)block_count_and_rank(f, &rank);
-    if (f) sel[block_off[blockIdx.x] + rank] = (int)m;
-}
-
-// (the running sums += (evaluated, M); one thread, a plain read-modify-write ordered by the stream)
-__global__ void field_edit_add_totals_kernel(const int* __restrict__ count, int64_t M, int64_t* __restrict__ totals) {
-    totals[0] += *count;
-    totals[1] += M;
-}
+// (passes 2 and 3, with owner != 255 as the flag: dmn_select_finish, skip.hip)
 
 // ---- filter.  One sample per lane; a row is 4 + C <= 132 floats.
-// (a select chain and not w[l >> 5]: a per-lane index into a kernel argument would put the mask into scratch)
-__device__ __forceinline__ bool mask_bit(const uint32_t (&w)[4], uint32_t l) {
-    const uint32_t q = l >> 5;
-    const uint32_t word = q == 0 ? w[0] : q == 1 ? w[1] : q == 2 ? w[2] : q == 3 ? w[3] : 0u;
-    return ((word >> (l & 31)) & 1u) != 0;
-}
-
 __global__ void field_edit_kept_init_kernel(int E, unsigned long long* __restrict__ kept) {
     if ((int)threadIdx.x <= E) kept[threadIdx.x] = 0;
 }
@@ -223,14 +141,14 @@ __global__ __launch_bounds__(BLOCK) void field_edit_filter_kernel(float* __restr
     for (int w = 0; w <= E; ++w) {                                 // (wave-uniform: scalar loads of the mask words)
         const bool in_w = active && own == w;
         if (__ballot(in_w) == 0) continue;
-        const bool ok = in_w && mask_bit(masks.w[w], label);
+        const bool ok = in_w && mask_bit(masks.m[w], label);
         const int n = __popcll(__ballot(ok));
         if (n && lane == 0) atomicAdd(&s_kept[w], (unsigned int)n);
         keep = keep || ok;
     }
     block_fill[threadIdx.x] = (active && !keep) ? 1 : 0;
     __syncthreads();
-    fill_block_rows(block_fill, raw, fill_row, m0, M, 4 + C);
+    fill_block_rows<BLOCK>(block_fill, raw, fill_row, m0, M, 4 + C);
     if (kept && (int)threadIdx.x <= E && s_kept[threadIdx.x]) atomicAdd(&kept[threadIdx.x], (unsigned long long)s_kept[threadIdx.x]);
 }
 
@@ -243,33 +161,23 @@ extern "C" int32_t dmnerf_field_edit_select(const uint8_t* d_source, const float
                                         int64_t* d_totals, void* stream) {
     const char* who = "field_edit_select";
     hipStream_t st = (hipStream_t)stream;
-    if (!lo || !inv_cell || !dims) return dmn_fail(DMNERF_E_ARG, "%s: null host array", who);
+    if (!lo || !inv_cell || !dims) return dmn_fail(DMNERF_E_ARG, "%s: null host array", who);      // (before N and S, as ever)
     if (N < 0 || S < 1) return dmn_fail(DMNERF_E_ARG, "%s: bad N=%lld S=%d", who, (long long)N, S);
     const int64_t M = N * S;
     if (M >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: %lld samples do not fit the int32 selection", who, (long long)M);
     FieldBox G;
-    int64_t cells = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1) return dmn_fail(DMNERF_E_ARG, "%s: bad dims %d x %d x %d", who, dims[0], dims[1], dims[2]);
-        G.lo[a] = lo[a]; G.inv_cell[a] = inv_cell[a]; G.dims[a] = dims[a];
-        cells *= dims[a];
-        if (cells >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: the cells do not fit int32", who);
-    }
+    int64_t cells;
+    if (int rc = dmn_grid_given(who, lo, nullptr, inv_cell, dims, &G.box, &cells)) return rc;
     for (int policy : {outside, unowned})
         if (policy != DMNERF_SKIP_OUTSIDE_EVALUATE && policy != DMNERF_SKIP_OUTSIDE_EMPTY)
             return dmn_fail(DMNERF_E_ARG, "%s: policy %d unknown (outside %d, unowned %d)", who, policy, outside, unowned);
-    if (C < 1 || C > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "%s: C=%d outside 1..%d", who, C, DMNERF_MAX_LOGITS);
-    if (E < 0 || E > MAX_E) return dmn_fail(DMNERF_E_ARG, "%s: E=%d outside 0..%d", who, E, MAX_E);
-    if (E > 0 && !entries) return dmn_fail(DMNERF_E_ARG, "%s: null entries", who);
+    if (int rc = dmn_check_labels(who, C)) return rc;
+    if (int rc = dmn_edit_count_given(who, E, entries)) return rc;
     FieldEntries ent = {};
+    if (int rc = dmn_edit_entries_given(who, entries, E, C, ent.e)) return rc;
     G.evaluable = 1ull;
-    for (int e = 0; e < E; ++e) {
-        const dmnerf_volume_edit_entry& s = entries[e];
-        if (s.kind < 0 || s.kind > 2) return dmn_fail(DMNERF_E_ARG, "%s: entry %d has kind %d (0 move, 1 copy, 2 remove)", who, e, s.kind);
-        if (s.label < 0 || s.label >= C) return dmn_fail(DMNERF_E_ARG, "%s: entry %d has label %d outside [0, %d)", who, e, s.label, C);
-        ent.e[e] = s;
-        if (s.kind != KIND_REMOVE) G.evaluable |= 1ull << (1 + e);
-    }
+    for (int e = 0; e < E; ++e)
+        if (ent.e[e].kind != KIND_REMOVE) G.evaluable |= 1ull << (1 + e);
     G.outside_owner = outside == DMNERF_SKIP_OUTSIDE_EVALUATE ? 0 : NOBODY;
     G.unowned_owner = unowned == DMNERF_SKIP_OUTSIDE_EVALUATE ? 0 : NOBODY;
     if (!d_count) return dmn_fail(DMNERF_E_ARG, "%s: null pointer", who);
@@ -280,9 +188,7 @@ extern "C" int32_t dmnerf_field_edit_select(const uint8_t* d_source, const float
     const int64_t nb = (M + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL(field_edit_owner_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, G, d_source, ent, E, d_rays_o, d_rays_d, d_z, M, S,
                        d_owner, d_o_w, d_d_w, d_work, d_rows, d_fill_row, 4 + C);
-    hipLaunchKernelGGL(field_edit_scan_kernel, dim3(1), dim3(1024), 0, st, d_work, nb, d_count);
-    hipLaunchKernelGGL(field_edit_scatter_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, d_owner, d_work, M, d_sel);
-    if (d_totals) hipLaunchKernelGGL(field_edit_add_totals_kernel, dim3(1), dim3(1), 0, st, d_count, M, d_totals);
+    dmn_select_finish(d_owner, NOBODY, M, d_work, d_sel, d_count, d_totals, st);
     return dmn_check_launch(who);
 }
 
@@ -290,14 +196,14 @@ extern "C" int32_t dmnerf_field_edit_filter(float* d_raw, const uint8_t* d_owner
                                         const float* d_fill_row, int64_t* d_kept, void* stream) {
     const char* who = "field_edit_filter";
     if (M < 0 || M >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: bad M=%lld (0 <= M < 2^31)", who, (long long)M);
-    if (C < 1 || C > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "%s: C=%d outside 1..%d", who, C, DMNERF_MAX_LOGITS);
-    if (E < 0 || E > MAX_E) return dmn_fail(DMNERF_E_ARG, "%s: E=%d outside 0..%d", who, E, MAX_E);
+    if (int rc = dmn_check_labels(who, C)) return rc;
+    if (int rc = dmn_edit_count_given(who, E, nullptr, false)) return rc;
     if (!masks) return dmn_fail(DMNERF_E_ARG, "%s: null masks", who);
     if (M == 0) return DMNERF_OK;
     if (!d_raw || !d_owner || !d_fill_row) return dmn_fail(DMNERF_E_ARG, "%s: null pointer", who);
     FieldMasks k = {};
     for (int w = 0; w <= E; ++w)
-        for (int q = 0; q < 4; ++q) k.w[w][q] = masks[4 * w + q];
+        for (int q = 0; q < 4; ++q) k.m[w].w[q] = masks[4 * w + q];
     unsigned long long* kept = reinterpret_cast<unsigned long long*>(d_kept);
     if (kept) hipLaunchKernelGGL(field_edit_kept_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, E, kept);
     const int64_t nb = (M + BLOCK - 1) / BLOCK;

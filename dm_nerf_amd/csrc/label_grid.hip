@@ -27,6 +27,7 @@
 
 #include "../../include/dmnerf_hip.h"
 #include "common.h"
+#include "grid_volume.h"
 
 namespace {
 
@@ -203,21 +204,13 @@ __global__ __launch_bounds__(BLOCK) void label_stats_kernel(const uint8_t* __res
 
 // ---- bits.  skip.hip's packing: a block owns 256 consecutive cells = 8 whole words; 64 cells = one ballot = 2 words, written by lanes
 // 0 and 32.  A cell past the end contributes 0, so the unused bits of the last word are 0.
-struct LabelMask {
-    uint32_t w[4];
-};
-
-__global__ __launch_bounds__(BLOCK) void skip_grid_from_labels_kernel(const uint8_t* __restrict__ labels, int64_t n_cells, LabelMask mask,
+__global__ __launch_bounds__(BLOCK) void skip_grid_from_labels_kernel(const uint8_t* __restrict__ labels, int64_t n_cells, LabelMask128 mask,
                                                                       uint32_t* __restrict__ bits) {
     const int64_t g0 = (int64_t)blockIdx.x * BLOCK;
     const int64_t g = g0 + threadIdx.x;
     bool set = false;
     if (g < n_cells) {
-        const uint32_t l = labels[g];
-        // (a select chain and not mask.w[l >> 5]: a dynamic index into a kernel argument would put the mask into scratch)
-        const uint32_t q = l >> 5;
-        const uint32_t word = q == 0 ? mask.w[0] : q == 1 ? mask.w[1] : q == 2 ? mask.w[2] : q == 3 ? mask.w[3] : 0u;
-        set = ((word >> (l & 31)) & 1u) != 0;
+        set = mask_bit(mask, labels[g]);
     }
     const unsigned long long ballot = __ballot(set);
     const int lane = threadIdx.x & 63;
@@ -227,17 +220,10 @@ __global__ __launch_bounds__(BLOCK) void skip_grid_from_labels_kernel(const uint
     }
 }
 
-inline int label_check_dims(const char* who, int dx, int dy, int dz, int64_t* total) {
-    if (dx < 1 || dy < 1 || dz < 1) return dmn_fail(DMNERF_E_ARG, "%s: bad dims %d x %d x %d", who, dx, dy, dz);
-    *total = (int64_t)dx * dy * dz;
-    if (*total >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: %lld cells do not fit int32", who, (long long)*total);
-    return DMNERF_OK;
-}
-
 }  // namespace
 
 extern "C" int dmnerf_label_cells(const float* d_raw, int64_t M, int C, float sigma_threshold, uint8_t* d_labels, void* stream) {
-    if (C < 1 || C > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "label_cells: C=%d outside 1..%d", C, DMNERF_MAX_LOGITS);
+    if (int rc = dmn_check_labels("label_cells", C)) return rc;
     if (M < 0) return dmn_fail(DMNERF_E_ARG, "label_cells: bad M=%lld", (long long)M);
     if (!(sigma_threshold >= 0.f)) return dmn_fail(DMNERF_E_ARG, "label_cells: sigma_threshold %g must be >= 0", (double)sigma_threshold);
     const int64_t nb = (M + BLOCK - 1) / BLOCK;
@@ -250,7 +236,7 @@ extern "C" int dmnerf_label_cells(const float* d_raw, int64_t M, int C, float si
 
 extern "C" int dmnerf_bake_cells(const float* d_raw, int64_t M, int C, float sigma_threshold, uint8_t* d_labels, float* d_cells,
                                  void* stream) {
-    if (C < 1 || C > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "bake_cells: C=%d outside 1..%d", C, DMNERF_MAX_LOGITS);
+    if (int rc = dmn_check_labels("bake_cells", C)) return rc;
     if (M < 0) return dmn_fail(DMNERF_E_ARG, "bake_cells: bad M=%lld", (long long)M);
     if (!(sigma_threshold >= 0.f)) return dmn_fail(DMNERF_E_ARG, "bake_cells: sigma_threshold %g must be >= 0", (double)sigma_threshold);
     const int64_t nb = (M + BLOCK - 1) / BLOCK;
@@ -265,9 +251,11 @@ extern "C" int dmnerf_bake_cells(const float* d_raw, int64_t M, int C, float sig
 
 extern "C" int dmnerf_label_stats(const uint8_t* d_labels, int dx, int dy, int dz, int C, int64_t* d_count, int64_t* d_index_sum,
                                   int32_t* d_lo, int32_t* d_hi, void* stream) {
+    const int dims[3] = {dx, dy, dz};
     int64_t total;
-    if (int rc = label_check_dims("label_stats", dx, dy, dz, &total)) return rc;
-    if (C < 1 || C > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "label_stats: C=%d outside 1..%d", C, DMNERF_MAX_LOGITS);
+    if (int rc = dmn_grid_dims("label_stats", dims)) return rc;
+    if (int rc = dmn_grid_cells("label_stats", dims, &total)) return rc;
+    if (int rc = dmn_check_labels("label_stats", C)) return rc;
     if (!d_labels || !d_count || !d_index_sum || !d_lo || !d_hi) return dmn_fail(DMNERF_E_ARG, "label_stats: null pointer");
     hipLaunchKernelGGL(label_stats_init_kernel, dim3(1), dim3(DMNERF_MAX_LOGITS), 0, (hipStream_t)stream, dx, dy, dz, C, d_count,
                        d_index_sum, d_lo, d_hi);
@@ -283,7 +271,7 @@ extern "C" int dmnerf_skip_grid_from_labels(const uint8_t* d_labels, int64_t n_c
                                             void* stream) {
     if (n_cells < 1 || n_cells >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_grid_from_labels: bad n_cells=%lld", (long long)n_cells);
     if (!d_labels || !mask || !d_bits) return dmn_fail(DMNERF_E_ARG, "skip_grid_from_labels: null pointer");
-    LabelMask m;
+    LabelMask128 m;
     for (int q = 0; q < 4; ++q) m.w[q] = mask[q];
     hipLaunchKernelGGL(skip_grid_from_labels_kernel, dim3((unsigned)((n_cells + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
                        d_labels, n_cells, m, d_bits);

@@ -33,7 +33,7 @@
 
 #include "../../include/dmnerf_hip.h"
 #include "common.h"
-#include "label_walk.h"                       // TraceGrid, nan_min / nan_max, plane_of
+#include "grid_volume.h"                      // GridBox, mask_bit, the walk
 
 namespace {
 
@@ -45,7 +45,7 @@ struct TraceMasks {
     uint32_t w[MAX_SETS * 4];
 };
 
-__global__ __launch_bounds__(BLOCK) void label_trace_kernel(const uint8_t* __restrict__ labels, TraceGrid G, int C,
+__global__ __launch_bounds__(BLOCK) void label_trace_kernel(const uint8_t* __restrict__ labels, GridBox G, int C,
                                                             const float* __restrict__ rays, int R, int64_t N, TraceMasks M,
                                                             float t_near, float t_far, uint8_t* __restrict__ out_label,
                                                             float* __restrict__ out_t, int32_t* __restrict__ out_cell,
@@ -63,68 +63,32 @@ __global__ __launch_bounds__(BLOCK) void label_trace_kernel(const uint8_t* __res
         const uint32_t m0 = M.w[r * 4 + 0], m1 = M.w[r * 4 + 1], m2 = M.w[r * 4 + 2], m3 = M.w[r * 4 + 3];
         const float* o = rays + ((int64_t)(2 * r) * N + n) * 3;
         const float* d = rays + ((int64_t)(2 * r + 1) * N + n) * 3;
-        const float o0 = o[0], o1 = o[1], o2 = o[2], d0 = d[0], d1 = d[1], d2 = d[2];
+        WalkRay ray = {o[0], o[1], o[2], d[0], d[1], d[2], inf, inf, inf};
         // ---- clip
         float t_enter = t_near, t_exit = t_far;
         bool miss = false;
-        float inv0 = inf, inv1 = inf, inv2 = inf;
-        if (d0 == 0.f) {
-            miss = miss || !(G.lo[0] <= o0 && o0 < hi0);
-        } else {
-            inv0 = __fdiv_rn(1.f, d0);
-            const float t0 = __fmul_rn(__fsub_rn(G.lo[0], o0), inv0), t1 = __fmul_rn(__fsub_rn(hi0, o0), inv0);
-            t_enter = nan_max(t_enter, nan_min(t0, t1));
-            t_exit = nan_min(t_exit, nan_max(t0, t1));
-        }
-        if (d1 == 0.f) {
-            miss = miss || !(G.lo[1] <= o1 && o1 < hi1);
-        } else {
-            inv1 = __fdiv_rn(1.f, d1);
-            const float t0 = __fmul_rn(__fsub_rn(G.lo[1], o1), inv1), t1 = __fmul_rn(__fsub_rn(hi1, o1), inv1);
-            t_enter = nan_max(t_enter, nan_min(t0, t1));
-            t_exit = nan_min(t_exit, nan_max(t0, t1));
-        }
-        if (d2 == 0.f) {
-            miss = miss || !(G.lo[2] <= o2 && o2 < hi2);
-        } else {
-            inv2 = __fdiv_rn(1.f, d2);
-            const float t0 = __fmul_rn(__fsub_rn(G.lo[2], o2), inv2), t1 = __fmul_rn(__fsub_rn(hi2, o2), inv2);
-            t_enter = nan_max(t_enter, nan_min(t0, t1));
-            t_exit = nan_min(t_exit, nan_max(t0, t1));
-        }
+        walk_clip_axis(G.lo[0], hi0, ray.o0, ray.d0, ray.inv0, t_enter, t_exit, miss);
+        walk_clip_axis(G.lo[1], hi1, ray.o1, ray.d1, ray.inv1, t_enter, t_exit, miss);
+        walk_clip_axis(G.lo[2], hi2, ray.o2, ray.d2, ray.inv2, t_enter, t_exit, miss);
         if (miss || !(t_enter < t_exit)) continue;
         // ---- start cell
-        const float f0 = floorf(__fmul_rn(__fsub_rn(__fadd_rn(o0, __fmul_rn(d0, t_enter)), G.lo[0]), G.inv_cell[0]));
-        const float f1 = floorf(__fmul_rn(__fsub_rn(__fadd_rn(o1, __fmul_rn(d1, t_enter)), G.lo[1]), G.inv_cell[1]));
-        const float f2 = floorf(__fmul_rn(__fsub_rn(__fadd_rn(o2, __fmul_rn(d2, t_enter)), G.lo[2]), G.inv_cell[2]));
-        int c0 = f0 >= 0.f ? (f0 < (float)dx ? (int)f0 : dx - 1) : 0;          // (a NaN: 0)
-        int c1 = f1 >= 0.f ? (f1 < (float)dy ? (int)f1 : dy - 1) : 0;
-        int c2 = f2 >= 0.f ? (f2 < (float)dz ? (int)f2 : dz - 1) : 0;
-        const int up0 = d0 > 0.f, up1 = d1 > 0.f, up2 = d2 > 0.f;
+        int c0 = walk_start_cell(ray.o0, ray.d0, t_enter, G.lo[0], G.inv_cell[0], dx);
+        int c1 = walk_start_cell(ray.o1, ray.d1, t_enter, G.lo[1], G.inv_cell[1], dy);
+        int c2 = walk_start_cell(ray.o2, ray.d2, t_enter, G.lo[2], G.inv_cell[2], dz);
         // ---- walk
         float t = t_enter;
         for (int it = 0; it < max_cells; ++it) {
             const int g = (c0 * dy + c1) * dz + c2;                               // 0 <= c_a < dims_a: always inside the volume
             const uint32_t l = labels[g];
-            const uint32_t q = l >> 5;
-            const uint32_t word = q == 0 ? m0 : q == 1 ? m1 : q == 2 ? m2 : q == 3 ? m3 : 0u;
-            if (l < (uint32_t)C && ((word >> (l & 31)) & 1u)) {
+            const bool in_set = mask_bit(m0, m1, m2, m3, l);
+            if (l < (uint32_t)C && in_set) {
                 if (t < best_t) { best_t = t; best_label = (int)l; best_cell = g; best_source = r; }
                 break;
             }
-            const float tm0 = d0 == 0.f ? inf : __fmul_rn(__fsub_rn(plane_of(G.lo[0], G.cell[0], c0 + up0), o0), inv0);
-            const float tm1 = d1 == 0.f ? inf : __fmul_rn(__fsub_rn(plane_of(G.lo[1], G.cell[1], c1 + up1), o1), inv1);
-            const float tm2 = d2 == 0.f ? inf : __fmul_rn(__fsub_rn(plane_of(G.lo[2], G.cell[2], c2 + up2), o2), inv2);
-            int axis = 0;
-            float tm = tm0;
-            if (tm1 < tm) { axis = 1; tm = tm1; }
-            if (tm2 < tm) { axis = 2; tm = tm2; }
-            if (!(tm < t_exit)) break;
-            t = tm > t ? tm : t;
-            c0 += axis == 0 ? (up0 ? 1 : -1) : 0;
-            c1 += axis == 1 ? (up1 ? 1 : -1) : 0;
-            c2 += axis == 2 ? (up2 ? 1 : -1) : 0;
-            if (c0 < 0 || c0 >= dx || c1 < 0 || c1 >= dy || c2 < 0 || c2 >= dz) break;
+            int axis;
+            float tm;
+            if (!walk_step(G, ray, c0, c1, c2, t_exit, &axis, &tm)) break;
+            if (walk_apply(G, ray, axis, tm, c0, c1, c2, t)) break;
         }
     }
     out_label[n] = (uint8_t)best_label;
@@ -138,20 +102,17 @@ __global__ __launch_bounds__(BLOCK) void label_trace_kernel(const uint8_t* __res
 extern "C" int dmnerf_label_trace(const uint8_t* d_labels, const float lo[3], const float cell[3], const float inv_cell[3],
                                   const int dims[3], int C, const float* d_rays, int R, int64_t N, const uint32_t* masks, float t_near,
                                   float t_far, uint8_t* d_label, float* d_t, int32_t* d_cell, uint8_t* d_source, void* stream) {
-    if (!lo || !cell || !inv_cell || !dims || !masks) return dmn_fail(DMNERF_E_ARG, "label_trace: null pointer");
+    if (!lo || !cell || !inv_cell || !dims || !masks) return dmn_fail(DMNERF_E_ARG, "label_trace: null pointer");      // (the host arrays: before N, as ever)
     if (N < 0) return dmn_fail(DMNERF_E_ARG, "label_trace: bad N=%lld", (long long)N);
     if (R < 1 || R > MAX_SETS) return dmn_fail(DMNERF_E_ARG, "label_trace: R=%d outside 1..%d", R, MAX_SETS);
-    if (C < 1 || C > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "label_trace: C=%d outside 1..%d", C, DMNERF_MAX_LOGITS);
-    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1)
-        return dmn_fail(DMNERF_E_ARG, "label_trace: bad dims %d x %d x %d", dims[0], dims[1], dims[2]);
-    const int64_t total = (int64_t)dims[0] * dims[1] * dims[2];
-    if (total >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "label_trace: %lld cells do not fit int32", (long long)total);
+    if (int rc = dmn_check_labels("label_trace", C)) return rc;
+    GridBox G;
+    int64_t total;
+    if (int rc = dmn_grid_given("label_trace", lo, cell, inv_cell, dims, &G, &total)) return rc;
     const int64_t nb = (N + BLOCK - 1) / BLOCK;
     if (nb > 0x7fffffffLL) return dmn_fail(DMNERF_E_ARG, "label_trace: %lld rays is too many for one launch", (long long)N);
     if (N == 0) return DMNERF_OK;
     if (!d_labels || !d_rays || !d_label || !d_t || !d_cell || !d_source) return dmn_fail(DMNERF_E_ARG, "label_trace: null pointer");
-    TraceGrid G;
-    for (int a = 0; a < 3; ++a) { G.lo[a] = lo[a]; G.cell[a] = cell[a]; G.inv_cell[a] = inv_cell[a]; G.dims[a] = dims[a]; }
     TraceMasks M;
     for (int q = 0; q < MAX_SETS * 4; ++q) M.w[q] = q < R * 4 ? masks[q] : 0u;
     hipLaunchKernelGGL(label_trace_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, (hipStream_t)stream, d_labels, G, C, d_rays, R, N, M, t_near,

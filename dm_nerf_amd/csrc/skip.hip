@@ -29,6 +29,7 @@
 
 #include "../../include/dmnerf_hip.h"
 #include "common.h"
+#include "grid_volume.h"
 
 namespace {
 
@@ -79,29 +80,19 @@ __global__ __launch_bounds__(BLOCK) void skip_grid_build_kernel(const float* __r
     }
 }
 
-// ---- select, pass 1: the flag of every sample and the number of flagged samples of every block
+// ---- select, pass 1: the flag of every sample and the number of flagged samples of every block.  The cell of a sample is
+// grid_cell_of_sample (grid_volume.h): what this flags is what the sparse network evaluates and what skip_mark_kernel marks.
 struct GridDev {
-    float lo[3], inv_cell[3];
-    int dims[3];
+    GridBox box;
     int outside_flag;          // the flag of a sample outside the box: 1 ("evaluate") or 0 ("empty")
     const uint32_t* bits;
 };
 
-__device__ __forceinline__ int block_count_and_rank(bool f, int* rank_out) {
-    // -> the block's total; *rank_out = number of flagged threads before this one (thread order)
-    __shared__ int wave_n[BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(f);
-    if (lane == 0) wave_n[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        if (w < wave) before += wave_n[w];
-        total += wave_n[w];
-    }
-    *rank_out = before + __popcll(b & ((1ull << lane) - 1ull));
-    return total;
+__device__ __forceinline__ bool skip_flag_of(const GridDev& G, const float* __restrict__ rays_o, const float* __restrict__ rays_d, int64_t n,
+                                             float zv) {
+    int64_t g;
+    const bool inside = grid_cell_of_sample(G.box, rays_o, rays_d, n, zv, &g);
+    return inside ? ((G.bits[g >> 5] >> (g & 31)) & 1u) != 0 : G.outside_flag != 0;
 }
 
 __global__ __launch_bounds__(BLOCK) void skip_flag_kernel(GridDev G, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
@@ -110,75 +101,39 @@ __global__ __launch_bounds__(BLOCK) void skip_flag_kernel(GridDev G, const float
     const int64_t m = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     bool f = false;
     if (m < M) {
-        const int64_t n = m / S;
-        const float zv = z[m];
-        bool inside = true;
-        int64_t g = 0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            // p = o + d z: separate multiply and add, as the MLP prologue (render.py:49); then every operation rounded on its own
-            const float p = __fadd_rn(rays_o[n * 3 + a], __fmul_rn(rays_d[n * 3 + a], zv));
-            const float c = floorf(__fmul_rn(__fsub_rn(p, G.lo[a]), G.inv_cell[a]));
-            inside = inside && (c >= 0.f) && (c < (float)G.dims[a]);        // on the float: a NaN point is outside
-            g = g * G.dims[a] + (inside ? (int)c : 0);
-        }
-        f = inside ? ((G.bits[g >> 5] >> (g & 31)) & 1u) != 0 : G.outside_flag != 0;
+        f = skip_flag_of(G, rays_o, rays_d, m / S, z[m]);
         flag[m] = f ? 1 : 0;
     }
     int rank;
-    const int total = block_count_and_rank(f, &rank);
+    const int total = block_count_and_rank<BLOCK>(f, &rank);
     if (threadIdx.x == 0) block_n[blockIdx.x] = total;
 }
 
-// ---- select-and-fill, pass 1: skip_flag_kernel that also writes fill_row into the rows of the samples it does not flag.  The block's
-// samples are rows [m0, m0 + 256) of `rows`, one contiguous run of 256 * width floats.  width = 4 + C is rarely a multiple of 4 and a
-// row is not 16-byte aligned, so the run is written one float per lane: lane t takes floats t, t + 256, ... of the run (a wave stores
-// 256 consecutive bytes), looks the float's row up in the block's flags (LDS) and stores fill_row[column] where the flag is 0.
-// (row, column) advance by (256 / width, 256 % width) per step: no division in the loop.  The flag arithmetic is skip_flag_kernel's,
-// statement for statement; that kernel is left as it is so that dmnerf_skip_select runs the machine code it always ran.
+// ---- select-and-fill, pass 1: skip_flag_kernel that also writes fill_row into the rows of the samples it does not flag: the block's
+// samples are rows [m0, m0 + 256) of `rows` (fill_block_rows, grid_volume.h).
 __global__ __launch_bounds__(BLOCK) void skip_flag_fill_kernel(GridDev G, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                                const float* __restrict__ z, int64_t M, int S, uint8_t* __restrict__ flag,
                                                                int* __restrict__ block_n, float* __restrict__ rows,
                                                                const float* __restrict__ fill_row, int width) {
-    __shared__ uint8_t block_flag[BLOCK];
+    __shared__ uint8_t block_fill[BLOCK];
     const int64_t m0 = (int64_t)blockIdx.x * BLOCK;
     const int64_t m = m0 + threadIdx.x;
     bool f = false;
     if (m < M) {
-        const int64_t n = m / S;
-        const float zv = z[m];
-        bool inside = true;
-        int64_t g = 0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float p = __fadd_rn(rays_o[n * 3 + a], __fmul_rn(rays_d[n * 3 + a], zv));
-            const float c = floorf(__fmul_rn(__fsub_rn(p, G.lo[a]), G.inv_cell[a]));
-            inside = inside && (c >= 0.f) && (c < (float)G.dims[a]);
-            g = g * G.dims[a] + (inside ? (int)c : 0);
-        }
-        f = inside ? ((G.bits[g >> 5] >> (g & 31)) & 1u) != 0 : G.outside_flag != 0;
+        f = skip_flag_of(G, rays_o, rays_d, m / S, z[m]);
         flag[m] = f ? 1 : 0;
     }
-    block_flag[threadIdx.x] = f ? 1 : 0;
+    block_fill[threadIdx.x] = f ? 0 : 1;
     int rank;
-    const int total = block_count_and_rank(f, &rank);            // (its barrier also publishes block_flag)
+    const int total = block_count_and_rank<BLOCK>(f, &rank);     // (its barrier also publishes block_fill)
     if (threadIdx.x == 0) block_n[blockIdx.x] = total;
-    const int nrows = (int)(M - m0 < BLOCK ? M - m0 : BLOCK);
-    const int run = nrows * width;                                 // <= 256 * width floats
-    float* out = rows + m0 * width;
-    const int dr = BLOCK / width, dc = BLOCK - dr * width;
-    int r = threadIdx.x / width, c = threadIdx.x - r * width;
-    for (int i = threadIdx.x; i < run; i += BLOCK) {
-        if (!block_flag[r]) out[i] = fill_row[c];
-        r += dr; c += dc;
-        if (c >= width) { c -= width; ++r; }
-    }
+    fill_block_rows<BLOCK>(block_fill, rows, fill_row, m0, M, width);
 }
 
-// ---- mark.  The cell of sample (ray n, depth zv): skip_flag_kernel's arithmetic, operation for operation (separate multiply and add
-// for p = o + d z, render.py:49; subtract, multiply, floorf, each rounded on its own; the inside test on the float, so a NaN point is
-// outside).  -> inside; *g_out = the cell's index where inside.  skip_flag_kernel and skip_flag_fill_kernel keep their own copies
-// of these statements so that they run the machine code they always ran.
+// ---- mark.  This kernel keeps its own statement of the cell rule and its own argument (the box without `cell`), as it always had
+// them: through grid_cell_of_sample and a GridBox the two mark passes measured 4 to 8 % (empty grid) and 17 to 19 % (saturated grid)
+// slower in two sessions (profiles/grid_refactor/README.md); like this its instruction text is the parent's.  The statements are
+// grid_cell_of_sample's, operation for operation, and tests/_mark_restate.py holds them to the one numpy cell rule.
 struct CellDev {
     float lo[3], inv_cell[3];
     int dims[3];
@@ -282,19 +237,20 @@ __global__ __launch_bounds__(1024) void skip_scan_kernel(int* __restrict__ block
     if (tid == 0) *count = carry;
 }
 
-// ---- pass 3: sample m goes to sel[block offset + rank within the block]
-__global__ __launch_bounds__(BLOCK) void skip_scatter_kernel(const uint8_t* __restrict__ flag, const int* __restrict__ block_off, int64_t M,
-                                                             int* __restrict__ sel) {
+// ---- pass 3: sample m goes to sel[block offset + rank within the block]; a sample is selected iff its byte is not `none`
+// (0 for the select's flags, 255 for the field edit's owners)
+__global__ __launch_bounds__(BLOCK) void skip_scatter_kernel(const uint8_t* __restrict__ flag, int none, const int* __restrict__ block_off,
+                                                             int64_t M, int* __restrict__ sel) {
     const int64_t m = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const bool f = m < M && flag[m] != 0;
+    const bool f = m < M && flag[m] != none;
     int rank;
-    (void)block_count_and_rank(f, &rank);
+    (void)block_count_and_rank<BLOCK>(f, &rank);
     if (f) sel[block_off[blockIdx.x] + rank] = (int)m;
 }
 
 __global__ void skip_set_int_kernel(int* p, int v) { *p = v; }
 
-// (select-and-fill: the running sums += (selected, M); one thread, a plain read-modify-write ordered by the stream)
+// (the running sums += (selected, M); one thread, a plain read-modify-write ordered by the stream)
 __global__ void skip_add_totals_kernel(const int* __restrict__ count, int64_t M, int64_t* __restrict__ totals) {
     totals[0] += *count;
     totals[1] += M;
@@ -308,12 +264,23 @@ int dmn_skip_set_int(int* d_p, int v, hipStream_t stream) {
     return dmn_check_launch("skip: set count");
 }
 
+// Passes 2 and 3 of a selection whose pass 1 left one byte per sample and the per-block counts (blocks of 256 samples) in d_work: the
+// scan, the scatter of the samples whose byte is not `none` into d_sel, *d_count, and (d_totals, may be NULL) the running sums.  The
+// caller checks the launches (dmn_check_launch).  Declared in common.h: field_edit.hip selects by owner with it.
+void dmn_select_finish(const uint8_t* d_byte, int none, int64_t M, int* d_work, int* d_sel, int* d_count, int64_t* d_totals, hipStream_t st) {
+    const int64_t nb = (M + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(skip_scan_kernel, dim3(1), dim3(1024), 0, st, d_work, nb, d_count);
+    hipLaunchKernelGGL(skip_scatter_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, d_byte, none, d_work, M, d_sel);
+    if (d_totals) hipLaunchKernelGGL(skip_add_totals_kernel, dim3(1), dim3(1), 0, st, d_count, M, d_totals);
+}
+
 extern "C" int dmnerf_skip_grid_build(const float* d_sigma, int dx, int dy, int dz, float threshold, int dilate, uint32_t* d_bits,
                                       void* stream) {
-    if (dx < 1 || dy < 1 || dz < 1) return dmn_fail(DMNERF_E_ARG, "skip_grid_build: bad dims %d x %d x %d", dx, dy, dz);
+    const int dims[3] = {dx, dy, dz};
+    int64_t total;
+    if (int rc = dmn_grid_dims("skip_grid_build", dims)) return rc;
     if (dilate < 0 || dilate > MAX_DILATE) return dmn_fail(DMNERF_E_ARG, "skip_grid_build: dilate %d outside 0..%d", dilate, MAX_DILATE);
-    const int64_t total = (int64_t)dx * dy * dz;
-    if (total >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_grid_build: %lld cells do not fit int32", (long long)total);
+    if (int rc = dmn_grid_cells("skip_grid_build", dims, &total)) return rc;
     if (!d_sigma || !d_bits) return dmn_fail(DMNERF_E_ARG, "skip_grid_build: null pointer");
     const int D = 2 * dilate + 1;
     const size_t lds = (size_t)D * D * (BLOCK + 2 * dilate);   // <= 81 * 264 B
@@ -337,13 +304,8 @@ static int skip_select_impl(const char* who, const dmnerf_skip_grid* grid, const
     if (grid->outside != DMNERF_SKIP_OUTSIDE_EVALUATE && grid->outside != DMNERF_SKIP_OUTSIDE_EMPTY)
         return dmn_fail(DMNERF_E_ARG, "%s: outside policy %d unknown", who, grid->outside);
     GridDev G;
-    int64_t cells = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (grid->dims[a] < 1) return dmn_fail(DMNERF_E_ARG, "%s: bad grid dims", who);
-        G.lo[a] = grid->lo[a]; G.inv_cell[a] = grid->inv_cell[a]; G.dims[a] = grid->dims[a];
-        cells *= grid->dims[a];
-    }
-    if (cells >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "%s: %lld cells do not fit int32", who, (long long)cells);
+    int64_t cells;
+    if (int rc = dmn_grid_given(who, grid->lo, nullptr, grid->inv_cell, grid->dims, &G.box, &cells)) return rc;
     G.outside_flag = grid->outside == DMNERF_SKIP_OUTSIDE_EVALUATE ? 1 : 0;
     G.bits = grid->d_bits;
     if (!d_count) return dmn_fail(DMNERF_E_ARG, "%s: null pointer", who);
@@ -357,9 +319,7 @@ static int skip_select_impl(const char* who, const dmnerf_skip_grid* grid, const
                            d_rows, d_fill_row, width);
     else                                                           // (dmnerf_skip_select: the three kernels it always launched)
         hipLaunchKernelGGL(skip_flag_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, G, d_rays_o, d_rays_d, d_z, M, S, d_flag, d_work);
-    hipLaunchKernelGGL(skip_scan_kernel, dim3(1), dim3(1024), 0, st, d_work, nb, d_count);
-    hipLaunchKernelGGL(skip_scatter_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, d_flag, d_work, M, d_sel);
-    if (d_totals) hipLaunchKernelGGL(skip_add_totals_kernel, dim3(1), dim3(1), 0, st, d_count, M, d_totals);
+    dmn_select_finish(d_flag, 0, M, d_work, d_sel, d_count, d_totals, st);
     return dmn_check_launch(who);
 }
 
@@ -389,14 +349,11 @@ extern "C" int dmnerf_skip_grid_mark(const dmnerf_skip_grid* grid, uint32_t* d_b
     if (!grid) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: null grid");
     if (int rc = dmn_check_rays("skip_grid_mark", 1, N, S, true)) return rc;          // (no network here: ins_num 1 always passes)
     if (!(threshold >= 0.f)) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: threshold %g must be >= 0", (double)threshold);
+    GridBox box;
+    int64_t cells;
+    if (int rc = dmn_grid_given("skip_grid_mark", grid->lo, nullptr, grid->inv_cell, grid->dims, &box, &cells)) return rc;
     CellDev G;
-    int64_t cells = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (grid->dims[a] < 1) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: bad grid dims");
-        G.lo[a] = grid->lo[a]; G.inv_cell[a] = grid->inv_cell[a]; G.dims[a] = grid->dims[a];
-        cells *= grid->dims[a];
-        if (cells >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: the cells do not fit int32");
-    }
+    for (int a = 0; a < 3; ++a) { G.lo[a] = box.lo[a]; G.inv_cell[a] = box.inv_cell[a]; G.dims[a] = box.dims[a]; }
     if (!d_bits || !d_rays_o || !d_rays_d || !d_z || !d_weights) return dmn_fail(DMNERF_E_ARG, "skip_grid_mark: null pointer");
     if (N == 0) return DMNERF_OK;
     const int64_t M = N * S;
@@ -407,10 +364,11 @@ extern "C" int dmnerf_skip_grid_mark(const dmnerf_skip_grid* grid, uint32_t* d_b
 
 extern "C" int dmnerf_skip_grid_dilate(const uint32_t* d_bits_in, int dx, int dy, int dz, int dilate, uint32_t* d_bits_out,
                                        void* stream) {
-    if (dx < 1 || dy < 1 || dz < 1) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: bad dims %d x %d x %d", dx, dy, dz);
+    const int dims[3] = {dx, dy, dz};
+    int64_t total;
+    if (int rc = dmn_grid_dims("skip_grid_dilate", dims)) return rc;
     if (dilate < 0 || dilate > MAX_DILATE) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: dilate %d outside 0..%d", dilate, MAX_DILATE);
-    const int64_t total = (int64_t)dx * dy * dz;
-    if (total >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: %lld cells do not fit int32", (long long)total);
+    if (int rc = dmn_grid_cells("skip_grid_dilate", dims, &total)) return rc;
     if (!d_bits_in || !d_bits_out) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: null pointer");
     if (d_bits_in == d_bits_out) return dmn_fail(DMNERF_E_ARG, "skip_grid_dilate: in and out must be different buffers");
     const int D = 2 * dilate + 1;

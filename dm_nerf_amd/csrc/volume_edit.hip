@@ -22,6 +22,7 @@
 
 #include "../../include/dmnerf_hip.h"
 #include "common.h"
+#include "grid_volume.h"
 
 namespace {
 
@@ -35,22 +36,6 @@ struct EditEntries {
     dmnerf_volume_edit_entry e[MAX_E];
 };
 
-struct EditBox {
-    float lo[3], cell[3], inv_cell[3];
-    int dims[3];
-};
-
-struct LabelMask {
-    uint32_t w[4];
-};
-
-// (a select chain and not m.w[l >> 5]: a per-lane index into a kernel argument would put the mask into scratch)
-__device__ __forceinline__ bool mask_bit(const LabelMask& m, uint32_t l) {
-    const uint32_t q = l >> 5;
-    const uint32_t word = q == 0 ? m.w[0] : q == 1 ? m.w[1] : q == 2 ? m.w[2] : q == 3 ? m.w[3] : 0u;
-    return ((word >> (l & 31)) & 1u) != 0;
-}
-
 __global__ void volume_edit_init_kernel(int E, int C, unsigned long long* __restrict__ won, unsigned long long* __restrict__ claimed,
                                         unsigned long long* __restrict__ hits) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -60,8 +45,8 @@ __global__ void volume_edit_init_kernel(int E, int C, unsigned long long* __rest
 }
 
 template <bool BAKED>
-__global__ __launch_bounds__(BLOCK) void volume_edit_kernel(const uint8_t* __restrict__ labels, const uint4* __restrict__ cells, EditBox box,
-                                                            int C, LabelMask keep, LabelMask gone, EditEntries ent, int E, int rule,
+__global__ __launch_bounds__(BLOCK) void volume_edit_kernel(const uint8_t* __restrict__ labels, const uint4* __restrict__ cells, GridBox box,
+                                                            int C, LabelMask128 keep, LabelMask128 gone, EditEntries ent, int E, int rule,
                                                             uint8_t* __restrict__ out_labels, uint4* __restrict__ out_cells,
                                                             uint8_t* __restrict__ out_source, unsigned long long* __restrict__ won,
                                                             unsigned long long* __restrict__ claimed,
@@ -112,6 +97,7 @@ __global__ __launch_bounds__(BLOCK) void volume_edit_kernel(const uint8_t* __res
             int c[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
+                // (not grid_cell_of: f < 2^31 and then the INTEGER against the dim is another predicate where a dim above 2^24 is no f32)
                 const float f = floorf((q[a] - box.lo[a]) * box.inv_cell[a]);
                 const bool in = f >= 0.f && f < 2147483648.f;                       // (false for NaN)
                 c[a] = in ? (int)f : 0;
@@ -188,14 +174,12 @@ extern "C" int32_t dmnerf_volume_edit(const uint8_t* d_labels, const float* d_ce
                                   const float inv_cell[3], const int dims[3], int C, const uint32_t keep[4],
                                   const dmnerf_volume_edit_entry* entries, int E, int rule, uint8_t* d_out_labels, float* d_out_cells,
                                   uint8_t* d_out_source, int64_t* d_won, int64_t* d_claimed, int64_t* d_hits, void* stream) {
-    if (!lo || !cell || !inv_cell || !dims || !keep) return dmn_fail(DMNERF_E_ARG, "volume_edit: null host array");
-    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1)
-        return dmn_fail(DMNERF_E_ARG, "volume_edit: bad dims %d x %d x %d", dims[0], dims[1], dims[2]);
-    const int64_t total = (int64_t)dims[0] * dims[1] * dims[2];
-    if (total >= (1LL << 31)) return dmn_fail(DMNERF_E_ARG, "volume_edit: %lld cells do not fit int32", (long long)total);
-    if (C < 1 || C > DMNERF_MAX_LOGITS) return dmn_fail(DMNERF_E_ARG, "volume_edit: C=%d outside 1..%d", C, DMNERF_MAX_LOGITS);
-    if (E < 0 || E > MAX_E) return dmn_fail(DMNERF_E_ARG, "volume_edit: E=%d outside 0..%d", E, MAX_E);
-    if (E > 0 && !entries) return dmn_fail(DMNERF_E_ARG, "volume_edit: null entries");
+    if (!cell || !keep) return dmn_fail(DMNERF_E_ARG, "volume_edit: null host array");
+    GridBox box;
+    int64_t total;
+    if (int rc = dmn_grid_given("volume_edit", lo, cell, inv_cell, dims, &box, &total)) return rc;
+    if (int rc = dmn_check_labels("volume_edit", C)) return rc;
+    if (int rc = dmn_edit_count_given("volume_edit", E, entries)) return rc;
     if (rule != 0 && rule != 1) return dmn_fail(DMNERF_E_ARG, "volume_edit: rule %d is neither 0 (first) nor 1 (densest)", rule);
     if (rule == 1 && !d_cells) return dmn_fail(DMNERF_E_ARG, "volume_edit: rule 1 (densest) needs d_cells");
     if (!d_labels || !d_out_labels || !d_out_source || !d_won || (E > 0 && (!d_claimed || !d_hits)))      // (E == 0: two empty outputs)
@@ -214,22 +198,11 @@ extern "C" int32_t dmnerf_volume_edit(const uint8_t* d_labels, const float* d_ce
                 overlap(region[a].p, region[a].n, region[b].p, region[b].n))
                 return dmn_fail(DMNERF_E_ARG, "volume_edit: a destination overlaps a source or another destination (arguments %d and %d)", a, b);
     EditEntries ent = {};
-    LabelMask k, gone = {{0u, 0u, 0u, 0u}};
+    if (int rc = dmn_edit_entries_given("volume_edit", entries, E, C, ent.e)) return rc;
+    LabelMask128 k, gone = {{0u, 0u, 0u, 0u}};
     for (int q = 0; q < 4; ++q) k.w[q] = keep[q];
-    for (int e = 0; e < E; ++e) {
-        const dmnerf_volume_edit_entry& s = entries[e];
-        if (s.kind < 0 || s.kind > 2) return dmn_fail(DMNERF_E_ARG, "volume_edit: entry %d has kind %d (0 move, 1 copy, 2 remove)", e, s.kind);
-        if (s.label < 0 || s.label >= C) return dmn_fail(DMNERF_E_ARG, "volume_edit: entry %d has label %d outside [0, %d)", e, s.label, C);
-        ent.e[e] = s;
-        if (s.kind != KIND_COPY) gone.w[s.label >> 5] |= 1u << (s.label & 31);
-    }
-    EditBox box;
-    for (int a = 0; a < 3; ++a) {
-        box.lo[a] = lo[a];
-        box.cell[a] = cell[a];
-        box.inv_cell[a] = inv_cell[a];
-        box.dims[a] = dims[a];
-    }
+    for (int e = 0; e < E; ++e)
+        if (ent.e[e].kind != KIND_COPY) gone.w[ent.e[e].label >> 5] |= 1u << (ent.e[e].label & 31);
     const int n_init = E * C > E + 1 ? E * C : E + 1;
     hipLaunchKernelGGL(volume_edit_init_kernel, dim3((unsigned)((n_init + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, E, C,
                        reinterpret_cast<unsigned long long*>(d_won), reinterpret_cast<unsigned long long*>(d_claimed),

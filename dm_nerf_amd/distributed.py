@@ -784,13 +784,12 @@ class ManipulationFrameRenderer:
             self._skip = (skip, render.check_skip_levels("ManipulationFrameRenderer", skip_levels))
         self.manipulate_chunk = manipulate_chunk or _default_manipulate_chunk
         self.draws = draws or _default_draws
-        from .editing import Copy, Deform, edit_kind
+        from .editing import Copy, Deform, check_edit_lengths, edit_kind
         kinds = [edit_kind(trans) for trans in trans_list]
         if len(kinds) == 0 and keep_labels is None and field_edit is None:
             raise ValueError("ManipulationFrameRenderer: at least one transformation")
         if any(kinds) or keep_labels is not None:                   # removals, copies, a keep set: manipulator()'s edit path
-            if len(self.args.target_labels) != len(kinds):
-                raise ValueError(f"ManipulationFrameRenderer: {len(self.args.target_labels)} target labels for {len(kinds)} edits")
+            check_edit_lengths("ManipulationFrameRenderer", len(kinds), len(self.args.target_labels))
             self.args.edit_kinds = kinds
             self.args.keep_labels = None if keep_labels is None else [int(l) for l in keep_labels]
         # only MOVE and COPY entries have target rays (and draws): a removal reads no target

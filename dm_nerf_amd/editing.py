@@ -244,6 +244,47 @@ def edit_label_sets(C, target_labels, kinds, keep_labels=None):
     return sorted(allowed - gone), [[int(l)] if (k != 2 and int(l) in allowed) else [] for l, k in zip(target_labels, kinds)]
 
 
+def check_edit_lengths(who, n_edits, n_labels):
+    """One target label per edit, or ``ValueError`` in ``who``'s name."""
+    if n_edits != n_labels:
+        raise ValueError(f"{who}: {n_labels} target labels for {n_edits} edits")
+
+
+class EditList:
+    """One edit list, normalised and checked in ``who``'s name before anything touches a device: ``trans_list`` / ``target_labels`` of
+    equal lengths, at most ``max_edits`` entries (``too_many`` ends that sentence), every target label and every label of
+    ``keep_labels`` in ``[0, C)`` (``C = None``: the caller has checks of its own to make first and calls ``check_labels(C)`` after
+    them).  Holds ``trans_list``, ``target_labels`` (ints), ``kinds`` (``edit_kind`` per entry), ``keep`` (the sorted keep set, or
+    ``None``), ``E`` and ``C``."""
+
+    def __init__(self, who, trans_list, target_labels, C, keep_labels=None, max_edits=None, too_many=""):
+        self.who, self.C = who, None
+        self.trans_list, self.target_labels = list(trans_list), [int(l) for l in target_labels]
+        self.E = len(self.trans_list)
+        check_edit_lengths(who, self.E, len(self.target_labels))
+        if max_edits is not None and self.E > max_edits:
+            raise ValueError(f"{who}: {self.E} edits, at most {max_edits}{too_many}")
+        self.keep = None if keep_labels is None else sorted({int(l) for l in keep_labels})
+        self.kinds = [edit_kind(trans) for trans in self.trans_list]
+        if C is not None:
+            self.check_labels(C)
+
+    def check_labels(self, C):
+        """Every target label and every kept label lies in ``[0, C)``; sets ``C``."""
+        for l in self.target_labels + (self.keep or []):
+            if not 0 <= l < C:
+                raise ValueError(f"{self.who}: label {l} outside [0, {C})")
+        self.C = C
+
+    def label_sets(self):
+        """``edit_label_sets`` of this list -> ``(own, per_entry)``."""
+        return edit_label_sets(self.C, self.target_labels, self.kinds, self.keep)
+
+    def entries(self, what_for):
+        """``pack_entries`` of this list: the ``dmnerf_volume_edit_entry`` structs, ``None`` for an empty list."""
+        return pack_entries(self.who, self.trans_list, self.target_labels, what_for)
+
+
 def _preview_sets(who, label_grid, H, W, K, pose, trans_list, target_labels, keep_labels, max_sets=None):
     """The rays and label sets of an edit preview (``preview_frame``'s docstring) -> ``(rays [R, 2, H W, 3], R label sets)``: set 0 the
     original rays of ``ManipulationFrameRenderer`` with every label but those of MOVE and REMOVE entries, set ``1 + e`` the target rays
@@ -251,14 +292,8 @@ def _preview_sets(who, label_grid, H, W, K, pose, trans_list, target_labels, kee
     raise ``ValueError``.  The argument checks come before anything touches a device."""
     import types
     C = label_grid.C
-    trans_list, target_labels = list(trans_list), [int(l) for l in target_labels]
-    if len(trans_list) != len(target_labels):
-        raise ValueError(f"{who}: {len(target_labels)} target labels for {len(trans_list)} edits")
-    keep = None if keep_labels is None else sorted({int(l) for l in keep_labels})
-    for l in target_labels + (keep or []):
-        if not 0 <= l < C:
-            raise ValueError(f"{who}: label {l} outside [0, {C})")
-    kinds = [edit_kind(trans) for trans in trans_list]
+    edits = EditList(who, trans_list, target_labels, C, keep_labels)
+    trans_list, target_labels, keep, kinds = edits.trans_list, edits.target_labels, edits.keep, edits.kinds
     with_rays = sum(k != 2 for k in kinds)
     if max_sets is not None and 1 + with_rays > max_sets:
         raise ValueError(f"{who}: {with_rays} edits with rays, at most {max_sets - 1} (one launch composites {max_sets} ray sets)")
@@ -268,7 +303,7 @@ def _preview_sets(who, label_grid, H, W, K, pose, trans_list, target_labels, kee
                                      keep_labels=keep if (keep is not None or trans_list) else ())
     if fr.ori.device != label_grid.labels.device:
         raise RuntimeError(f"{who}: the label volume lives on another device than the rays")
-    own, per_entry = edit_label_sets(C, target_labels, kinds, keep)
+    own, per_entry = edits.label_sets()
     sets = [own] + [s for s, k in zip(per_entry, kinds) if k != 2]
     rays = torch.cat([fr.ori[None], fr.tar], dim=0) if fr.T else fr.ori[None]
     return rays, sets
@@ -405,21 +440,15 @@ def edit_volume(grid, trans_list, target_labels, keep_labels=None, rule="first",
         raise TypeError(f"{who}: grid must be a field.LabelGrid or a field.BakedGrid")
     baked = isinstance(grid, field.BakedGrid)
     C = grid.C
-    trans_list, target_labels = list(trans_list), [int(l) for l in target_labels]
-    if len(trans_list) != len(target_labels):
-        raise ValueError(f"{who}: {len(target_labels)} target labels for {len(trans_list)} edits")
-    E = len(trans_list)
-    if E > MAX_VOLUME_EDITS:
-        raise ValueError(f"{who}: {E} edits, at most {MAX_VOLUME_EDITS} in one call (apply the rest to the result)")
+    edits = EditList(who, trans_list, target_labels, None, keep_labels, MAX_VOLUME_EDITS, " in one call (apply the rest to the result)")
+    E = edits.E
     if rule not in VOLUME_RULES:
         raise ValueError(f"{who}: rule must be 'first' or 'densest', got {rule!r}")
     if rule == "densest" and not baked:
         raise ValueError(f"{who}: rule='densest' compares baked densities: it needs a field.BakedGrid, not a plain LabelGrid")
-    keep = range(C) if keep_labels is None else sorted({int(l) for l in keep_labels})
-    for l in target_labels + list(keep if keep_labels is not None else ()):
-        if not 0 <= l < C:
-            raise ValueError(f"{who}: label {l} outside [0, {C})")
-    entries = pack_entries(who, trans_list, target_labels, "resample the volume under (preview_frame / render_preview take it)")
+    edits.check_labels(C)
+    keep = range(C) if edits.keep is None else edits.keep
+    entries = edits.entries("resample the volume under (preview_frame / render_preview take it)")
     src_cells = grid.cells if baked else None
     if out is not None:
         if out is not grid and (type(out) is not type(grid) or out.dims != grid.dims or out.C != C or not np.array_equal(out.lo, grid.lo)
@@ -438,8 +467,7 @@ def edit_volume(grid, trans_list, target_labels, keep_labels=None, rule="first",
     res = {"grid": out, "source": torch.empty(grid.dims, dtype=torch.uint8, device=dev),
            "won": torch.empty(1 + E, dtype=torch.int64, device=dev), "claimed": torch.empty(E, dtype=torch.int64, device=dev),
            "hits": torch.empty(E, C, dtype=torch.int64, device=dev)}
-    f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
-    _lib.launch("dmnerf_volume_edit", grid.labels, src_cells, f3(grid.lo), f3(grid.cell), f3(grid.inv_cell), (ctypes.c_int * 3)(*grid.dims), C,
+    _lib.launch("dmnerf_volume_edit", grid.labels, src_cells, *_lib.box_args(grid), C,
                 (ctypes.c_uint32 * 4)(*field.label_mask_words(keep, C)), entries, E, VOLUME_RULES[rule], out.labels,
                 out.cells if baked else None, res["source"], res["won"], res["claimed"], res["hits"])
     return res
@@ -487,18 +515,9 @@ class FieldEdit:
         self.dims = field._dims3(tuple(source.shape))
         self.lo, self.hi, self.cell, self.inv_cell = field._box(who, lo, hi, self.dims)
         self.source, self.outside, self.unowned, self.volume = source, outside, unowned, volume
-        trans_list, self.target_labels = list(trans_list), [int(l) for l in target_labels]
-        if len(trans_list) != len(self.target_labels):
-            raise ValueError(f"{who}: {len(self.target_labels)} target labels for {len(trans_list)} edits")
-        self.E = len(trans_list)
-        if self.E > MAX_VOLUME_EDITS:
-            raise ValueError(f"{who}: {self.E} edits, at most {MAX_VOLUME_EDITS}")
-        self.keep_labels = None if keep_labels is None else sorted({int(l) for l in keep_labels})
-        for l in self.target_labels + (self.keep_labels or []):
-            if not 0 <= l < self.C:
-                raise ValueError(f"{who}: label {l} outside [0, {self.C})")
-        self.kinds = [edit_kind(trans) for trans in trans_list]
-        self.entries = pack_entries(who, trans_list, self.target_labels, "carry a sample back under")
+        edits = EditList(who, trans_list, target_labels, self.C, keep_labels, MAX_VOLUME_EDITS)
+        self.target_labels, self.E, self.keep_labels, self.kinds = edits.target_labels, edits.E, edits.keep, edits.kinds
+        self.entries = edits.entries("carry a sample back under")
         self.masks = (ctypes.c_uint32 * (4 * (1 + self.E)))(*field_edit_masks(self.C, self.target_labels, self.kinds, self.keep_labels))
 
     @classmethod

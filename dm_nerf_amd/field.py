@@ -408,6 +408,17 @@ def _box(who, lo, hi, dims):
     return lo, hi, cell, np.float32(1.0) / cell
 
 
+def _ray_pair(who, rays_o, rays_d):
+    """``rays_o``, ``rays_d [N, 3]`` f32 on the device, checked in ``who``'s name -> one ray set ``[2, N, 3]``."""
+    for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be a float32 tensor")
+    _lib.require_gpu(rays_o, rays_d)
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
+        raise ValueError(f"{who} expects rays_o, rays_d [N, 3], got {tuple(rays_o.shape)} and {tuple(rays_d.shape)}")
+    return torch.stack([rays_o, rays_d])
+
+
 def _axis_centres(grid, a, n0, n1, dev):
     """The centres of cells ``n0 .. n1 - 1`` of ``grid`` along axis ``a`` on ``dev`` (f32 ops, one rounding each)."""
     return (torch.arange(n0, n1, dtype=torch.float32, device=dev) + 0.5) * float(grid.cell[a]) + float(grid.lo[a])
@@ -461,8 +472,7 @@ class SkipGrid:
     def c_struct(self):
         """The ``dmnerf_skip_grid`` of this grid (points into ``bits``)."""
         g = _lib.SkipGridArgs()
-        for a in range(3):
-            g.lo[a], g.inv_cell[a], g.dims[a] = float(self.lo[a]), float(self.inv_cell[a]), self.dims[a]
+        g.lo, _, g.inv_cell, g.dims = _lib.box_args(self)
         g.outside = SKIP_OUTSIDE[self.outside]
         g.d_bits = self.bits.data_ptr()
         return g
@@ -837,21 +847,14 @@ class LabelGrid:
         dev = rays.device
         out = {"label": torch.empty(N, dtype=torch.uint8, device=dev), "t": torch.empty(N, dtype=torch.float32, device=dev),
                "cell": torch.empty(N, dtype=torch.int32, device=dev), "source": torch.empty(N, dtype=torch.uint8, device=dev)}
-        f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
-        _lib.launch("dmnerf_label_trace", self.labels, f3(self.lo), f3(self.cell), f3(self.inv_cell), (ctypes.c_int * 3)(*self.dims), self.C, rays, R,
-                    N, (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), out["label"], out["t"], out["cell"], out["source"])
+        _lib.launch("dmnerf_label_trace", self.labels, *_lib.box_args(self), self.C, rays, R, N,
+                    (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), out["label"], out["t"], out["cell"], out["source"])
         return out
 
     def trace(self, rays_o, rays_d, near, far, labels=None):
         """``trace_sets`` with one ray set: ``rays_o``, ``rays_d [N, 3]`` f32 -> ``{"label", "t", "cell"}``.  ``labels``: an int or an
         iterable as in ``skip_grid``; the default is every label ``0 .. C - 1``."""
-        for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
-            if not torch.is_tensor(t) or t.dtype != torch.float32:
-                raise ValueError(f"LabelGrid.trace: {name} must be a float32 tensor")
-        _lib.require_gpu(rays_o, rays_d)
-        if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
-            raise ValueError(f"LabelGrid.trace expects rays_o, rays_d [N, 3], got {tuple(rays_o.shape)} and {tuple(rays_d.shape)}")
-        out = self.trace_sets(torch.stack([rays_o, rays_d])[None], [range(self.C) if labels is None else labels], near, far)
+        out = self.trace_sets(_ray_pair("LabelGrid.trace", rays_o, rays_d)[None], [range(self.C) if labels is None else labels], near, far)
         del out["source"]
         return out
 
@@ -909,18 +912,11 @@ class BakedGrid(LabelGrid):
         out = {"rgb": torch.empty(N, 3, dtype=torch.float32, device=dev), "depth": torch.empty(N, dtype=torch.float32, device=dev),
                "acc": torch.empty(N, dtype=torch.float32, device=dev), "label": torch.empty(N, dtype=torch.uint8, device=dev),
                "source": torch.empty(N, dtype=torch.uint8, device=dev), "nseg": torch.empty(N, dtype=torch.int32, device=dev)}
-        f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
-        _lib.launch("dmnerf_baked_render", self.labels, self.cells, f3(self.lo), f3(self.cell), f3(self.inv_cell), (ctypes.c_int * 3)(*self.dims),
-                    self.C, rays, R, N, (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), stop, out["rgb"], out["depth"], out["acc"],
+        _lib.launch("dmnerf_baked_render", self.labels, self.cells, *_lib.box_args(self), self.C,
+                    rays, R, N, (ctypes.c_uint32 * (4 * R))(*words), float(near), float(far), stop, out["rgb"], out["depth"], out["acc"],
                     out["label"], out["source"], out["nseg"])
         return out
 
     def render(self, rays_o, rays_d, near, far, labels=None, stop=0.0):
         """``render_sets`` with one ray set: ``rays_o``, ``rays_d [N, 3]`` f32; ``labels`` as in ``trace`` (default: every label)."""
-        for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
-            if not torch.is_tensor(t) or t.dtype != torch.float32:
-                raise ValueError(f"BakedGrid.render: {name} must be a float32 tensor")
-        _lib.require_gpu(rays_o, rays_d)
-        if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
-            raise ValueError(f"BakedGrid.render expects rays_o, rays_d [N, 3], got {tuple(rays_o.shape)} and {tuple(rays_d.shape)}")
-        return self.render_sets(torch.stack([rays_o, rays_d])[None], [range(self.C) if labels is None else labels], near, far, stop)
+        return self.render_sets(_ray_pair("BakedGrid.render", rays_o, rays_d)[None], [range(self.C) if labels is None else labels], near, far, stop)

@@ -201,13 +201,12 @@ def run_network_edited(model, rays_o, rays_d, z_vals, edit, split=None, counts=N
     raw = torch.empty(N, S, 4 + C, dtype=torch.float32, device=dev)
     if M == 0:
         return raw
-    import ctypes
     sel, owner, work = select_buffers(M, dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     o_w, d_w = torch.empty(M, 3, dtype=torch.float32, device=dev), torch.empty(M, 3, dtype=torch.float32, device=dev)
     fill = empty_row(C, dev)
-    f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
-    _lib.launch("dmnerf_field_edit_select", edit.source, f3(edit.lo), f3(edit.inv_cell), (ctypes.c_int * 3)(*edit.dims),
+    lo, _, inv_cell, dims = _lib.box_args(edit)
+    _lib.launch("dmnerf_field_edit_select", edit.source, lo, inv_cell, dims,
                 editing.FIELD_POLICIES[edit.outside], editing.FIELD_POLICIES[edit.unowned], edit.entries, edit.E, C, rays_o, rays_d, z, N, S,
                 owner, o_w, d_w, sel, count, work, raw, fill, counts)
     if split == "f16x2":

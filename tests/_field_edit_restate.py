@@ -8,6 +8,7 @@ rows are the 3 x 4 map (ignored for REMOVE).  Policies: 0 EVALUATE (owner 0), 1 
 import numpy as np
 
 import _volume_edit_restate as V
+from _grid_restate import cells_f32
 
 f32 = np.float32
 NOBODY = 255
@@ -31,20 +32,6 @@ def accept_masks(C, entries, keep=None):
     for k, l, _ in entries:
         rows.append(V.mask_words([int(l)] if (k != REMOVE and int(l) in keep) else [], C))
     return np.asarray(rows, dtype=np.uint32).reshape(1 + len(entries), 4)
-
-
-def cells_f32(rays_o, rays_d, z, lo, inv_cell, dims):
-    """``dmnerf_skip_select``'s arithmetic -> ``(inside [N,S] bool, flat cell [N,S] int64 (0 where outside))``."""
-    o, d, z = np.asarray(rays_o, f32), np.asarray(rays_d, f32), np.asarray(z, f32)
-    inside = np.ones(z.shape, dtype=bool)
-    g = np.zeros(z.shape, dtype=np.int64)
-    with np.errstate(all="ignore"):
-        for a in range(3):
-            p = (o[:, a:a + 1] + (d[:, a:a + 1] * z).astype(f32)).astype(f32)
-            c = np.floor(((p - f32(lo[a])).astype(f32) * f32(inv_cell[a])).astype(f32))
-            inside &= (c >= 0) & (c < f32(dims[a]))
-            g = g * dims[a] + np.where(inside, c, 0).astype(np.int64)
-    return inside, np.where(inside, g, 0)
 
 
 def owners(source, inside, g, entries, outside, unowned):

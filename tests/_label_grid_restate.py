@@ -3,6 +3,7 @@ reduction with the quantities ``LabelGrid.stats()`` derives from it, the bits of
 label points.  Loops and array ops only: nothing here shares code with the product."""
 import numpy as np
 
+import _grid_restate as G
 import _skip_restate as RS
 
 F = np.float32
@@ -65,11 +66,8 @@ def derived(count, index_sum, lo_idx, hi_idx, lo, hi, dims):
 
 
 def mask_words(labels):
-    """Label ``l`` -> bit ``l & 31`` of word ``l >> 5`` of four uint32 words."""
-    words = [0, 0, 0, 0]
-    for l in ([labels] if np.ndim(labels) == 0 else labels):
-        words[int(l) >> 5] |= 1 << (int(l) & 31)
-    return words
+    """``_grid_restate.mask_words`` of one label or an iterable of labels below 128."""
+    return G.mask_words([labels] if np.ndim(labels) == 0 else labels, 128)
 
 
 def skip_words(labels, words4):

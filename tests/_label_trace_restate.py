@@ -6,34 +6,18 @@ still walking as a mask.  ``referee`` sorts plane crossings in float64 and looks
 """
 import numpy as np
 
+import _grid_restate as G
+from _grid_restate import _in_mask, mask_words
+
 f32 = np.float32
 UNLABELLED = 255
 INF = f32(np.inf)
 
 
 def grid_consts(lo, hi, dims):
-    """``lo, cell, inv_cell`` (float32 [3]) and ``dims`` as ``field.SkipGrid`` / ``field.LabelGrid`` compute them on the host."""
-    lo = np.asarray(lo, dtype=f32).reshape(3)
-    hi = np.asarray(hi, dtype=f32).reshape(3)
+    """``_grid_restate.grid_consts`` and ``dims`` as a tuple of ints: the four things a trace case carries around."""
     dims = tuple(int(d) for d in dims)
-    cell = (hi - lo) / np.asarray(dims, dtype=f32)
-    inv_cell = f32(1.0) / cell
-    return lo, cell, inv_cell, dims
-
-
-def mask_words(labels, C):
-    """``field.label_mask_words``: label l is bit l & 31 of word l >> 5."""
-    w = [0, 0, 0, 0]
-    for l in labels:
-        assert 0 <= int(l) < C
-        w[int(l) >> 5] |= 1 << (int(l) & 31)
-    return w
-
-
-def _in_mask(l, words):
-    """labels (int64 array) -> bool: bit l of the 128-bit mask, False for l >= 128."""
-    words = np.asarray(list(words) + [0, 0, 0, 0], dtype=np.uint64)
-    return ((words[np.minimum(l >> 5, 4)] >> (l & 31).astype(np.uint64)) & np.uint64(1)) != 0
+    return (*G.grid_consts(lo, hi, dims), dims)
 
 
 def nan_min(x, y):

@@ -4,31 +4,24 @@ operations in the stated order); the dilation works on the words themselves, bit
 one to f32 on its own) and loops: nothing here shares code with the product."""
 import numpy as np
 
-from _skip_restate import grid_consts, pack_bits, unpack_bits
+from _grid_restate import cells_f32, grid_consts
+from _skip_restate import pack_bits, unpack_bits
 
 F = np.float32
 
 
 def mark(words, rays_o, rays_d, z, weights, lo, hi, dims, threshold=0.0):
     """-> new uint32 words = ``words`` OR the bit of the cell of every sample ``(n, s)`` that is inside the box and whose weight is
-    not ``<= threshold`` (so NaN marks).  ``p = o + d * z`` (multiply, then add, each rounded to f32), ``c = floor((p - lo) *
-    inv_cell)`` (subtract, multiply, each rounded), inside iff ``0 <= c < dims`` on the float for all axes (a NaN point is outside).
-    A sample outside the box marks nothing; a set bit is never cleared."""
+    not ``<= threshold`` (so NaN marks).  The cell of a sample is ``_grid_restate.cells_f32`` (a NaN point is outside).  A sample
+    outside the box marks nothing; a set bit is never cleared."""
     lo, _, inv = grid_consts(lo, hi, dims)
     o, d, z, w = (np.asarray(t, dtype=F) for t in (rays_o, rays_d, z, weights))
     out = np.array(words, dtype=np.uint32, copy=True)
     assert out.shape == ((dims[0] * dims[1] * dims[2] + 31) // 32,)
     assert w.shape == z.shape and o.shape == d.shape == (z.shape[0], 3)
-    hit = ~(w <= F(threshold))                                        # NaN: marks
-    g = np.zeros(z.shape, dtype=np.int64)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for a in range(3):                                           # float32 arrays: numpy rounds every operation to f32 on its own
-            p = o[:, a:a + 1] + d[:, a:a + 1] * z
-            c = np.floor((p - lo[a]) * inv[a])
-            assert p.dtype == F and c.dtype == F
-            ok = (c >= 0) & (c < F(dims[a]))
-            hit &= ok
-            g = g * dims[a] + np.where(ok, c, F(0)).astype(np.int64)
+    inside, g = cells_f32(o, d, z, lo, inv, dims)
+    with np.errstate(invalid="ignore"):
+        hit = ~(w <= F(threshold)) & inside                          # NaN: marks
     for cell in np.unique(g[hit]):
         out[cell >> 5] |= np.uint32(1) << np.uint32(cell & 31)
     return out

@@ -3,14 +3,9 @@ clipped dilation, bit packing), the select (float32 operations in the stated ord
 the masking of rows.  Loops and array ops only: nothing here shares code with the product."""
 import numpy as np
 
+from _grid_restate import cells_f32, grid_consts
+
 F = np.float32
-
-
-def grid_consts(lo, hi, dims):
-    """``cell = float32(hi - lo) / float32(dims)``, ``inv_cell = float32(1) / cell`` (one rounding each)."""
-    lo, hi = np.asarray(lo, dtype=F), np.asarray(hi, dtype=F)
-    cell = (hi - lo) / np.asarray(dims, dtype=F)
-    return lo, cell.astype(F), (F(1.0) / cell).astype(F)
 
 
 def occupied(sigma, threshold):
@@ -79,26 +74,13 @@ def cell_centres(lo, hi, dims):
 
 
 def select(rays_o, rays_d, z, words, lo, hi, dims, outside="evaluate"):
-    """-> ``(flag [N,S] uint8, sel int32 ascending, count)``.  ``p = o + d * z`` (multiply, then add, each rounded to f32),
-    ``c = floor((p - lo) * inv_cell)`` (subtract, multiply, each rounded), inside iff ``0 <= c < dims`` on the float for all axes
-    (a NaN point is outside); inside: the cell's bit; outside: 1 for ``"evaluate"``, 0 for ``"empty"``."""
+    """-> ``(flag [N,S] uint8, sel int32 ascending, count)``.  The cell of a sample is ``_grid_restate.cells_f32``; inside: the
+    cell's bit; outside (a NaN point included): 1 for ``"evaluate"``, 0 for ``"empty"``."""
     assert outside in ("evaluate", "empty")
     lo, _, inv = grid_consts(lo, hi, dims)
-    o, d, z = np.asarray(rays_o, dtype=F), np.asarray(rays_d, dtype=F), np.asarray(z, dtype=F)
-    N, S = z.shape
-    occ = unpack_bits(words, dims)
-    flag = np.zeros((N, S), dtype=np.uint8)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for n in range(N):
-            for s in range(S):
-                inside, idx = True, []
-                for a in range(3):
-                    p = F(o[n, a] + F(d[n, a] * z[n, s]))
-                    c = np.floor(F(F(p - lo[a]) * inv[a]))
-                    ok = bool(c >= 0) and bool(c < F(dims[a]))
-                    inside = inside and ok
-                    idx.append(int(c) if ok else 0)
-                flag[n, s] = (1 if occ[idx[0], idx[1], idx[2]] else 0) if inside else (1 if outside == "evaluate" else 0)
+    inside, g = cells_f32(rays_o, rays_d, z, lo, inv, dims)
+    occ = unpack_bits(words, dims).reshape(-1)
+    flag = np.where(inside, occ[g], outside == "evaluate").astype(np.uint8)
     sel = np.nonzero(flag.reshape(-1))[0].astype(np.int32)
     return flag, sel, int(sel.size)
 

@@ -9,32 +9,11 @@ are the 3 x 4 map (ignored for REMOVE).  The matrix maps the centre of a DESTINA
 """
 import numpy as np
 
+from _grid_restate import _in_mask, grid_consts, mask_words
+
 f32 = np.float32
 UNLABELLED = 255
 MOVE, COPY, REMOVE = 0, 1, 2
-
-
-def grid_consts(lo, hi, dims):
-    """``lo, cell, inv_cell`` (float32 [3]) as ``field.LabelGrid`` computes them on the host."""
-    lo, hi = np.asarray(lo, dtype=f32).reshape(3), np.asarray(hi, dtype=f32).reshape(3)
-    cell = (hi - lo) / np.asarray(dims, dtype=f32)
-    return lo, cell, f32(1.0) / cell
-
-
-def mask_words(labels, C):
-    """``field.label_mask_words``: label l is bit l & 31 of word l >> 5."""
-    w = [0, 0, 0, 0]
-    for l in labels:
-        assert 0 <= l < C
-        w[l >> 5] |= 1 << (l & 31)
-    return w
-
-
-def _in_mask(l, words):
-    """labels (int64 array or int) -> bool: bit l of the 128-bit mask, False for l >= 128."""
-    l = np.asarray(l, dtype=np.int64)
-    words = np.asarray(list(words) + [0], dtype=np.uint64)
-    return ((words[np.minimum(l >> 5, 4)] >> (l & 31).astype(np.uint64)) & np.uint64(1)) != 0
 
 
 def matrix_f32(m):
