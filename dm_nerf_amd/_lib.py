@@ -196,6 +196,10 @@ SIGNATURES = {
     "dmnerf_surface_clusters": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_surface_clean_mark": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_surface_clean_compact": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_object_surface_count": (ctypes.c_int32, [c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_uint32), c_float, c_int, c_vp, c_vp, c_vp]),
+    "dmnerf_object_surface_emit": (ctypes.c_int32, [c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_uint32), c_float, c_int, c_vp, c_vp, c_vp,
+                                           c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_object_surface_measures": (ctypes.c_int32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, ctypes.POINTER(c_double), c_vp, c_vp, c_vp]),
     "dmnerf_skip_grid_build": (c_int, [c_vp, c_int, c_int, c_int, c_float, c_int, c_vp, c_vp]),
     "dmnerf_skip_select_work_ints": (c_i64, [c_i64]),
     "dmnerf_skip_select": (c_int, [ctypes.POINTER(SkipGridArgs), c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -13,6 +13,7 @@ This is the reference's ``mesh_main`` (tools/mesh_generator.py:12-143) without i
     :89, :140                  the two .ply files                                                            ->  ``write_ply`` (host)
 
 The surface stages are csrc/surface.hip; only the vertex and triangle totals that size the outputs reach the host.
+``object_surfaces`` (csrc/object_surface.hip) is :68 per object of a label volume: one closed mesh each, all in one pass.
 
 The density depends on neither the view direction nor the heads, so the grid goes through the trunk-only kernel
 (csrc/mlp_fwd_points.hip): no ``[n, 90]`` embedding, no heads, no point tensor, no ``torch.cat`` and no host copy.  Tensors
@@ -920,3 +921,170 @@ class BakedGrid(LabelGrid):
     def render(self, rays_o, rays_d, near, far, labels=None, stop=0.0):
         """``render_sets`` with one ray set: ``rays_o``, ``rays_d [N, 3]`` f32; ``labels`` as in ``trace`` (default: every label)."""
         return self.render_sets(_ray_pair("BakedGrid.render", rays_o, rays_d)[None], [range(self.C) if labels is None else labels], near, far, stop)
+
+
+# ---- one closed surface per object of a label volume (csrc/object_surface.hip; tests/_object_surface_restate.py states it in numpy)
+def _empty_objects(C, device):
+    v, f = _empty_surface(device)
+    zeros = torch.zeros(C + 1, dtype=torch.int64, device=device)
+    return v, f, zeros, zeros.clone(), torch.zeros(0, dtype=torch.int32, device=device)
+
+
+def object_surfaces(grid, value=None, level=0.45, voxel=None, labels=None, closed=True):
+    """The iso-surface of every object of ``grid`` (a ``LabelGrid`` or a ``BakedGrid``, an ``editing.edit_volume`` result included) in
+    one pass over the volume -> ``ObjectSurfaces``: all objects' meshes concatenated in ascending label.  The surface of object ``k`` is
+    DEFINED as ``extract_surface(torch.where(grid.labels == k, value, 0), level)``: the same inside rule (``v > level``, NaN outside),
+    f32 vertex formula, table, winding and order, bit for bit -- so an edge between two inside points of different labels carries two
+    vertices, one per object, and the far end of a crossing edge contributes its real value only if it carries the same label.
+    Labels ``>= C``, 255 included, own nothing.  With ``closed`` (the default) every masked field is surrounded by one virtual layer of
+    0 points -- ``extract_surface`` on the volume padded by one point on all six sides, 1 subtracted from the vertices, in the padded
+    grid's order -- so a mesh is watertight even where its object touches the box, and coordinates in ``[-1, d]`` are legal.
+
+    ``value``: f32 ``[dx, dy, dz]`` on the volume's device.  ``None``: for a ``BakedGrid`` the occupancy ``1 - exp(-relu(sigma) * voxel)``
+    of ``cells[..., 3]`` (``query_density``'s formula; ``voxel`` is then required), for a plain ``LabelGrid`` 1.0 everywhere, which gives
+    blocky surfaces half-way between cells.  ``level`` must be ``> 0`` and finite in f32 (``ValueError``).  ``labels``: an int or an
+    iterable as in ``skip_grid``; only those objects are meshed, the others get empty ranges.
+
+    What it is not: ownership is the nearest cell's, so the surfaces of neighbouring objects do not coincide (a gap of up to one cell
+    lies between them), and the table is the classic one, without Lewiner's ambiguity resolution.
+
+    ``dmnerf_object_surface_count``, two ``torch.cumsum``, ``dmnerf_object_surface_emit`` in grid order with a key ``(label << 40) |
+    position`` per vertex and triangle, two ``torch.sort`` of the (unique) keys and one ``torch.searchsorted`` that turns a corner's key
+    into its vertex id.  The host reads the two totals that size the outputs, once; for that reason the call cannot be captured in a
+    graph.  Totals of ``2^31`` or more raise; an empty result gives ``[0, 3]`` tensors and all-zero offsets.  CPU tensors raise: there
+    is no fallback."""
+    who = "object_surfaces"
+    if not isinstance(grid, LabelGrid):
+        raise TypeError(f"{who}: grid must be a LabelGrid or a BakedGrid")
+    level = float(np.float32(level))
+    if not (level > 0.0 and np.isfinite(level)):
+        raise ValueError(f"{who}: level must be > 0 and finite in float32, got {level}")
+    _lib.require_gpu(grid.labels)
+    dev, C = grid.labels.device, grid.C
+    if value is None:
+        if isinstance(grid, BakedGrid):
+            if voxel is None:
+                raise ValueError(f"{who}: a BakedGrid without value needs voxel (the occupancy is 1 - exp(-relu(sigma) * voxel))")
+            voxel = float(voxel)
+            if not voxel >= 0.0:
+                raise ValueError(f"{who}: voxel must be >= 0, got {voxel}")
+            _lib.require_gpu(grid.cells)
+            value = 1.0 - torch.exp(-torch.relu(grid.cells[..., 3]) * voxel)
+        else:
+            value = torch.ones(grid.dims, dtype=torch.float32, device=dev)
+    if not torch.is_tensor(value) or value.dtype != torch.float32 or tuple(value.shape) != tuple(grid.dims):
+        raise ValueError(f"{who}: value must be a float32 tensor {tuple(grid.dims)}, got {getattr(value, 'dtype', type(value))} "
+                         f"{tuple(getattr(value, 'shape', ()))}")
+    value = value.contiguous() if value.is_cuda else value
+    _lib.require_gpu(value)
+    if value.device != dev:
+        raise RuntimeError(f"{who}: value lives on another device than the volume")
+    mask = (ctypes.c_uint32 * 4)(*label_mask_words(range(C) if labels is None else labels, C))
+    closed = bool(closed)
+    dx, dy, dz = grid.dims
+    n = (dx + 2 * closed) * (dy + 2 * closed) * (dz + 2 * closed)
+    if n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} points (with the border) do not fit int32")
+    head = (value, grid.labels, dx, dy, dz, C, mask, level, int(closed))
+    counts = torch.empty(2, n, dtype=torch.uint8, device=dev)
+    _lib.launch("dmnerf_object_surface_count", *head, counts[0], counts[1])
+    scans = torch.cumsum(counts, dim=1, dtype=torch.int64)
+    V, F = scans[:, -1].tolist()
+    if V >= 2 ** 31 or F >= 2 ** 31:
+        raise ValueError(f"{who}: {V} vertices / {F} triangles do not fit int32 ids")
+    if V == 0:
+        return ObjectSurfaces(*_empty_objects(C, dev), grid.lo, grid.hi, grid.dims, C)
+    vkey = torch.empty(V, dtype=torch.int64, device=dev)
+    vpos = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    vcell = torch.empty(V, dtype=torch.int32, device=dev)
+    tkey = torch.empty(F, dtype=torch.int64, device=dev)
+    ckey = torch.empty(F, 3, dtype=torch.int64, device=dev)
+    _lib.launch("dmnerf_object_surface_emit", *head, counts[0], counts[1], scans[0], scans[1], V, F, vkey, vpos, vcell, tkey, ckey)
+    vkey, vorder = torch.sort(vkey)
+    tkey, torder = torch.sort(tkey)
+    faces = torch.searchsorted(vkey, ckey[torder]).to(torch.int32)
+    first = torch.arange(C + 1, dtype=torch.int64, device=dev) << 40
+    return ObjectSurfaces(vpos[vorder], faces, torch.searchsorted(vkey, first), torch.searchsorted(tkey, first), vcell[vorder],
+                          grid.lo, grid.hi, grid.dims, C)
+
+
+class ObjectSurfaces:
+    """What ``object_surfaces`` returns, all on the device: ``vertices [V, 3]`` f32 in index units (grid point ``p`` is the centre of cell
+    ``p``), ``faces [F, 3]`` int32 with GLOBAL vertex ids, ``vertex_offset`` / ``face_offset [C + 1]`` int64 (object ``k`` owns
+    ``vertices[vo[k]:vo[k + 1]]`` and ``faces[fo[k]:fo[k + 1]]``), ``vertex_cell [V]`` int32: the linear index ``(i dy + j) dz + k`` of the
+    end of the vertex's grid edge that is inside the object -- gather anything per vertex with it, the baked colour for example -- and
+    the volume's ``lo``, ``hi``, ``dims``, ``cell``, ``C``."""
+
+    def __init__(self, vertices, faces, vertex_offset, face_offset, vertex_cell, lo, hi, dims, C, normals=None, kept_vertex_index=None):
+        self.vertices, self.faces, self.vertex_offset, self.face_offset, self.vertex_cell = vertices, faces, vertex_offset, face_offset, vertex_cell
+        self.dims, self.C = _dims3(dims), int(C)
+        self.lo, self.hi, self.cell, _ = _box("ObjectSurfaces", lo, hi, self.dims)
+        self._normals = normals
+        self.kept_vertex_index = kept_vertex_index          # of ``cleaned()``: the index of every vertex in the uncleaned object
+
+    def _range(self, k):
+        k = int(k)
+        if not 0 <= k < self.C:
+            raise ValueError(f"ObjectSurfaces: label {k} outside [0, {self.C})")
+        return self.vertex_offset[k:k + 2].tolist(), self.face_offset[k:k + 2].tolist()
+
+    def object(self, k):
+        """``(vertices, faces)`` of object ``k``: a view of its vertices and its faces with local ids.  Reads the object's four
+        offsets on the host."""
+        (v0, v1), (f0, f1) = self._range(k)
+        return self.vertices[v0:v1], self.faces[f0:f1] - v0
+
+    def world_vertices(self):
+        """``lo + (v + 0.5) * cell`` in float64, rounded once to f32 (as ``scene_vertices`` does) -> ``[V, 3]``."""
+        cell = torch.as_tensor(self.cell.astype(np.float64), device=self.vertices.device)
+        lo = torch.as_tensor(self.lo.astype(np.float64), device=self.vertices.device)
+        return (lo + (self.vertices.double() + 0.5) * cell).float()
+
+    def normals(self, world=False):
+        """``vertex_normals`` of the concatenation (objects share no vertex, so it applies as it is) -> ``[V, 3]`` f32; of the
+        index-unit vertices, or with ``world`` of ``world_vertices()``, which differ where the cells are not cubes."""
+        if world:
+            return vertex_normals(self.world_vertices(), self.faces)
+        if self._normals is None:
+            self._normals = vertex_normals(self.vertices, self.faces)
+        return self._normals
+
+    def measures(self):
+        """``{"area" [C], "volume" [C]}`` float64 on the device, in world units: per object the area ``sum |(p1 - p0) x (p2 - p0)| / 2``
+        and the signed volume ``sum p0 . (p1 x p2) / 6`` of its triangles over the vertices multiplied by ``cell`` in float64
+        (``dmnerf_object_surface_measures``: one workgroup per object, a fixed summation order, the same bits every run).  The volume
+        of a closed mesh does not depend on the origin, so ``lo`` plays no part; an open mesh's is only a partial sum."""
+        dev = self.vertices.device
+        out = torch.zeros(2, self.C, dtype=torch.float64, device=dev)
+        _lib.require_gpu(self.vertices, self.faces, self.face_offset)
+        _lib.launch("dmnerf_object_surface_measures", self.vertices, self.vertices.shape[0], self.faces, self.faces.shape[0], self.face_offset,
+                    self.C, (ctypes.c_double * 3)(*[float(c) for c in self.cell]), out[0], out[1])
+        return {"area": out[0], "volume": out[1]}
+
+    def cleaned(self, min_triangles=400, keep_single_cluster=False):
+        """``clean_surface`` on the concatenation with ``normals()`` -> a new ``ObjectSurfaces`` (its ``normals()`` are the ones that
+        travelled, its ``kept_vertex_index [V']`` int64 the old global index of every vertex).  A cluster never spans two objects, so
+        ``min_triangles`` acts per object; ``keep_single_cluster`` keeps the largest cluster of the whole scene.  The offsets and
+        ``vertex_cell`` are recomputed from ``kept_vertex_index`` on the device."""
+        v, n, f, kept = clean_surface(self.vertices, self.normals(), self.faces, min_triangles=min_triangles, keep_single_cluster=keep_single_cluster)
+        vo = torch.searchsorted(kept, self.vertex_offset)                                  # kept is ascending: the vertices kept below each start
+        owner = torch.searchsorted(vo, f[:, 0].long(), right=True) - 1                     # the object of every kept triangle: ascending
+        fo = torch.searchsorted(owner, torch.arange(self.C + 1, dtype=torch.int64, device=v.device))
+        return ObjectSurfaces(v, f, vo, fo, self.vertex_cell[kept], self.lo, self.hi, self.dims, self.C, normals=n, kept_vertex_index=kept)
+
+    def write(self, pattern, colors=None):
+        """One ``write_ply`` per non-empty object (the only host step) -> the list of ``(label, path)`` written: ``pattern.format(k)`` is
+        object ``k``'s file, with ``world_vertices()``, ``normals(world=True)`` and, when given, its rows of ``colors [V, 3]`` uint8."""
+        if colors is not None and tuple(colors.shape) != tuple(self.vertices.shape):
+            raise ValueError("colors must be [V, 3]")
+        v, n = self.world_vertices(), self.normals(world=True)
+        vo, fo = self.vertex_offset.tolist(), self.face_offset.tolist()
+        written = []
+        for k in range(self.C):
+            if fo[k + 1] == fo[k]:
+                continue
+            path = pattern.format(k)
+            write_ply(path, v[vo[k]:vo[k + 1]], self.faces[fo[k]:fo[k + 1]] - vo[k], n[vo[k]:vo[k + 1]],
+                      None if colors is None else colors[vo[k]:vo[k + 1]])
+            written.append((k, path))
+        return written

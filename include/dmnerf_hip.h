@@ -1087,6 +1087,37 @@ int dmnerf_surface_clean_compact(const float* d_vertices, const float* d_normals
                                  int64_t Fk, float* d_out_vertices, float* d_out_normals, int32_t* d_out_faces, int64_t* d_out_kept,
                                  void* stream);
 
+/* ---- one closed iso-surface per object of a label volume, in one pass (tools/mesh_generator.py:68 per object; csrc/object_surface.hip)
+ * d_value [dx, dy, dz] f32 and d_labels [dx, dy, dz] uint8, row-major; every dimension >= 1.  label_mask: four host words, bit l set
+ * = object l is meshed; a label >= C (1 .. DMNERF_MAX_LOGITS), 255 included, or one whose bit is clear owns nothing.  level must be
+ * > 0 and finite (-1 otherwise).  The surface of object k is what dmnerf_surface_count / _emit give on the masked field M_k = value
+ * where labels == k, else 0: the same inside rule, vertex formula, table, winding and order.  closed = 1: M_k is surrounded by one
+ * layer of 0 points, so every mesh is watertight and coordinates lie in [-1, d]; the kernels then walk the EXTENDED grid of
+ * (dx + 2) (dy + 2) (dz + 2) points, which (like dx dy dz with closed = 0) must stay below 2^31.  All per-point arrays below are over
+ * that grid, p = (i Dy + j) Dz + k.
+ * dmnerf_object_surface_count: d_vcount [p] = vertices on the (up to) three edges that run from p along +i, +j, +k over all objects
+ *   (0..6: an edge between two inside points of different labels carries one per object); d_tcount [p] = triangles of the cell whose
+ *   lowest corner is p over all objects (0..40).  The caller forms the INCLUSIVE int64 prefix sums d_vscan / d_tscan.
+ * dmnerf_object_surface_emit: in grid order, per vertex d_vkey [V] int64 = (label << 40) | (3 p + axis), d_vpos [V, 3] f32 = the
+ *   position in index units of the real grid (i + t, t = (level - a) / (b - a) on the masked operands, then - 1 with closed), d_vcell
+ *   [V] int32 = the linear index in the real grid of the edge's end that is inside the object; per triangle d_tkey [F] int64 =
+ *   (label << 40) | (5 p + position in the table row) and d_ckey [F, 3] int64 = the d_vkey of its three corners.  The keys are
+ *   unique: sorting them gives the order (object, owning point, axis) / (object, cell, table position), and a corner's vertex id is
+ *   the rank of its key among the sorted d_vkey.
+ * dmnerf_object_surface_measures: per object k < C the area d_area [k] and the signed volume d_volume [k] in float64 of the
+ *   triangles d_face_offset [k] .. d_face_offset [k + 1] (device int64 [C + 1]) of d_faces [F, 3] over d_vertices [V, 3], every
+ *   coordinate first multiplied by the host doubles cell [3]: sum |(p1 - p0) x (p2 - p0)| / 2 and sum p0 . (p1 x p2) / 6.  One
+ *   workgroup per object, a fixed summation order, no atomics: the same bits every run.
+ * All three return the status as int32_t, as dmnerf_volume_edit does.                                                      */
+int32_t dmnerf_object_surface_count(const float* d_value, const uint8_t* d_labels, int dx, int dy, int dz, int C, const uint32_t* label_mask,
+                                float level, int closed, uint8_t* d_vcount, uint8_t* d_tcount, void* stream);
+int32_t dmnerf_object_surface_emit(const float* d_value, const uint8_t* d_labels, int dx, int dy, int dz, int C, const uint32_t* label_mask,
+                               float level, int closed, const uint8_t* d_vcount, const uint8_t* d_tcount, const int64_t* d_vscan,
+                               const int64_t* d_tscan, int64_t V, int64_t F, int64_t* d_vkey, float* d_vpos, int32_t* d_vcell,
+                               int64_t* d_tkey, int64_t* d_ckey, void* stream);
+int32_t dmnerf_object_surface_measures(const float* d_vertices, int64_t V, const int32_t* d_faces, int64_t F, const int64_t* d_face_offset,
+                                   int C, const double* cell, double* d_area, double* d_volume, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
