@@ -3,7 +3,8 @@
   1. one 640 x 480 view of ``editing.manipulate_demo_path`` with T = 2 objects (a deformation and a rigid move), ins_num 13,
      N_test 4096 -- wall time with one synchronisation at the end, and the share of it spent in ``dmnerf_edit_rays`` and
      ``frame_products``;
-  2. ``editing.frame_products`` on a 640 x 480 frame at C = 14 and C = 95 (HIP events, median of 50 warm calls) against what it
+  2. ``editing.frame_products`` on a 640 x 480 frame at C = 14 and C = 95 (HIP events, median of 50 warm calls: with an even count,
+     the mean of the two middle runs) against what it
      replaces: the float maps copied to the host, ``to8b``, ``argmax`` and the ``torch.unique`` loop of ``render_label2img``.
 
     python scripts/time_edit_frame.py [--out profiles/edit_frame/edit_frame.json]
@@ -18,27 +19,19 @@ import types
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
 
 from dm_nerf_amd import editing as E  # noqa: E402
 from dm_nerf_amd.networks import dm_nerf as M  # noqa: E402
 from oracle import ref_cpu as O  # noqa: E402
 
-H, W = 480, 640
+H, W = T.H, T.W
 
 
 def events_ms(fn, warm=5, reps=50):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    ts.sort()
-    return dict(median_ms=ts[len(ts) // 2], min_ms=ts[0], max_ms=ts[-1], reps=reps)
+    t = T.time_events(fn, reps, warm)
+    return dict(median_ms=t.median, min_ms=t.min, max_ms=t.max, reps=reps)
 
 
 def host_products(rgb, ins, rgbs, color_dict, ins_map):
@@ -92,12 +85,13 @@ def time_demo_view():
     args = types.SimpleNamespace(N_samples=64, N_importance=128, near=4.0, far=15.0, N_test=4096)
     rgbs = np.random.RandomState(1).randint(0, 256, size=(ins_num + 1, 3))
     tables = (rgbs, {str(k): k for k in range(ins_num + 1)}, {str(k): k for k in range(ins_num + 1)})
-    ts = []
+    out = {}
+
+    def view():
+        out.update(E.manipulate_demo_path(poses[1:], (H, W, K), models, args, objs, {"b": objs_trans["b"][1:]}, *tables))
+
     with torch.no_grad():
-        for i in range(3):                                     # the first one warms up
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            out = E.manipulate_demo_path(poses[1:], (H, W, K), models, args, objs, {"b": objs_trans["b"][1:]}, *tables)
-            torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
+        ts = [ms / 1e3 for ms in T.time_host(view, 3, 0).runs]  # the first one warms up
     off = np.stack([E.deform_offsets(H, "sin", 1), np.zeros(H)])
     rays = events_ms(lambda: E.edit_rays(H, W, K, poses, [1, 0], off))
     return dict(T=2, ins_num=ins_num, N_test=args.N_test, view_s=min(ts[1:]), views_s=ts, shape=list(out["rgb8"].shape),
@@ -108,6 +102,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    T.require_gpu(__file__)
     rec = dict(device=torch.cuda.get_device_name(0), frame=[H, W], demo_view=time_demo_view(), products=[time_products(C) for C in (14, 95)])
     line = json.dumps(rec)
     print(line)

@@ -3,7 +3,8 @@
   one 640 x 480 view through ``distributed.manipulate_frame``, ins_num 13, 64 + 128 samples, N_test 4096, the same models, pose
   and target label -- once with ``trans_list = [Remove()]`` (1 coarse + 2 fine launches of the original rays per chunk, 192
   samples in the final level), once with ``trans_list = [matrix]`` (T = 1: 2 coarse + 4 fine launches, 320 samples in the final
-  level).  Each is warmed up, then timed ``--reps`` times with HIP events around the whole frame; the median is reported.
+  level).  Each is warmed up, then timed ``--reps`` times with HIP events around the whole frame; the median is reported (with an
+  even ``--reps``, the mean of the two middle runs).
 
     python scripts/time_edit_kinds.py [--reps 7] [--out profiles/edit_kinds/edit_kinds.json]
 """
@@ -15,29 +16,20 @@ import types
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
 
 from dm_nerf_amd import distributed as D  # noqa: E402
 from dm_nerf_amd import editing as E  # noqa: E402
 from dm_nerf_amd.networks import dm_nerf as M  # noqa: E402
 from oracle import ref_cpu as O  # noqa: E402
 
-H, W, INS, LABEL = 480, 640, 13, 2
+H, W, INS, LABEL = T.H, T.W, 13, 2
 
 
 def frame_ms(fn, warm, reps):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    s = sorted(ts)
-    return dict(median_ms=s[len(s) // 2], min_ms=s[0], max_ms=s[-1], runs_ms=ts, warm=warm, reps=reps)
+    t = T.time_events(fn, reps, warm)
+    return dict(median_ms=t.median, min_ms=t.min, max_ms=t.max, runs_ms=t.runs, warm=warm, reps=reps)
 
 
 def main():
@@ -48,6 +40,7 @@ def main():
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps: at least 5 timed runs")
+    T.require_gpu(__file__)
     models = []
     for seed in (721, 722):
         m = M.DM_NeRF(8, 256, 63, 27, [4], INS)

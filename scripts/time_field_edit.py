@@ -11,10 +11,10 @@ T = 1 and T = 3 rigid moves, dense and with ``skip=`` the bit grid of the same l
 (moves, with a copy and a removal among them from E = 3 on) through ``FieldEdit.from_volume``; the ``edit_volume`` call is outside the
 timed window (it is made once per edit, not per frame).  Per row: HIP-event milliseconds of the whole frame, median and minimum of
 ``--iters`` runs after ``--warmup``, rays/s, the network launches per chunk, and ``n_eval`` = (samples evaluated, samples).  The first
-line records the device and its clocks as ``rocm-smi --showclocks`` reports them (read-only).  One JSON object per line.
+line records the device and its clocks as ``rocm-smi`` reports them (read-only).  One JSON object per line.
 
 ``--quality`` (the ANALYTIC scene only; no real scene is measured): the training loop of tests/test_gpu_convergence.py as
-scripts/time_baked.py runs it (``--steps`` steps on the twelve 120 x 160 views of oracle/analytic_scene.py), ``SkipGrid.from_model`` and
+scripts/time_baked.py's ``--quality`` runs it (``--steps`` steps on the twelve 120 x 160 views of oracle/analytic_scene.py), ``SkipGrid.from_model`` and
 ``bake_grid`` over [-8, 8)^3 at 128^3 per ``--sigma-threshold`` value, then on three held-out poses, with both policies ``"evaluate"``
 and with both ``"empty"``:
 
@@ -28,56 +28,25 @@ with the evaluated fraction of the field-edit frames.  The timing rows are not p
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
 import torch
 
-
-def clocks():
-    try:
-        r = subprocess.run(["rocm-smi", "--showclocks", "--json"], capture_output=True, text=True, timeout=30)
-        return json.loads(r.stdout) if r.returncode == 0 else {"error": r.stderr[-200:]}
-    except Exception as e:                                           # the tool is optional
-        return {"error": repr(e)}
-
-
-def time_steps(make, iters, warmup):
-    """``make()`` -> a frame renderer with ``n_chunks`` / ``step``; -> (median ms, min ms, the last renderer)."""
-    ms = []
-    for it in range(warmup + iters):
-        fr = make()
-        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        b.record()
-        for i in range(fr.n_chunks):
-            fr.step(i)
-        e.record()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            ms.append(b.elapsed_time(e))
-    return float(np.median(ms)), float(np.min(ms)), fr
-
-
-def rigid(k):
-    """The k-th rigid move: time_manip_skip.py's for k = 0, then others of the same size."""
-    ang = 0.2 + 0.05 * k
-    s = 1.0 if k % 2 == 0 else -1.0
-    return np.array([[np.cos(ang), -np.sin(ang), 0., 0.3 * s], [np.sin(ang), np.cos(ang), 0., -0.2 + 0.02 * k], [0., 0., 1., 0.1 * s],
-                     [0., 0., 0., 1.]], dtype=np.float64)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
 
 
 def quality(a, emit):
     import types
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from time_baked import LO, HI, train_analytic
     from dm_nerf_amd import distributed as D, editing as Ed, field as F
     from oracle import analytic_scene as S
     dev = torch.device("cuda:0")
     H, W, C = 120, 160, 14
     t0 = time.perf_counter()
-    mc, mf = train_analytic(a.steps, dev)
+    LO, HI = T.BOX
+    mc, mf = T.train_analytic(a.steps, dev)
     torch.cuda.synchronize()
     emit({"leg": "quality_setup", "scene": "analytic scene only: no real scene was measured", "train_steps": a.steps,
           "train_s": time.perf_counter() - t0, "frame": [H, W], "dims": a.dims, "box": [LO, HI]})
@@ -172,28 +141,19 @@ def main():
     ap.add_argument("--sigma-threshold", type=float, nargs="+", default=[0.0, 5.0], help="bake_grid thresholds of --quality")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_field_edit.py measures on the GPU: no device found")
-    tree = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, tree)
+    T.require_gpu(__file__)
     import types
     import bench_common as C
     from dm_nerf_amd import distributed as D, editing as Ed, field as F
-    from oracle import ref_cpu as O
     dev = torch.device("cuda")
     _, _, mc, mf = C.build_models(dev)
     ins_num = mf.ins_num
     NC = ins_num + 1
-    H, W = 480, 640
-    K = O.dmsr_intrinsics(H, W)
-    pose = O.pose_spherical(30.0, -65.0, 7.0).to(dev)
+    H, W, K, pose = T.study_view()
+    pose = pose.to(dev)
     base = dict(N_samples=64, N_importance=128, near=4.0, far=15.0, N_test=4096)
     if a.mfma_split:
         base["mfma_split"] = a.mfma_split
-    lo, hi = (-8.0, -8.0, -8.0), (8.0, 8.0, 8.0)
-    lines = [{"leg": "device", "name": torch.cuda.get_device_name(0), "clocks": clocks(), "iters": a.iters, "warmup": a.warmup,
-              "dims": a.dims, "mfma_split": a.mfma_split}]
-
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         open(a.out, "w").close()
@@ -204,14 +164,15 @@ def main():
             with open(a.out, "a") as f:
                 f.write(json.dumps(row) + "\n")
 
-    emit(lines[0])
+    emit(T.device_line(iters=a.iters, warmup=a.warmup, dims=a.dims, mfma_split=a.mfma_split))
     if a.quality:
         return quality(a, emit)
 
-    def row(leg, med, mn, fr=None, **kw):
-        r = dict(leg=leg, ms_median=med, ms_min=mn, rays_per_s=H * W / med * 1e3, **kw)
-        if fr is not None and hasattr(fr, "n_eval"):
-            n_eval = fr.n_eval.tolist()
+    def row(leg, make, counts=False, **kw):
+        t = T.time_events(T.render_chunks, a.iters, a.warmup, setup=make)
+        r = dict(leg=leg, ms_median=t.median, ms_min=t.min, rays_per_s=H * W / t.median * 1e3, **kw)
+        if counts:
+            n_eval = t.last.n_eval.tolist()
             if n_eval[1]:
                 r.update(n_eval=n_eval, evaluated_fraction=n_eval[0] / n_eval[1])
         emit(r)
@@ -221,32 +182,27 @@ def main():
 
         def frame():
             return D.FrameRenderer(H, W, K, pose, (mc, mf), 4.0, 15.0, plain, chunk=4096, n_samples=64)
-        med, mn, _ = time_steps(frame, a.iters, a.warmup)
-        row("render_frame", med, mn, launches_per_chunk=2)
+        row("render_frame", frame, launches_per_chunk=2)
 
-        def manip(T, **kw):
-            args = types.SimpleNamespace(target_labels=[2 + t for t in range(T)], **base)
+        def manip(n, **kw):
+            args = types.SimpleNamespace(target_labels=[2 + t for t in range(n)], **base)
 
             def make():
                 torch.manual_seed(7)                                 # the same draws in every run and every row
-                return D.ManipulationFrameRenderer(H, W, K, pose, [torch.tensor(rigid(t), dtype=torch.float32) for t in range(T)], (mc, mf),
+                return D.ManipulationFrameRenderer(H, W, K, pose, [torch.tensor(T.rigid(t), dtype=torch.float32) for t in range(n)], (mc, mf),
                                                    args, chunk=4096, **kw)
             return make
-        for T in a.moves:
-            med, mn, _ = time_steps(manip(T), a.iters, a.warmup)
-            row("manipulate_frame_dense", med, mn, T=T, launches_per_chunk=2 + 4 * T)
+        for n in a.moves:
+            row("manipulate_frame_dense", manip(n), T=n, launches_per_chunk=2 + 4 * n)
         for pct in a.fills:
-            rng = np.random.RandomState(pct)
-            labels = rng.randint(0, NC - 1, size=(a.dims,) * 3).astype(np.uint8)
-            labels[rng.rand(a.dims, a.dims, a.dims) >= pct / 100.0] = 255
-            grid = F.LabelGrid.from_labels(torch.from_numpy(labels).to(dev), lo, hi, NC)
+            labels = T.random_labels(pct, a.dims, NC - 1)
+            grid = F.LabelGrid.from_labels(torch.from_numpy(labels).to(dev), *T.BOX, NC)
             fill = float((labels != 255).mean())
             skip = grid.skip_grid(range(NC), outside="empty")
-            for T in a.moves:
-                med, mn, fr = time_steps(manip(T, skip=skip), a.iters, a.warmup)
-                row("manipulate_frame_skip", med, mn, fr, T=T, fill=fill, launches_per_chunk=2 + 4 * T)
+            for n in a.moves:
+                row("manipulate_frame_skip", manip(n, skip=skip), True, T=n, fill=fill, launches_per_chunk=2 + 4 * n)
             for E in a.edits:
-                trans = [Ed.Remove() if (E >= 3 and e == 2) else Ed.Copy(rigid(e)) if (E >= 3 and e == 1) else rigid(e) for e in range(E)]
+                trans = [Ed.Remove() if (E >= 3 and e == 2) else Ed.Copy(T.rigid(e)) if (E >= 3 and e == 1) else T.rigid(e) for e in range(E)]
                 targets = [e % (NC - 1) for e in range(E)]
                 edit = Ed.FieldEdit.from_volume(grid, trans, targets, outside="empty", unowned="empty")
                 args = types.SimpleNamespace(target_labels=[], **base)
@@ -254,8 +210,7 @@ def main():
                 def make():
                     torch.manual_seed(7)
                     return D.ManipulationFrameRenderer(H, W, K, pose, [], (mc, mf), args, chunk=4096, field_edit=edit)
-                med, mn, fr = time_steps(make, a.iters, a.warmup)
-                row("field_edit", med, mn, fr, E=E, fill=fill, owned=float((edit.source != 255).float().mean()), launches_per_chunk=2)
+                row("field_edit", make, True, E=E, fill=fill, owned=float((edit.source != 255).float().mean()), launches_per_chunk=2)
 
 
 if __name__ == "__main__":

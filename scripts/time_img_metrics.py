@@ -14,13 +14,13 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
+
+sys.path.insert(0, os.path.join(T.ROOT, "tests"))
 H, W, C = 480, 640, 3
 
 
@@ -41,54 +41,42 @@ def main():
     ap.add_argument("--host-iters", type=int, default=3)
     ap.add_argument("--skip-host", action="store_true")
     a = ap.parse_args()
+    T.require_gpu(__file__)
     import torch
     torch.set_num_threads(min(16, torch.get_num_threads()))
     import _img_metrics_restate as RS
     from dm_nerf_amd import _lib
     from dm_nerf_amd.networks import evaluator as E
-    assert torch.cuda.is_available(), "the timing needs the GPU: there is no CPU path to time"
     lib = _lib.load()
     for P in a.frames:
         pred_h, gt_h = frames(P)
         pred, gt = torch.from_numpy(pred_h).cuda(), torch.from_numpy(gt_h).cuda()
-        for _ in range(a.warmup):
-            s, p = E.img_metrics_device(pred, gt)
-        torch.cuda.synchronize()
-        us = []
-        for _ in range(a.iters):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            s, p = E.img_metrics_device(pred, gt)
-            e1.record()
-            e1.synchronize()
-            us.append(1e3 * e0.elapsed_time(e1))
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            s, p = E.img_metrics_device(pred, gt)
-        e1.record()
-        e1.synchronize()
-        burst = 1e3 * e0.elapsed_time(e1) / a.iters
+        call = T.time_events(lambda: E.img_metrics_device(pred, gt), a.iters, a.warmup)
+
+        def in_a_burst():
+            for _ in range(a.iters):
+                E.img_metrics_device(pred, gt)
+
+        burst = 1e3 * T.time_events(in_a_burst, 1, 0).median / a.iters
+        s, p = E.img_metrics_device(pred, gt)
         want = [RS.ssim_uniform(pred_h[i], gt_h[i]) for i in range(P)]
-        print(json.dumps({"leg": "device", "frames": P, "shape": [H, W, C], "iters": a.iters, "us_median": float(np.median(us)),
-                          "us_min": float(np.min(us)), "us_max": float(np.max(us)), "us_per_call_in_a_burst": burst,
+        print(json.dumps({"leg": "device", "frames": P, "shape": [H, W, C], "iters": a.iters, "us_median": 1e3 * call.median,
+                          "us_min": 1e3 * call.min, "us_max": 1e3 * call.max, "us_per_call_in_a_burst": burst,
                           "us_per_frame_in_a_burst": burst / P, "work_bytes": int(lib.dmnerf_img_metrics_work_bytes(P, H, W, C)),
                           "ssim": [float(v) for v in s.cpu()], "psnr": [float(v) for v in p.cpu()],
                           "max_abs_delta_ssim_vs_host": float(np.max(np.abs(np.array(want) - s.cpu().numpy())))}), flush=True)
         if a.skip_host:
             continue
-        ts = []
-        for _ in range(a.host_iters):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
+
+        def host():
             for i in range(P):
                 rgb = pred[i].cpu().numpy()                # tester.py:89-90: the copy and its synchronisation, per pose
                 RS.psnr_restate(rgb, gt_h[i])
                 RS.ssim_uniform(rgb, gt_h[i])
-            ts.append((time.perf_counter() - t0) / P)
+
+        t = T.time_host(host, a.host_iters, 0)
         print(json.dumps({"leg": "host", "frames": P, "shape": [H, W, C], "iters": a.host_iters, "threads": torch.get_num_threads(),
-                          "ms_per_frame_median": 1e3 * float(np.median(ts)), "ms_per_frame_min": 1e3 * float(np.min(ts)),
-                          "ms_per_frame_max": 1e3 * float(np.max(ts))}), flush=True)
+                          "ms_per_frame_median": t.median / P, "ms_per_frame_min": t.min / P, "ms_per_frame_max": t.max / P}), flush=True)
 
 
 if __name__ == "__main__":

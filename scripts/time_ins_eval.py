@@ -19,9 +19,10 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-H, W = 480, 640
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
+
+H, W = T.H, T.W
 
 
 def frame(ins_num, seed=0):
@@ -47,20 +48,10 @@ def device(ins_nums, iters, warmup):
     for C in ins_nums:
         pl, conf, gt = (torch.from_numpy(x).cuda() for x in frame(C))
         rows = torch.unique(gt)
-        for _ in range(warmup):
-            E.ins_eval_device(pl, conf, gt, rows, C)
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(iters):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            E.ins_eval_device(pl, conf, gt, rows, C)
-            b.record()
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
+        t = T.time_events(lambda: E.ins_eval_device(pl, conf, gt, rows, C), iters, warmup)
         _, ap, _ = E.ins_eval_device(pl, conf, gt, rows, C)
         print(json.dumps({"leg": "device", "ins_num": C, "frame": [H, W], "gt_num": int(rows.numel()), "iters": iters,
-                          "ms_median": float(np.median(ms)), "ms_min": float(np.min(ms)),
+                          "ms_median": t.median, "ms_min": t.min,
                           "work_bytes": int(lib.dmnerf_ins_eval_work_bytes(H * W, C)), "ap": [round(float(v), 4) for v in ap.cpu()]}),
               flush=True)
 
@@ -104,6 +95,7 @@ def main():
             line["peak_rss_gb"] = resource.getrusage(resource.RUSAGE_CHILDREN).ru_maxrss / 2 ** 20   # (max over children so far)
             print(json.dumps(line), flush=True)
         return
+    T.require_gpu(__file__)                                          # (the two host legs above use no device)
     device(a.ins_num, a.iters, a.warmup)
 
 

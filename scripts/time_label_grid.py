@@ -14,20 +14,16 @@ and 100 %.  Per row, HIP-event milliseconds, median and minimum of ``--iters`` r
 
 and the evaluated fraction (samples evaluated / samples, counted on the device by ``run_network_skip(counts=)``) and the labelled
 fraction.  There is no earlier implementation to compare against: these are absolute times of this tree.  The first line records
-the device and its clocks (sclk among them) as ``rocm-smi --showclocks`` reports them (read-only).  One JSON object per line."""
+the device and its clocks (sclk among them) as ``rocm-smi`` reports them (read-only).  One JSON object per line."""
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from time_mark import time_call  # noqa: E402
-from time_skip import clocks  # noqa: E402
+import _timing as T  # noqa: E402
 
 
 def main():
@@ -38,25 +34,23 @@ def main():
     ap.add_argument("--mfma-split", default=None, choices=["f16x2"], help="the network kernels (default: f32)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    T.require_gpu(__file__)
     import bench_common as C
     from dm_nerf_amd import _lib, field as F
     from dm_nerf_amd.networks import render as R
     dev = torch.device("cuda")
     _, _, _, mf = C.build_models(dev, ins_num=13)
     n_logits = mf.ins_num + 1
-    lo, hi, dims = (-8.0, -8.0, -8.0), (8.0, 8.0, 8.0), (a.dims,) * 3
+    (lo, hi), dims = T.BOX, (a.dims,) * 3
     slab = 1 << 20
     step = max(1, slab // (dims[1] * dims[2]))
-    lines = [{"leg": "device", "name": torch.cuda.get_device_name(0), "clocks": clocks(), "iters": a.iters, "warmup": a.warmup,
-              "dims": a.dims, "ins_num": mf.ins_num, "mfma_split": a.mfma_split}]
+    lines = [T.device_line(iters=a.iters, warmup=a.warmup, dims=a.dims, ins_num=mf.ins_num, mfma_split=a.mfma_split)]
     lib = _lib.load()
     rng = np.random.RandomState(0)
     with torch.no_grad():
         for p in (0.05, 0.25, 1.0):
-            cells = np.zeros((a.dims ** 3 + 31) // 32 * 32, dtype=bool)            # (whole words: cell g is bit g & 31 of word g >> 5)
-            cells[:a.dims ** 3] = rng.rand(a.dims ** 3) < p
-            occ = F.SkipGrid.full(lo, hi, dims, device=dev) if p == 1.0 else \
-                F.SkipGrid.from_bits(np.packbits(cells, bitorder="little").view(np.uint32), lo, hi, dims, device=dev)
+            cells = rng.rand(a.dims ** 3) < p                        # (one generator through the three rows, not random_bits' seed per row)
+            occ = F.SkipGrid.full(lo, hi, dims, device=dev) if p == 1.0 else F.SkipGrid.from_bits(T.pack_bits(cells), lo, hi, dims, device=dev)
             counts = torch.zeros(2, dtype=torch.int64, device=dev)
 
             def network(counts=None):
@@ -81,14 +75,10 @@ def main():
                    "labelled_fraction": float((lg.labels != F.UNLABELLED).float().mean()), "top_label": top}
             for name, fn in (("label_grid", lambda: F.label_grid(mf, occ, slab=slab, split=a.mfma_split)), ("network", network),
                              ("label_pass", label_pass), ("stats", lg.stats), ("skip_grid", lambda: lg.skip_grid(top))):
-                row[name + "_ms_median"], row[name + "_ms_min"] = time_call(fn, a.iters, a.warmup)
+                t = T.time_events(fn, a.iters, a.warmup)
+                row[name + "_ms_median"], row[name + "_ms_min"] = t.median, t.min
             lines.append(row)
-    text = "\n".join(json.dumps(l) for l in lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    T.write_jsonl(lines, a.out)
 
 
 if __name__ == "__main__":

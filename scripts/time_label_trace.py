@@ -15,33 +15,15 @@ R = 1 (the plain frame) and R = 2 (one rigid move of label 2), median and minimu
 and the fraction of pixels with a hit.  The last line is ONE dense ``manipulate_frame`` of the same view and transformation with the
 benchmark's models (``--no-frame`` leaves it out): the frame the preview stands in for; its code is untouched by the trace.  There
 is no earlier implementation of the trace: these are absolute times of this tree.  The first line records the device and its clocks
-(sclk among them) as ``rocm-smi --showclocks`` reports them (read-only).  One JSON object per line."""
+(sclk among them) as ``rocm-smi`` reports them (read-only).  One JSON object per line."""
 import argparse
-import json
 import os
 import sys
-import time
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from time_mark import time_call  # noqa: E402
-from time_manip_skip import clocks, time_frame  # noqa: E402
-
-
-def time_host(fn, iters, warmup):
-    ms = []
-    for it in range(warmup + iters):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            ms.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ms)), float(np.min(ms))
+import _timing as T  # noqa: E402
 
 
 def main():
@@ -53,30 +35,22 @@ def main():
     ap.add_argument("--no-frame", action="store_true", help="do not render the manipulation frame")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    T.require_gpu(__file__)
     import types
     from dm_nerf_amd import distributed as D, editing as Ed, field as F
-    from oracle import ref_cpu as O
     dev = torch.device("cuda")
-    H, W, C, target = 480, 640, 14, 2
+    H, W, K, pose = T.study_view()
+    C, target = 14, 2
     near, far = 4.0, 15.0
-    K = O.dmsr_intrinsics(H, W)
-    pose = O.pose_spherical(30.0, -65.0, 7.0)
-    ang = 0.2
-    trans = torch.tensor([[np.cos(ang), -np.sin(ang), 0., 0.3], [np.sin(ang), np.cos(ang), 0., -0.2], [0., 0., 1., 0.1], [0., 0., 0., 1.]],
-                         dtype=torch.float32)
-    lo, hi = (-8.0, -8.0, -8.0), (8.0, 8.0, 8.0)
-    lines = [{"leg": "device", "name": torch.cuda.get_device_name(0), "clocks": clocks(), "iters": a.iters, "warmup": a.warmup,
-              "batch": a.batch, "dims": a.dims, "frame": [H, W], "near": near, "far": far, "ins_num": C - 1}]
+    trans = torch.tensor(T.rigid(), dtype=torch.float32)
+    lines = [T.device_line(iters=a.iters, warmup=a.warmup, batch=a.batch, dims=a.dims, frame=[H, W], near=near, far=far, ins_num=C - 1)]
     fr = D.ManipulationFrameRenderer(H, W, K, pose, [trans], None, types.SimpleNamespace(N_importance=0, target_labels=[target]),
                                      ins_num=C - 1, rank=0, world=1)
     rays = {1: fr.ori[None].contiguous(), 2: torch.cat([fr.ori[None], fr.tar], 0)}
     sets = {1: [range(C)], 2: [[l for l in range(C) if l != target], [target]]}
     edits = {1: ((), ()), 2: ([trans], [target])}
     for pct in (0, 5, 25, 100):
-        rng = np.random.RandomState(pct)
-        vol = rng.randint(0, C, size=(a.dims,) * 3).astype(np.uint8)
-        vol[rng.rand(a.dims, a.dims, a.dims) >= pct / 100.0] = F.UNLABELLED
-        lg = F.LabelGrid.from_labels(torch.from_numpy(vol).to(dev), lo, hi, C)
+        lg = F.LabelGrid.from_labels(torch.from_numpy(T.random_labels(pct, a.dims, C)).to(dev), *T.BOX, C)
         for R in (1, 2):
             out = lg.trace_sets(rays[R], sets[R], near, far)
             row = {"leg": "trace", "labelled_fraction": float((lg.labels != F.UNLABELLED).float().mean()), "R": R,
@@ -86,10 +60,10 @@ def main():
                 for _ in range(a.batch):
                     lg.trace_sets(rays[R], sets[R], near, far)
 
-            med, mn = time_call(batch, a.iters, a.warmup)
-            row["trace_ms_median"], row["trace_ms_min"] = med / a.batch, mn / a.batch
-            row["preview_ms_median"], row["preview_ms_min"] = time_host(
-                lambda: Ed.preview_frame(lg, H, W, K, pose, *edits[R], near=near, far=far), a.iters, a.warmup)
+            t = T.time_events(batch, a.iters, a.warmup)
+            row["trace_ms_median"], row["trace_ms_min"] = t.median / a.batch, t.min / a.batch
+            t = T.time_host(lambda: Ed.preview_frame(lg, H, W, K, pose, *edits[R], near=near, far=far), a.iters, a.warmup)
+            row["preview_ms_median"], row["preview_ms_min"] = t.median, t.min
             lines.append(row)
     if not a.no_frame:
         import bench_common as B
@@ -101,14 +75,9 @@ def main():
             return D.ManipulationFrameRenderer(H, W, K, pose.to(dev), [trans], (mc, mf), args, chunk=4096)
 
         with torch.no_grad():
-            med, mn, _ = time_frame(renderer, 1, 1)
-        lines.append({"leg": "manipulate_frame_dense", "runs": 1, "warmup": 1, "ms": med})
-    text = "\n".join(json.dumps(l) for l in lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+            t = T.time_events(T.render_chunks, 1, 1, setup=renderer)
+        lines.append({"leg": "manipulate_frame_dense", "runs": 1, "warmup": 1, "ms": t.median})
+    T.write_jsonl(lines, a.out)
 
 
 if __name__ == "__main__":

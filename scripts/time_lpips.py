@@ -18,29 +18,12 @@ import json
 import os
 import sys
 
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(T.ROOT, "tests"))
 
 PEAK_F32_MFMA_TFLOPS = 157.3
-
-
-def timed(fn, iters, warmup):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.min(ms))
 
 
 def conv_gflop(P, H, W):
@@ -118,6 +101,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-torch", action="store_true")
     a = ap.parse_args()
+    T.require_gpu(__file__)
     if a.iters < 10:
         print("note: fewer than 10 timed runs", file=sys.stderr)
 
@@ -133,7 +117,7 @@ def main():
 
     for name, P in (("pair", 1), ("batch", a.batch)):
         pred, gt = frames[P]
-        med, mn = timed(lambda: model(pred, gt), a.iters, a.warmup)
+        med, mn = T.time_events(lambda: model(pred, gt), a.iters, a.warmup)[:2]
         gf = sum(conv_gflop(P, H, W))
         print(json.dumps({"stage": name, "P": P, **base, "ms_median": med, "ms_min": mn, "ms_per_pair": med / P, "conv_gflop": gf,
                           "achieved_tflops": gf / med, "fraction_of_f32_mfma_peak": gf / med / PEAK_F32_MFMA_TFLOPS,
@@ -143,7 +127,7 @@ def main():
     steps, _ = steps_of(model, pred, gt)
     gfs = iter(conv_gflop(1, H, W))
     for step, fn in steps:                              # (in order: each step reads what the one before it left)
-        med, mn = timed(fn, a.iters, a.warmup)
+        med, mn = T.time_events(fn, a.iters, a.warmup)[:2]
         rec = {"stage": "step", "step": step, "P": 1, **base, "ms_median": med, "ms_min": mn}
         if step.startswith("conv"):
             gf = next(gfs)
@@ -154,7 +138,7 @@ def main():
         for name, P in (("torch_pair", 1), ("torch_batch", a.batch)):
             pred, gt = frames[P]
             with torch.no_grad():
-                med, mn = timed(lambda: torch_lpips(pred, gt, sd), a.iters, a.warmup)
+                med, mn = T.time_events(lambda: torch_lpips(pred, gt, sd), a.iters, a.warmup)[:2]
                 s = torch_lpips(pred, gt, sd)
             print(json.dumps({"stage": name, "P": P, **base, "ms_median": med, "ms_min": mn, "ms_per_pair": med / P,
                               "score": [float(v) for v in s[:2]]}), flush=True)

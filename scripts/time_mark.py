@@ -10,35 +10,18 @@ already holds the frame's bits (the steady state: the mark kernel only loads), a
 run-to-run spread the overhead has to be read against.  Per leg: HIP-event milliseconds of the whole frame, median and minimum of
 ``--iters`` runs after ``--warmup``.  The last line times the two stand-alone passes on one chunk's worth of samples:
 ``SkipGrid.mark`` on 4096 x 192 samples and ``dilated(1)`` of the 128^3 grid.  The first line records the device and its clocks as
-``rocm-smi --showclocks`` reports them (read-only).  One JSON object per line.
+``rocm-smi`` reports them (read-only).  One JSON object per line.
 
 The quality of a ``from_views`` grid on a trained field (occupancy, evaluated fraction, PSNR against the dense render of held-out
 poses) is NOT measured by this script."""
 import argparse
-import json
 import os
 import sys
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from time_skip import clocks, time_frame  # noqa: E402
-
-
-def time_call(fn, iters, warmup):
-    ms = []
-    for it in range(warmup + iters):
-        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        b.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            ms.append(b.elapsed_time(e))
-    return float(np.median(ms)), float(np.min(ms))
+import _timing as T  # noqa: E402
 
 
 def main():
@@ -49,20 +32,18 @@ def main():
     ap.add_argument("--mfma-split", default=None, choices=["f16x2"], help="render with args.mfma_split (default: the f32 kernels)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    T.require_gpu(__file__)
     import types
     import bench_common as C
     from dm_nerf_amd import distributed as D, field as F
-    from oracle import ref_cpu as O
     dev = torch.device("cuda")
     _, _, mc, mf = C.build_models(dev)
-    H, W = 480, 640
-    K = O.dmsr_intrinsics(H, W)
-    c2w = O.pose_spherical(30.0, -65.0, 7.0).to(dev)
+    H, W, K, c2w = T.study_view()
+    c2w = c2w.to(dev)
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
     if a.mfma_split:
         args.mfma_split = a.mfma_split
-    lo, hi = (-8.0, -8.0, -8.0), (8.0, 8.0, 8.0)
-    lines = [{"leg": "device", "name": torch.cuda.get_device_name(0), "clocks": clocks(), "iters": a.iters, "warmup": a.warmup}]
+    lines = [T.device_line(iters=a.iters, warmup=a.warmup)]
     if a.mfma_split:
         lines[0]["mfma_split"] = a.mfma_split
 
@@ -70,10 +51,14 @@ def main():
         return D.FrameRenderer(H, W, K, c2w, (mc, mf), 4.0, 15.0, args, chunk=4096, n_samples=64, **kw)
 
     def leg(name, make, **extra):
-        med, mn = time_frame(make, a.iters, a.warmup)
-        lines.append(dict({"leg": name, "ms_median": med, "ms_min": mn, "rays_per_s": H * W / med * 1e3}, **extra))
+        t = T.time_events(T.render_chunks, a.iters, a.warmup, setup=make)
+        lines.append(dict({"leg": name, "ms_median": t.median, "ms_min": t.min, "rays_per_s": H * W / t.median * 1e3}, **extra))
 
-    grid = F.SkipGrid.empty(lo, hi, a.dims, device=dev)
+    def call(fn):
+        t = T.time_events(fn, a.iters, a.warmup)
+        return t.median, t.min
+
+    grid = F.SkipGrid.empty(*T.BOX, a.dims, device=dev)
 
     def fresh():
         grid.bits.zero_()
@@ -87,18 +72,13 @@ def main():
         fr = renderer()
         z, w = torch.rand(4096, 192, device=dev) * 11.0 + 4.0, torch.rand(4096, 192, device=dev)
         ro, rd = fr.rays_o[:4096].contiguous(), fr.rays_d[:4096].contiguous()
-        scratch = F.SkipGrid.empty(lo, hi, a.dims, device=dev)
-        first = time_call(lambda: (scratch.bits.zero_(), scratch.mark(ro, rd, z, w)), a.iters, a.warmup)       # (with the 256 KB clear)
-        steady = time_call(lambda: scratch.mark(ro, rd, z, w), a.iters, a.warmup)
-        dil = time_call(lambda: grid.dilated(1), a.iters, a.warmup)
+        scratch = F.SkipGrid.empty(*T.BOX, a.dims, device=dev)
+        first = call(lambda: (scratch.bits.zero_(), scratch.mark(ro, rd, z, w)))       # (with the 256 KB clear)
+        steady = call(lambda: scratch.mark(ro, rd, z, w))
+        dil = call(lambda: grid.dilated(1))
         lines.append({"leg": "passes", "samples": 4096 * 192, "mark_from_empty_ms": first, "mark_saturated_ms": steady,
                       "dilate1_ms": dil, "dims": a.dims})
-    text = "\n".join(json.dumps(l) for l in lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    T.write_jsonl(lines, a.out)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,7 @@ round ``field.extract_surface`` on ``torch.where(labels == k, value, 0)``, which
 
 Synthetic volumes: Voronoi labels of ``ins_num + 1`` random seeds (every label present), a smooth field of Gaussian blobs through
 the occupancy activation, about 2.5 % of the cells unlabelled.  Host clock round a device synchronise (both routes read totals on
-the host, so that is what a caller waits for), median of ``--iters`` after ``--warmup`` runs.  The first line records the device and
+the host, so that is what a caller waits for), median (``*_ms``) and minimum (``*_ms_min``) of ``--iters`` after ``--warmup`` runs.  The first line records the device and
 its clocks (sclk among them, read-only).
 
     loop_open_ms     the per-label loop on the volume as it is: open meshes where an object touches the box (C extracts, C host reads)
@@ -19,14 +19,9 @@ import argparse
 import json
 import os
 import sys
-import time
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-from time_manip_skip import clocks  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
 
 
 def synthetic(dim, C, seed):
@@ -50,20 +45,6 @@ def synthetic(dim, C, seed):
     return labels.contiguous(), value
 
 
-def timed(fn, iters, warmup):
-    import torch
-    for _ in range(warmup):
-        fn()
-    ms = []
-    for _ in range(iters):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ms))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dims", type=int, nargs="+", default=[128, 256])
@@ -72,18 +53,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--level", type=float, default=0.45)
     a = ap.parse_args()
+    T.require_gpu(__file__)
 
     import ctypes
 
     import torch
     from dm_nerf_amd import _lib, field as F
 
-    print(json.dumps({"leg": "device", "name": torch.cuda.get_device_name(0), "clocks": clocks(), "iters": a.iters, "warmup": a.warmup}), flush=True)
+    print(json.dumps(T.device_line(iters=a.iters, warmup=a.warmup)), flush=True)
     for dim in a.dims:
         for ins_num in a.ins_nums:
             C = ins_num + 1
             labels, value = synthetic(dim, C, 100 * dim + ins_num)
-            grid = F.LabelGrid.from_labels(labels, (-8.0,) * 3, (8.0,) * 3, C)
+            grid = F.LabelGrid.from_labels(labels, *T.BOX, C)
             zero = torch.zeros_like(value)
 
             def loop(lab, val):
@@ -103,10 +85,15 @@ def main():
             assert all(torch.equal(ref[k][0] - 1.0, surf.vertices[vo[k]:vo[k + 1]]) for k in range(C)), "the single pass differs from the loop"
             line = {"leg": "object_surfaces", "dim": dim, "ins_num": ins_num, "C": C, "vertices": int(surf.vertices.shape[0]),
                     "triangles": int(surf.faces.shape[0]), "objects": int((surf.face_offset[1:] > surf.face_offset[:-1]).sum())}
-            line["loop_open_ms"] = timed(lambda: loop(labels, value), a.iters, a.warmup)
-            line["loop_closed_ms"] = timed(loop_closed, a.iters, a.warmup)
-            line["one_pass_ms"] = timed(lambda: F.object_surfaces(grid, value, a.level), a.iters, a.warmup)
-            line["one_pass_open_ms"] = timed(lambda: F.object_surfaces(grid, value, a.level, closed=False), a.iters, a.warmup)
+
+            def timed(name, fn):
+                t = T.time_host(fn, a.iters, a.warmup)
+                line[name + "_ms"], line[name + "_ms_min"] = t.median, t.min
+
+            timed("loop_open", lambda: loop(labels, value))
+            timed("loop_closed", loop_closed)
+            timed("one_pass", lambda: F.object_surfaces(grid, value, a.level))
+            timed("one_pass_open", lambda: F.object_surfaces(grid, value, a.level, closed=False))
             line["ratio_closed"] = line["loop_closed_ms"] / line["one_pass_ms"]
             line["ratio_open"] = line["loop_open_ms"] / line["one_pass_open_ms"]
 
@@ -136,10 +123,10 @@ def main():
                 tk, torder = torch.sort(tkey)
                 return vpos[vorder], vcell[vorder], torch.searchsorted(vk, ckey[torder]).to(torch.int32)
             emit()
-            line["count_ms"] = timed(count, a.iters, a.warmup)
-            line["emit_ms"] = timed(emit, a.iters, a.warmup)
-            line["sort_ms"] = timed(sort, a.iters, a.warmup)
-            line["measures_ms"] = timed(surf.measures, a.iters, a.warmup)
+            timed("count", count)
+            timed("emit", emit)
+            timed("sort", sort)
+            timed("measures", surf.measures)
             print(json.dumps(line), flush=True)
             del surf, ref, zero
 

@@ -23,27 +23,11 @@ import types
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
 
 EXTENTS, OCC_RANGE, NEAR, FAR, N_IMP = (1.9, 7.0, 7.0), (-1.0, 1.0), 4.0, 15.0, 128
 MFMA_DENSITY, MFMA_FULL_C14 = 7680, 10880          # per 32 samples (csrc/mlp_fwd_points.hip, mlp_fwd_impl.h)
-
-
-def timed(fn, iters, warmup):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.min(ms))
 
 
 def main():
@@ -57,6 +41,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--legs", nargs="*", default=["grid", "points", "baseline", "reference_loop"])
     a = ap.parse_args()
+    T.require_gpu(__file__)
 
     import torch
     from dm_nerf_amd import field as F
@@ -69,9 +54,9 @@ def main():
     pe, ve = M.get_embedder(10, 0)[0], M.get_embedder(4, 0)[0]
     args = types.SimpleNamespace(near=NEAR, far=FAR, N_importance=N_IMP)
     voxel = (FAR - NEAR) / N_IMP
-    T = np.eye(4)
-    T[:3, :3] = np.linalg.qr(np.random.default_rng(0).standard_normal((3, 3)))[0]
-    T[:3, 3] = (0.3, -0.2, 0.5)
+    trans = np.eye(4)
+    trans[:3, :3] = np.linalg.qr(np.random.default_rng(0).standard_normal((3, 3)))[0]
+    trans[:3, 3] = (0.3, -0.2, 0.5)
     n = a.dim ** 3
     base = {"dim": a.dim, "points": n, "ins_num": a.ins_num, "iters": a.iters, "device": torch.cuda.get_device_name(0)}
     results = {}
@@ -82,11 +67,11 @@ def main():
 
     with torch.no_grad():
         if "grid" in a.legs:
-            med, mn = timed(lambda: F.occupancy_grid(model, T, args, EXTENTS, OCC_RANGE, a.dim, slab=a.slab), a.iters, a.warmup)
+            med, mn = T.time_events(lambda: F.occupancy_grid(model, trans, args, EXTENTS, OCC_RANGE, a.dim, slab=a.slab), a.iters, a.warmup)[:2]
             report("grid", med, mn, slab=a.slab, gsamples_per_s=n / med / 1e6)
-        pts = F.grid_points(OCC_RANGE, EXTENTS, T, a.dim) if {"points", "baseline"} & set(a.legs) else None
+        pts = F.grid_points(OCC_RANGE, EXTENTS, trans, a.dim) if {"points", "baseline"} & set(a.legs) else None
         if "points" in a.legs:
-            med, mn = timed(lambda: F.query_density(model, pts, voxel), a.iters, a.warmup)
+            med, mn = T.time_events(lambda: F.query_density(model, pts, voxel), a.iters, a.warmup)[:2]
             report("points", med, mn)
         if "baseline" in a.legs:
             out = torch.empty(n, dtype=torch.float32, device="cuda")
@@ -97,15 +82,15 @@ def main():
                     emb = torch.cat([pe.embed(p), ve.embed(torch.zeros_like(p))], -1)
                     out[s:s + a.n_test] = model(emb)[..., 3]
                 return 1.0 - torch.exp(-torch.relu(out) * voxel)
-            med, mn = timed(baseline, a.iters, a.warmup)
+            med, mn = T.time_events(baseline, a.iters, a.warmup)[:2]
             report("baseline", med, mn, n_test=a.n_test)
             if "grid" in results:
-                got = F.occupancy_grid(model, T, args, EXTENTS, OCC_RANGE, a.dim, slab=a.slab).reshape(-1)
+                got = F.occupancy_grid(model, trans, args, EXTENTS, OCC_RANGE, a.dim, slab=a.slab).reshape(-1)
                 print(json.dumps({"leg": "compare", "max_abs_diff_grid_vs_baseline": float((got - baseline()).abs().max()),
                                   "time_ratio_grid_over_baseline": results["grid"] / med,
                                   "mfma_count_ratio": MFMA_DENSITY / MFMA_FULL_C14}), flush=True)
         if "reference_loop" in a.legs:
-            lp = F.grid_points(OCC_RANGE, EXTENTS, T, a.loop_dim)
+            lp = F.grid_points(OCC_RANGE, EXTENTS, trans, a.loop_dim)
             nl = lp.shape[0]
 
             def loop():
@@ -115,8 +100,8 @@ def main():
                     raw_fine = model(torch.cat([pe.embed(p), ve.embed(torch.zeros_like(p))], -1))
                     raw = raw_fine if raw is None else torch.cat((raw, raw_fine), dim=0)
                 return (1.0 - torch.exp(-torch.relu(raw[..., 3]) * voxel)).cpu()
-            med, mn = timed(loop, a.iters, a.warmup)
-            g_med, g_mn = timed(lambda: F.occupancy_grid(model, T, args, EXTENTS, OCC_RANGE, a.loop_dim, slab=a.slab), a.iters, a.warmup)
+            med, mn = T.time_events(loop, a.iters, a.warmup)[:2]
+            g_med, g_mn = T.time_events(lambda: F.occupancy_grid(model, trans, args, EXTENTS, OCC_RANGE, a.loop_dim, slab=a.slab), a.iters, a.warmup)[:2]
             print(json.dumps({"leg": "reference_loop", **base, "dim": a.loop_dim, "points": nl, "n_test": a.n_test, "ms_median": med, "ms_min": mn,
                               "grid_ms_median_same_dim": g_med}), flush=True)
 

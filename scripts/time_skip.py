@@ -8,41 +8,15 @@ a 128^3 box round the scene whose cells are set at random with probability 5, 10
 occupancy is the fraction of in-box samples that is evaluated.  The 100 % row is the overhead of select, zero-fill and the
 over-sized launch; the ``dense`` row is ``FrameRenderer`` without ``skip=`` in the same process.  Per row: HIP-event milliseconds
 of the whole frame, median and minimum of ``--iters`` runs after ``--warmup``, rays/s, and the samples evaluated per level.  The
-first line records the device and its clocks as ``rocm-smi --showclocks`` reports them (read-only).  One JSON object per line."""
+first line records the device and its clocks as ``rocm-smi`` reports them (read-only).  One JSON object per line."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def clocks():
-    try:
-        r = subprocess.run(["rocm-smi", "--showclocks", "--json"], capture_output=True, text=True, timeout=30)
-        return json.loads(r.stdout) if r.returncode == 0 else {"error": r.stderr[-200:]}
-    except Exception as e:                                           # the tool is optional
-        return {"error": repr(e)}
-
-
-def time_frame(make, iters, warmup):
-    """``make()`` -> a FrameRenderer; -> (median ms, min ms) of rendering all its chunks."""
-    ms = []
-    for it in range(warmup + iters):
-        fr = make()
-        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        b.record()
-        for i in range(fr.n_chunks):
-            fr.step(i)
-        e.record()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            ms.append(b.elapsed_time(e))
-    return float(np.median(ms)), float(np.min(ms))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
 
 
 def main():
@@ -53,22 +27,19 @@ def main():
     ap.add_argument("--mfma-split", default=None, choices=["f16x2"], help="render with args.mfma_split (default: the f32 kernels)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    T.require_gpu(__file__)
     import types
     import bench_common as C
     from dm_nerf_amd import distributed as D, field as F
     from dm_nerf_amd.networks import render as R
-    from oracle import ref_cpu as O
     dev = torch.device("cuda")
     _, _, mc, mf = C.build_models(dev)
-    H, W = 480, 640
-    K = O.dmsr_intrinsics(H, W)
-    c2w = O.pose_spherical(30.0, -65.0, 7.0).to(dev)
+    H, W, K, c2w = T.study_view()
+    c2w = c2w.to(dev)
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
     if a.mfma_split:
         args.mfma_split = a.mfma_split
-    lo, hi = (-8.0, -8.0, -8.0), (8.0, 8.0, 8.0)
-    lines = [{"leg": "device", "name": torch.cuda.get_device_name(0), "clocks": clocks(), "iters": a.iters, "warmup": a.warmup}]
-
+    lines = [T.device_line(iters=a.iters, warmup=a.warmup)]
     if a.mfma_split:
         lines[0]["mfma_split"] = a.mfma_split
 
@@ -76,28 +47,20 @@ def main():
         return D.FrameRenderer(H, W, K, c2w, (mc, mf), 4.0, 15.0, args, chunk=4096, n_samples=64, **kw)
 
     with torch.no_grad():
-        med, mn = time_frame(renderer, a.iters, a.warmup)
-        lines.append({"leg": "dense", "ms_median": med, "ms_min": mn, "rays_per_s": H * W / med * 1e3})
+        t = T.time_events(T.render_chunks, a.iters, a.warmup, setup=renderer)
+        lines.append({"leg": "dense", "ms_median": t.median, "ms_min": t.min, "rays_per_s": H * W / t.median * 1e3})
         for pct in (5, 10, 25, 50, 100):
-            occ = np.random.RandomState(pct).rand(a.dims, a.dims, a.dims) < pct / 100.0
-            words = np.packbits(occ.reshape(-1), bitorder="little")
-            words = np.concatenate([words, np.zeros(-words.size % 4, np.uint8)]).view(np.uint32)
-            grid = F.SkipGrid.from_bits(words, lo, hi, a.dims, outside="empty")
-            med, mn = time_frame(lambda: renderer(skip=grid), a.iters, a.warmup)
+            grid = F.SkipGrid.from_bits(T.random_bits(pct, a.dims), *T.BOX, a.dims, outside="empty")
+            t = T.time_events(T.render_chunks, a.iters, a.warmup, setup=lambda: renderer(skip=grid))
             fr = renderer()
             n_eval = torch.zeros(2, dtype=torch.int64, device=dev)
             for i in range(fr.n_chunks):
                 s, e = i * 4096, min((i + 1) * 4096, H * W)
                 out = R.dm_nerf_fine_skip(torch.stack([fr.rays_o[s:e], fr.rays_d[s:e]]), None, None, mc, mf, fr.z_full[:e - s], args, grid)
                 n_eval += out["n_eval"]
-            lines.append({"leg": "skip", "grid_occupancy": float(grid.occupancy()), "ms_median": med, "ms_min": mn,
-                          "rays_per_s": H * W / med * 1e3, "n_eval": n_eval.tolist(), "n_dense": [H * W * 64, H * W * 192]})
-    text = "\n".join(json.dumps(l) for l in lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+            lines.append({"leg": "skip", "grid_occupancy": float(grid.occupancy()), "ms_median": t.median, "ms_min": t.min,
+                          "rays_per_s": H * W / t.median * 1e3, "n_eval": n_eval.tolist(), "n_dense": [H * W * 64, H * W * 192]})
+    T.write_jsonl(lines, a.out)
 
 
 if __name__ == "__main__":

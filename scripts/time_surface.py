@@ -22,27 +22,11 @@ import types
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
 
 EXTENTS, OCC_RANGE, NEAR, FAR, N_IMP = (1.9, 7.0, 7.0), (-1.0, 1.0), 4.0, 15.0, 128
 HBM_COPY_TBS = 6.3
-
-
-def timed(fn, iters, warmup):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.min(ms))
 
 
 def main():
@@ -54,6 +38,7 @@ def main():
     ap.add_argument("--level", type=float, default=0.45)
     ap.add_argument("--min-triangles", type=int, default=400)
     a = ap.parse_args()
+    T.require_gpu(__file__)
     if a.iters < 10:
         print("note: fewer than 10 timed runs", file=sys.stderr)
 
@@ -63,16 +48,16 @@ def main():
     from oracle import ref_cpu as O
 
     dim = a.dim
-    T = np.eye(4)
-    T[:3, :3] = np.linalg.qr(np.random.default_rng(0).standard_normal((3, 3)))[0]
-    T[:3, 3] = (0.3, -0.2, 0.5)
+    trans = np.eye(4)
+    trans[:3, :3] = np.linalg.qr(np.random.default_rng(0).standard_normal((3, 3)))[0]
+    trans[:3, 3] = (0.3, -0.2, 0.5)
     model = M.DM_NeRF(8, 256, 63, 27, [4], a.ins_num)
     model.load_state_dict(O.make_weights(2, a.ins_num, gain=1.7, sigma_bias=7.5, sigma_gain=10.0))
     model = model.cuda().eval()
     args = types.SimpleNamespace(near=NEAR, far=FAR, N_importance=N_IMP)
     fields = {}
     with torch.no_grad():
-        fields["model"] = F.occupancy_grid(model, T, args, EXTENTS, OCC_RANGE, dim)
+        fields["model"] = F.occupancy_grid(model, trans, args, EXTENTS, OCC_RANGE, dim)
     g = torch.arange(dim, dtype=torch.float32, device="cuda") - (dim - 1) / 2.0
     r = torch.sqrt(g[:, None, None] ** 2 + g[None, :, None] ** 2 + g[None, None, :] ** 2)
     fields["sphere"] = torch.clamp(1.0 - 0.55 * r / (0.4 * dim), 0.0, 1.0).contiguous()     # 0.45 at r = 0.4 dim
@@ -84,7 +69,7 @@ def main():
         base = {"field": name, "dim": dim, "points": n, "iters": a.iters, "device": torch.cuda.get_device_name(0)}
 
         def report(stage, fn, **kw):
-            med, mn = timed(fn, a.iters, a.warmup)
+            med, mn = T.time_events(fn, a.iters, a.warmup)[:2]
             print(json.dumps({"stage": stage, **base, **kw, "ms_median": med, "ms_min": mn}), flush=True)
             return med
 
@@ -93,15 +78,15 @@ def main():
         def count():
             _lib.check(lib.dmnerf_surface_count(_lib.ptr(occ), dim, dim, dim, ctypes.c_float(a.level), _lib.ptr(counts[0]), _lib.ptr(counts[1]),
                                                 _lib.stream()), "dmnerf_surface_count")
-        med = timed(count, a.iters, a.warmup)
-        tbs = 6.0 * n / (med[0] * 1e-3) / 1e12
-        print(json.dumps({"stage": "count", **base, "ms_median": med[0], "ms_min": med[1], "bytes_per_point": 6, "achieved_TB_per_s": tbs,
+        med, mn = T.time_events(count, a.iters, a.warmup)[:2]
+        tbs = 6.0 * n / (med * 1e-3) / 1e12
+        print(json.dumps({"stage": "count", **base, "ms_median": med, "ms_min": mn, "bytes_per_point": 6, "achieved_TB_per_s": tbs,
                           "fraction_of_hbm_copy_rate": tbs / HBM_COPY_TBS}), flush=True)
         v_idx, faces = F.extract_surface(occ, a.level)
         V, Fn = v_idx.shape[0], faces.shape[0]
         report("extract", lambda: F.extract_surface(occ, a.level), vertices=V, triangles=Fn)
-        report("scene", lambda: F.scene_vertices(v_idx, dim, T, EXTENTS))
-        v = F.scene_vertices(v_idx, dim, T, EXTENTS)
+        report("scene", lambda: F.scene_vertices(v_idx, dim, trans, EXTENTS))
+        v = F.scene_vertices(v_idx, dim, trans, EXTENTS)
         report("normals", lambda: F.vertex_normals(v, faces, occ.shape))
         nrm = F.vertex_normals(v, faces, occ.shape)
         report("clusters", lambda: F.surface_clusters(faces))

@@ -13,7 +13,7 @@ random with probability 5, 10, 25, 50 and 100 %, ``outside="empty"``, both level
 of the step, median and minimum of ``--iters`` steps after ``--warmup``, and the evaluated fraction per level from
 ``args.train_skip_counts``.  The ``dense`` row is the same step without ``args.train_skip``; with ``--tree`` the package is imported
 from that checkout (its library must be built), which is how the parent commit's dense step is timed in the same session.  The first
-line records the device and its clocks as ``rocm-smi --showclocks`` reports them (read-only).
+line records the device and its clocks as ``rocm-smi`` reports them (read-only).
 
 Quality: tests/test_gpu_convergence.py's loop on the analytic scene (12 views of 120 x 160 + one held out, 3072 rays per step, Adam
 5e-4 with the reference's decay), twice with the same seeds: dense, and with a ``TrainSkip`` (its defaults; a 128^3 grid over the box
@@ -22,7 +22,6 @@ per level since the last checkpoint, and wall seconds of the training steps (eva
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 import types
@@ -30,48 +29,21 @@ import types
 import numpy as np
 import torch
 
-
-def clocks():
-    try:
-        r = subprocess.run(["rocm-smi", "--showclocks", "--json"], capture_output=True, text=True, timeout=30)
-        return json.loads(r.stdout) if r.returncode == 0 else {"error": r.stderr[-200:]}
-    except Exception as e:                                           # the tool is optional
-        return {"error": repr(e)}
-
-
-def time_steps(one, iters, warmup):
-    ms = []
-    for it in range(warmup + iters):
-        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        b.record()
-        one()
-        e.record()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            ms.append(b.elapsed_time(e))
-    return float(np.median(ms)), float(np.min(ms))
-
-
-def random_grid(F, pct, dims, lo, hi):
-    occ = np.random.RandomState(pct).rand(dims, dims, dims) < pct / 100.0
-    words = np.packbits(occ.reshape(-1), bitorder="little")
-    words = np.concatenate([words, np.zeros(-words.size % 4, np.uint8)]).view(np.uint32)
-    return F.SkipGrid.from_bits(words, lo, hi, dims, outside="empty")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
 
 
 def timing(a, lines):
     import bench_common as C
     from dm_nerf_amd import distributed as D, field as F
     from dm_nerf_amd.networks import helpers as H
-    from oracle import ref_cpu as O
     dev = torch.device("cuda")
     _, _, mc, mf = C.build_models(dev)
     mc.train(); mf.train()
-    K = O.dmsr_intrinsics(480, 640)
-    ro, rd = H.get_rays_k(480, 640, K, O.pose_spherical(30.0, -65.0, 7.0).to(dev))
+    _, _, K, pose = T.study_view()
+    ro, rd = H.get_rays_k(480, 640, K, pose.to(dev))
     pick = torch.from_numpy(np.random.RandomState(0).choice(480 * 640, 4096, replace=False)).to(dev)
     ro, rd = ro.reshape(-1, 3)[pick].contiguous(), rd.reshape(-1, 3)[pick].contiguous()
-    lo, hi = (-8.0, -8.0, -8.0), (8.0, 8.0, 8.0)
     opt = torch.optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=5e-4, betas=(0.9, 0.999))
     start = [p.detach().clone() for p in opt.param_groups[0]["params"]]
     for n in (3072, 4096):
@@ -84,7 +56,7 @@ def timing(a, lines):
             args = types.SimpleNamespace(perturb=1.0, N_importance=128, is_train=True, N_ins=None, penalize=True, tolerance=0.05, deta_w=0.05,
                                          mfma_split=a.mfma_split or False)
             if pct is not None:
-                args.train_skip = random_grid(F, pct, a.dims, lo, hi)
+                args.train_skip = F.SkipGrid.from_bits(T.random_bits(pct, a.dims), *T.BOX, a.dims, outside="empty")
                 args.train_skip_levels = ("coarse", "fine")
                 args.train_skip_counts = {l: torch.zeros(2, dtype=torch.int64, device=dev) for l in ("coarse", "fine")}
             with torch.no_grad():                                    # every row starts from the same weights and optimizer state
@@ -92,7 +64,8 @@ def timing(a, lines):
                     p.copy_(s)
             opt.state.clear()
             torch.manual_seed(0); torch.cuda.manual_seed(0)
-            med, mn = time_steps(lambda: D.sharded_train_step(rays, z, target, labels, (mc, mf), args, opt, C.INS_NUM), a.iters, a.warmup)
+            t = T.time_events(lambda: D.sharded_train_step(rays, z, target, labels, (mc, mf), args, opt, C.INS_NUM), a.iters, a.warmup)
+            med, mn = t.median, t.min
             row = {"leg": "dense" if pct is None else "skip", "rays": n, "ms_median": med, "ms_min": mn}
             if pct is None:
                 dense_ms = med
@@ -198,20 +171,17 @@ def main():
     ap.add_argument("--checkpoints", default="1000,2000,3000")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    tree = os.path.abspath(a.tree) if a.tree else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    T.require_gpu(__file__)
+    tree = os.path.abspath(a.tree) if a.tree else T.ROOT
     sys.path.insert(0, tree)
     import dm_nerf_amd
-    lines = [{"leg": "device", "name": torch.cuda.get_device_name(0), "clocks": clocks(), "iters": a.iters, "warmup": a.warmup,
-              "tree": a.label or os.path.relpath(tree),
-              "package_in_tree": os.path.relpath(os.path.dirname(os.path.abspath(dm_nerf_amd.__file__)), tree)}]
+    lines = [T.device_line(iters=a.iters, warmup=a.warmup, tree=a.label or os.path.relpath(tree),
+                           package_in_tree=os.path.relpath(os.path.dirname(os.path.abspath(dm_nerf_amd.__file__)), tree))]
     if a.mfma_split:
         lines[0]["mfma_split"] = a.mfma_split
     print(json.dumps(lines[0]), flush=True)
     (quality if a.quality else timing)(a, lines)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(json.dumps(l) for l in lines) + "\n")
+    T.write_jsonl(lines, a.out, echo=False)                          # (every line was printed as it was measured)
 
 
 if __name__ == "__main__":
