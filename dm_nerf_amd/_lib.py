@@ -221,6 +221,10 @@ SIGNATURES = {
     "dmnerf_label_cells": (c_int, [c_vp, c_i64, c_int, c_float, c_vp, c_vp]),
     "dmnerf_label_stats": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_skip_grid_from_labels": (c_int, [c_vp, c_i64, ctypes.POINTER(ctypes.c_uint32), c_vp, c_vp]),
+    "dmnerf_label_components": (ctypes.c_int32, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "dmnerf_label_components_largest": (ctypes.c_int32, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "dmnerf_label_components_filter": (ctypes.c_int32, [c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_uint32), c_vp, c_vp, c_int, c_int,
+                                               c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_label_trace": (c_int, [c_vp, ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_int), c_int,
                                    c_vp, c_int, c_i64, ctypes.POINTER(ctypes.c_uint32), c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmnerf_bake_cells": (c_int, [c_vp, c_i64, c_int, c_float, c_vp, c_vp, c_vp]),

@@ -125,7 +125,9 @@ def about(matrix, centre):
 def object_centre(label_grid_or_stats, label):
     """The centre of object ``label`` -> numpy float64 ``[3]``: row ``label`` of ``stats()["centre"]`` of a ``field.LabelGrid`` (or of
     the dict ``stats()`` returned), the mean of the centres of the cells the object owns.  This is the one host read of the label
-    grid: one copy of four numbers.  ``ValueError`` if the object owns no cell or ``label`` is not a row of the stats."""
+    grid: one copy of four numbers.  ``ValueError`` if the object owns no cell or ``label`` is not a row of the stats.  The mean is
+    over ALL cells of the label, so stray cells pull it: ``object_centre(grid.cleaned(keep="largest")[0], label)`` is the robust
+    pivot, the centre of the object's largest connected component (``field.LabelGrid.cleaned``)."""
     stats = label_grid_or_stats if isinstance(label_grid_or_stats, dict) else label_grid_or_stats.stats()
     label = int(label)
     if not 0 <= label < stats["count"].shape[0]:

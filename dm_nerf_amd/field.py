@@ -628,6 +628,14 @@ class SkipGrid:
         """Fraction of set cells (a device scalar)."""
         return self.unpack().float().mean()
 
+    def cleaned(self, min_cells, connectivity=26):
+        """A new grid, same box and ``outside``, without the isolated cells the render would march into: a set cell stays set iff
+        its connected component of set cells has at least ``min_cells`` cells (``LabelGrid.cleaned`` of the bits as a one-label
+        volume, then ``skip_grid(0)``).  ``connectivity`` 26 (default) or 6; bad arguments raise ``ValueError``."""
+        labels = torch.where(self.unpack(), 0, UNLABELLED).to(torch.uint8)
+        grid, _ = LabelGrid.from_labels(labels, self.lo, self.hi, C=1).cleaned(min_cells, connectivity=connectivity)
+        return grid.skip_grid(0, outside=self.outside)
+
 
 class TrainSkip:
     """When the grid of a training run that skips empty space (``autograd.dm_nerf_train(..., skip=)``, ``args.train_skip``) is
@@ -766,6 +774,72 @@ def label_grid(model_fine, occ, sigma_threshold=0.0, slab=1 << 20, split=None):
     return LabelGrid(labels, occ.lo, occ.hi, C)
 
 
+def _stats_of_sums(grid, count, index_sum, lo_idx, hi_idx):
+    """The dict of ``LabelGrid.stats()`` (per label) and ``Components.table()`` (per component) from the integer sums of its rows: the
+    float64 quantities are derived on the device from python scalars of ``grid``'s box (no host-to-device copy: capturable)."""
+    n = count.double()
+    lo, cell = grid.lo.astype(np.float64), grid.cell.astype(np.float64)
+    per_axis = lambda idx, plus: torch.stack([(idx[:, a] + plus) * float(cell[a]) + float(lo[a]) for a in range(3)], dim=-1)
+    return {"count": count, "index_sum": index_sum, "lo_idx": lo_idx, "hi_idx": hi_idx,
+            "centre": per_axis(index_sum.double() / n[:, None], 0.5),
+            "box_lo": per_axis(lo_idx.double(), 0.0), "box_hi": per_axis(hi_idx.double(), 0.0),
+            "volume": n * float(cell[0] * cell[1] * cell[2])}
+
+
+COMPONENTS_KEEP = {"all": 0, "largest": 1}    # DMNERF_COMPONENTS_KEEP_* (include/dmnerf_hip.h)
+COMPONENTS_TILE = (8, 8, 32)                  # CC_TI, CC_TJ, CC_TK (csrc/components.hip): the cells of one workgroup of the tile pass
+
+
+def _connectivity(who, connectivity):
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (6, 26):
+        raise ValueError(f"{who}: connectivity must be 6 or 26, got {connectivity!r}")
+    return int(connectivity)
+
+
+class Components:
+    """The connected components of a ``LabelGrid`` (``LabelGrid.components``): ``root`` / ``size`` int32 ``[dx, dy, dz]`` on the device,
+    ``connectivity``, and the grid's ``labels``, box (``lo``, ``hi``, ``cell``, ``inv_cell``), ``dims`` and ``C``."""
+
+    def __init__(self, grid, root, size, connectivity):
+        self.labels, self.root, self.size, self.connectivity = grid.labels, root, size, connectivity
+        self.lo, self.hi, self.cell, self.inv_cell, self.dims, self.C = grid.lo, grid.hi, grid.cell, grid.inv_cell, grid.dims, grid.C
+
+    def largest(self):
+        """The largest component of every label -> ``{"root" [C] int32, "size" [C] int32}`` on the device; on equal sizes the one with
+        the smallest root; ``-1`` and ``0`` for a label without a cell (``dmnerf_label_components_largest``: ``atomicMax`` of
+        ``size << 32 | 0x7fffffff - root`` over the root cells).  Nothing reaches the host."""
+        best = torch.empty(self.C, dtype=torch.int64, device=self.labels.device)
+        dx, dy, dz = self.dims
+        _lib.launch("dmnerf_label_components_largest", self.labels, dx, dy, dz, self.C, self.root, self.size, best)
+        size = best >> 32
+        return {"root": torch.where(size > 0, 0x7fffffff - (best & 0xffffffff), -1).int(), "size": size.int()}
+
+    def table(self):
+        """One row per component, in ascending order of the roots -> a dict of device tensors.  ``id [dx, dy, dz]`` int32: the row of
+        the cell's component, ``-1`` for an unlabelled cell.  Per component ``label [K]`` uint8, ``root [K]`` int32 and, with exactly
+        ``LabelGrid.stats()``'s definitions and dtypes, ``count [K]``, ``index_sum [K, 3]``, ``lo_idx`` / ``hi_idx [K, 3]``, ``centre``,
+        ``box_lo``, ``box_hi [K, 3]`` and ``volume [K]``.  The number of components ``K`` is read on the host (the one host read: the
+        call cannot be captured in a graph).  The sums are torch's integer scatter operations: the same every run."""
+        dev, n = self.labels.device, self.dims[0] * self.dims[1] * self.dims[2]
+        root = self.root.reshape(-1)
+        is_root = root == torch.arange(n, dtype=torch.int32, device=dev)
+        roots = torch.nonzero(is_root).reshape(-1)                   # ascending; its length is the host read
+        K = roots.shape[0]
+        rank = torch.cumsum(is_root, 0) - 1
+        cell_id = torch.where(root >= 0, rank[root.clamp(min=0).long()], -1)
+        member = torch.nonzero(root >= 0).reshape(-1)
+        row = cell_id[member]
+        dy, dz = self.dims[1], self.dims[2]
+        ijk = torch.stack([member // (dy * dz), (member // dz) % dy, member % dz], dim=-1)
+        index_sum = torch.zeros(K, 3, dtype=torch.int64, device=dev).index_add_(0, row, ijk)
+        rows3 = row[:, None].expand(-1, 3)
+        lo_idx = torch.full((K, 3), 2 ** 31 - 1, dtype=torch.int32, device=dev).scatter_reduce_(0, rows3, ijk.int(), "amin")
+        hi_idx = torch.zeros(K, 3, dtype=torch.int32, device=dev).scatter_reduce_(0, rows3, ijk.int() + 1, "amax")
+        out = {"id": cell_id.int().reshape(self.dims), "label": self.labels.reshape(-1)[roots], "root": roots.int()}
+        out.update(_stats_of_sums(self, self.size.reshape(-1)[roots].long(), index_sum, lo_idx, hi_idx))
+        return out
+
+
 class LabelGrid:
     """``labels``: uint8 ``[dx, dy, dz]`` on the device over the box ``[lo, hi)`` of a ``SkipGrid`` (same ``cell`` arithmetic): the object
     that owns each cell, ``0 .. C - 1``, or 255 for none.  ``C`` is the number of labels the reductions cover."""
@@ -801,14 +875,7 @@ class LabelGrid:
         lo_idx = torch.empty(C, 3, dtype=torch.int32, device=dev)
         hi_idx = torch.empty(C, 3, dtype=torch.int32, device=dev)
         _lib.launch("dmnerf_label_stats", self.labels, dx, dy, dz, C, count, index_sum, lo_idx, hi_idx)
-        n = count.double()
-        lo, cell = self.lo.astype(np.float64), self.cell.astype(np.float64)
-        # (python scalars, not a host tensor: no host-to-device copy, so the call can be captured)
-        per_axis = lambda idx, plus: torch.stack([(idx[:, a] + plus) * float(cell[a]) + float(lo[a]) for a in range(3)], dim=-1)
-        return {"count": count, "index_sum": index_sum, "lo_idx": lo_idx, "hi_idx": hi_idx,
-                "centre": per_axis(index_sum.double() / n[:, None], 0.5),
-                "box_lo": per_axis(lo_idx.double(), 0.0), "box_hi": per_axis(hi_idx.double(), 0.0),
-                "volume": n * float(cell[0] * cell[1] * cell[2])}
+        return _stats_of_sums(self, count, index_sum, lo_idx, hi_idx)
 
     def skip_grid(self, labels, dilate=0, outside="evaluate"):
         """The cells owned by ``labels`` (an int or an iterable of ints in ``[0, C)``, else ``ValueError``) as a ``SkipGrid`` over the
@@ -817,6 +884,69 @@ class LabelGrid:
         g = SkipGrid.empty(self.lo, self.hi, self.dims, outside, self.labels.device)
         _lib.launch("dmnerf_skip_grid_from_labels", self.labels, g.n_cells, mask, g.bits)
         return g.dilated(dilate) if int(dilate) else g
+
+    # ---- what is connected in the volume (csrc/components.hip; tests/_components_restate.py states it in numpy)
+    def components(self, connectivity=6):
+        """The connected components of the volume -> ``Components``.  Two cells are adjacent iff they carry the same label ``< C`` and
+        differ by exactly one in one axis (``connectivity=6``) or by at most one in every axis (``26``), without wrap-around; a
+        component is a class of that adjacency.  ``.root [dx, dy, dz]`` int32: the smallest index ``g = (i dy + j) dz + k`` of the
+        cell's component, ``-1`` for an unlabelled cell; ``.size``: the component's number of cells, ``0``.  Canonical, so the same
+        arrays every run (``dmnerf_label_components``: union-find with integer atomics).  One launch, nothing reaches the host: after
+        a warm-up call it can be captured in a graph and follows ``labels`` on replay.  Another connectivity raises ``ValueError``."""
+        connectivity = _connectivity("LabelGrid.components", connectivity)
+        _lib.require_gpu(self.labels)
+        dx, dy, dz = self.dims
+        root = torch.empty(self.dims, dtype=torch.int32, device=self.labels.device)
+        size = torch.empty(self.dims, dtype=torch.int32, device=self.labels.device)
+        _lib.launch("dmnerf_label_components", self.labels, dx, dy, dz, self.C, connectivity, root, size)
+        return Components(self, root, size, connectivity)
+
+    def cleaned(self, min_cells=1, keep="all", connectivity=6, labels=None, out=None):
+        """The volume without its stray cells -> ``(grid, info)``.  ``grid`` is a volume of this one's class over the same box and ``C``
+        (a ``BakedGrid`` stays a ``BakedGrid``): a cell whose label is in ``labels`` (an int or an iterable as in ``skip_grid``;
+        default: every label ``< C``) keeps it iff its component (``components(connectivity)``) has at least ``min_cells`` cells and,
+        with ``keep="largest"``, is the largest component of its label -- on equal sizes the one with the smallest root.  Otherwise
+        the cell becomes 255 and, in a baked volume, its four floats zero (``BakedGrid``'s invariant for an unlabelled cell).  Every
+        other cell, and every other cell's floats, pass through bit for bit; with the defaults the result equals the input.
+        ``info = {"removed" [C], "kept" [C]}`` int64 on the device: the cells of each label that lost it and that still carry it
+        (``removed + kept == stats()["count"]``).  Connectivity is per label: nothing is merged across labels, no hole is filled, and
+        a thin bridge of cells joins two blobs into one component.
+
+        ``out``: an earlier result's ``grid`` (same class, dims, ``C``, box and device, sharing no memory with this volume) to write
+        into.  Nothing reaches the host: after a warm-up call, ``cleaned(..., out=grid)`` can be captured in a graph and follows
+        ``labels`` / ``cells`` on replay.  ``ValueError``: ``min_cells`` not an integer in ``[1, 2^31)``, another ``keep`` or
+        ``connectivity``, a label outside ``[0, C)``, an ``out`` that does not fit or aliases the volume."""
+        from .editing import _overlaps
+        who = "LabelGrid.cleaned"
+        if isinstance(min_cells, bool) or not isinstance(min_cells, (int, np.integer)) or not 1 <= min_cells < 2 ** 31:
+            raise ValueError(f"{who}: min_cells must be an integer in [1, 2^31), got {min_cells!r}")
+        if keep not in COMPONENTS_KEEP:
+            raise ValueError(f"{who}: keep must be 'all' or 'largest', got {keep!r}")
+        connectivity = _connectivity(who, connectivity)
+        mask = (ctypes.c_uint32 * 4)(*label_mask_words(range(self.C) if labels is None else labels, self.C))
+        baked = isinstance(self, BakedGrid)
+        src_cells = self.cells if baked else None
+        if out is not None:
+            if out is not self and (type(out) is not type(self) or out.dims != self.dims or out.C != self.C
+                                    or not np.array_equal(out.lo, self.lo) or not np.array_equal(out.hi, self.hi)
+                                    or out.labels.device != self.labels.device):
+                raise ValueError(f"{who}: out must be a {type(self).__name__} of dims {self.dims}, C = {self.C} and the box {self.lo} .. "
+                                 f"{self.hi} on {self.labels.device} (an earlier result's grid)")
+            if out is self or _overlaps(out.labels, self.labels) or (baked and _overlaps(out.cells, self.cells)):
+                raise ValueError(f"{who}: out shares memory with the source volume")
+            _lib.require_gpu(out.labels, out.cells if baked else None)
+        comp = self.components(connectivity)
+        _lib.require_gpu(src_cells)
+        dev = self.labels.device
+        if out is None:
+            new = torch.empty_like(self.labels)
+            out = BakedGrid(new, torch.empty_like(self.cells), self.lo, self.hi, self.C) if baked else LabelGrid(new, self.lo, self.hi, self.C)
+        info = {"removed": torch.empty(self.C, dtype=torch.int64, device=dev), "kept": torch.empty(self.C, dtype=torch.int64, device=dev)}
+        best = torch.empty(self.C, dtype=torch.int64, device=dev)
+        dx, dy, dz = self.dims
+        _lib.launch("dmnerf_label_components_filter", self.labels, src_cells, dx, dy, dz, self.C, mask, comp.root, comp.size, int(min_cells),
+                    COMPONENTS_KEEP[keep], best, out.labels, out.cells if baked else None, info["removed"], info["kept"])
+        return out, info
 
     # ---- rays through the volume (csrc/label_trace.hip; tests/_label_trace_restate.py states it in numpy)
     def _ray_sets(self, who, rays, label_sets, max_sets):

@@ -768,6 +768,46 @@ int dmnerf_label_stats(const uint8_t* d_labels, int dx, int dy, int dz, int C, i
                        int32_t* d_hi, void* stream);
 int dmnerf_skip_grid_from_labels(const uint8_t* d_labels, int64_t n_cells, const uint32_t mask[4], uint32_t* d_bits, void* stream);
 
+/* What is connected in a label volume (csrc/components.hip): 3-D connected-component labelling and the filters built on it, so stray
+ * cells can be dropped from the volume itself.  tests/_components_restate.py states all of it in numpy.  Additive (the ABI version
+ * stays).
+ *   Contract (canonical: independent of the algorithm and of the execution order).  d_labels [dx,dy,dz] uint8, cell (i,j,k) at
+ *     g = (i * dy + j) * dz + k.  A cell is labelled iff d_labels[g] < C.  Two labelled cells are adjacent iff they carry the same
+ *     label and differ by exactly one in one axis (connectivity 6) or by at most one in every axis without being the same cell (26);
+ *     nothing wraps round the box.  Components are the equivalence classes of adjacency.
+ *   dmnerf_label_components: d_root [dx,dy,dz] int32 = the smallest index g of the cell's component, -1 for an unlabelled cell;
+ *     d_size [dx,dy,dz] int32 = the number of cells of the cell's component, 0 for an unlabelled cell.  Both are written whole and
+ *     are the call's only workspace.  A tile pass (union-find on LDS parents inside 8 x 8 x 32 cells), a seam pass (cells with a
+ *     neighbour of smaller index in another tile join it in d_root: find with path halving, the larger root hooked under the smaller
+ *     by atomicMin, a failed hook retried from the returned, strictly smaller index), a flatten and a size pass.  parent[x] <= x
+ *     always, so every walk descends and ends; no loop waits for another lane or workgroup, no grid-wide synchronisation.  Integer
+ *     atomics only: the same arrays every run.
+ *   dmnerf_label_components_largest: d_best [C] int64, written whole: for a label with a cell, size << 32 | (0x7fffffff - root) of its
+ *     largest component, the smallest root on equal sizes (atomicMax over the root cells); 0 for a label without a cell.
+ *   dmnerf_label_components_filter: d_root / d_size as dmnerf_label_components wrote them for the same d_labels and C; mask = four HOST
+ *     words (dmnerf_skip_grid_from_labels' packing).  A cell whose label is < C and in the mask keeps its label iff its component has
+ *     size >= min_cells and, with mode DMNERF_COMPONENTS_KEEP_LARGEST, is the largest component of its label (d_best, which the call
+ *     computes first in that mode, as dmnerf_label_components_largest does; mode DMNERF_COMPONENTS_KEEP_ALL neither writes nor
+ *     reads it); otherwise d_out_labels[g] = 255.  Every other cell passes through
+ *     unchanged.  With d_cells [dx,dy,dz,4] f32 (else null, with d_out_cells; both 16-byte aligned) a cell that loses its label gets
+ *     four zeros, every other cell its 16 bytes copied bit for bit.  d_removed / d_kept [C] int64, written whole: per label < C the
+ *     cells that lost it and the cells that carry it in d_out_labels (labels outside the mask count as kept): removed + kept =
+ *     dmnerf_label_stats' count.  Ballots and popcounts per wave into an LDS table, then integer atomics.  The outputs must not
+ *     overlap the inputs.
+ *   Refused with DMNERF_E_ARG before anything touches a device: a dim < 1, dx dy dz >= 2^31, C outside 1..128, a connectivity other
+ *     than 6 or 26, min_cells < 1, a mode other than the two, a null pointer, cells given on one side only or misaligned.  No
+ *     allocation, no synchronisation, no host read: each can be captured in a graph and reads d_labels anew on every replay.  All three
+ *     return the status as int32_t, as dmnerf_volume_edit does. */
+#define DMNERF_COMPONENTS_KEEP_ALL 0
+#define DMNERF_COMPONENTS_KEEP_LARGEST 1
+int32_t dmnerf_label_components(const uint8_t* d_labels, int dx, int dy, int dz, int C, int connectivity, int32_t* d_root, int32_t* d_size,
+                            void* stream);
+int32_t dmnerf_label_components_largest(const uint8_t* d_labels, int dx, int dy, int dz, int C, const int32_t* d_root, const int32_t* d_size,
+                                    int64_t* d_best, void* stream);
+int32_t dmnerf_label_components_filter(const uint8_t* d_labels, const float* d_cells, int dx, int dy, int dz, int C, const uint32_t mask[4],
+                                   const int32_t* d_root, const int32_t* d_size, int min_cells, int mode, int64_t* d_best,
+                                   uint8_t* d_out_labels, float* d_out_cells, int64_t* d_removed, int64_t* d_kept, void* stream);
+
 /* Rays through the label volume (csrc/label_trace.hip): the first cell along a ray whose label belongs to a set -- an object from
  * a pixel, an edit previewed without the networks.  Additive (the ABI version stays).
  *   dmnerf_label_trace: d_labels [dx,dy,dz] uint8 over the box whose lower corner, cell size, 1 / cell size and dims are the HOST

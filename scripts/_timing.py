@@ -140,6 +140,23 @@ def random_baked(pct, dims, C):
     return set_cells, vol, cells
 
 
+def voronoi_labels(dims, n_labels, C, stray_pct=3.0, seed=0):
+    """A dims^3 uint8 volume that looks like objects with strays: the Voronoi partition of ``n_labels`` random seed points (label = the
+    nearest seed, the lowest on ties; squared distances in int64), then ``stray_pct`` per cent of the cells relabelled uniformly in
+    0 .. C - 1 (label C - 1 is "empty": it exists only as strays)."""
+    rng = np.random.RandomState(seed)
+    points = rng.randint(0, dims, size=(n_labels, 3)).astype(np.int64)
+    ax = np.arange(dims, dtype=np.int64)
+    vol = np.empty((dims,) * 3, np.uint8)
+    for i in range(dims):                                            # plane by plane: [n_labels, dims, dims] int64 at a time
+        d2 = (i - points[:, 0, None, None]) ** 2 + (ax[None, :, None] - points[:, 1, None, None]) ** 2 \
+            + (ax[None, None, :] - points[:, 2, None, None]) ** 2
+        vol[i] = np.argmin(d2, axis=0)
+    stray = rng.rand(dims, dims, dims) < stray_pct / 100.0
+    vol[stray] = rng.randint(0, C, size=int(stray.sum())).astype(np.uint8)
+    return vol
+
+
 def rigid(e=0, series="frame"):
     """The e-th rigid test move, a rotation about z and a shift, as a 4 x 4 float64 array.  ``rigid()`` is THE move of the frame
     scripts (0.2 rad, shift 0.3 / -0.2 / 0.1); series "frame" goes on with moves of the same size, alternating the shift's side;
