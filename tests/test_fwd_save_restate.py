@@ -12,11 +12,8 @@ import torch
 
 import _dgrad_restate as DR
 import _fwd_save_restate as FR
+from _gpu import ulp32
 from oracle import ref_cpu as O
-
-
-def ulp32(x):
-    return 2.0 ** (np.floor(np.log2(x)) - 23)
 
 
 def split(x):

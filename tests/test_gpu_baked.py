@@ -19,6 +19,8 @@ import _baked_restate as B
 import _label_grid_restate as LR
 import _label_trace_restate as T
 import _skip_restate as RS
+import _gpu
+from _gpu import A, model_from  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -28,15 +30,6 @@ NAN = float("nan")
 CONSTS = T.grid_consts(B.LO, B.HI, B.DIMS)
 
 
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D, editing as Ed, field as F
-    from dm_nerf_amd.networks import dm_nerf as M, render as R
-    _lib.load()
-    return types.SimpleNamespace(F=F, Ed=Ed, D=D, M=M, R=R, lib=_lib)
-
-
 # ---- dmnerf_bake_cells
 def bake_kernel(A, raw, C, thr):
     """The raw entry with one guard element behind each output."""
@@ -44,7 +37,7 @@ def bake_kernel(A, raw, C, thr):
     M = raw.shape[0]
     labels = torch.full((M + 1,), 77, dtype=torch.uint8, device="cuda")
     cells = torch.full((M + 1, 4), -7.0, dtype=torch.float32, device="cuda")
-    A.lib.check(A.lib.load().dmnerf_bake_cells(A.lib.ptr(raw), M, C, thr, A.lib.ptr(labels), A.lib.ptr(cells), A.lib.stream()), "dmnerf_bake_cells")
+    A.L.check(A.lib.dmnerf_bake_cells(A.L.ptr(raw), M, C, thr, A.L.ptr(labels), A.L.ptr(cells), A.L.stream()), "dmnerf_bake_cells")
     assert int(labels[M]) == 77 and bool((cells[M] == -7.0).all())
     return raw, labels[:M], cells[:M]
 
@@ -79,7 +72,7 @@ def crafted_rows(M, C, seed):
 def test_bake_cells_equals_label_cells_and_the_masked_rows(A, C, M):
     raw, labels, cells = bake_kernel(A, crafted_rows(M, C, 10 * C + M), C, 0.5)
     plain = torch.empty(M, dtype=torch.uint8, device="cuda")
-    A.lib.check(A.lib.load().dmnerf_label_cells(A.lib.ptr(raw), M, C, 0.5, A.lib.ptr(plain), A.lib.stream()), "dmnerf_label_cells")
+    A.L.check(A.lib.dmnerf_label_cells(A.L.ptr(raw), M, C, 0.5, A.L.ptr(plain), A.L.stream()), "dmnerf_label_cells")
     assert torch.equal(labels, plain)
     assert torch.equal(labels.cpu(), torch.from_numpy(LR.label_cells(raw.cpu().numpy(), C, 0.5)))
     want = torch.where((labels != 255)[:, None], raw[:, :4].view(torch.int32), torch.zeros(M, 4, dtype=torch.int32, device="cuda"))
@@ -95,9 +88,7 @@ _models = {}
 
 def model(A, ins_num):
     if ins_num not in _models:
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(O.make_weights(72, ins_num, gain=1.7, sigma_bias=0.0))
-        _models[ins_num] = m.cuda().eval()
+        _models[ins_num] = model_from(O.make_weights(72, ins_num, gain=1.7, sigma_bias=0.0), ins_num)
     return _models[ins_num]
 
 
@@ -129,7 +120,7 @@ def test_bake_grid_is_label_grid_with_the_rows_kept(A, split):
 def render_kernel(A, labels, cells, rays, masks, near, far, stop, Cn):
     """The raw entry with one guard element behind every output."""
     lo, cell, inv_cell, dims = CONSTS
-    L = A.lib
+    L = A.L
     vol, cel = torch.from_numpy(labels).cuda(), torch.from_numpy(cells).cuda()
     r = torch.from_numpy(np.ascontiguousarray(rays, dtype=f32)).cuda()
     R, _, N, _ = r.shape
@@ -299,16 +290,11 @@ def shift_x(dx):
     return m
 
 
-def frame_rays(A, trans_list, target_labels, keep=None):
-    """The rays ``preview_frame`` uses: ``ManipulationFrameRenderer``'s own."""
-    args = types.SimpleNamespace(N_importance=0, target_labels=list(target_labels))
-    fr = A.D.ManipulationFrameRenderer(H, W, K, torch.from_numpy(POSE), trans_list, None, args, ins_num=CS - 1, rank=0, world=1,
-                                       keep_labels=keep if (keep is not None or trans_list) else ())
-    return torch.cat([fr.ori[None], fr.tar], dim=0) if fr.T else fr.ori[None]
+renderer_rays = functools.partial(_gpu.renderer_rays, camera=(H, W, K, POSE), ins_num=CS - 1)
 
 
 def assert_preview(A, scene, out, trans_list, target_labels, sets, keep=None, stop=0.0):
-    want = scene.baked.render_sets(frame_rays(A, trans_list, target_labels, keep), sets, NEAR, FAR, stop)
+    want = scene.baked.render_sets(renderer_rays(A, trans_list, target_labels, keep), sets, NEAR, FAR, stop)
     assert tuple(out["rgb"].shape) == (H, W, 3) and tuple(out["nseg"].shape) == (H, W)
     for k in ("rgb", "depth", "acc"):
         assert torch.equal(out[k].reshape(-1).view(torch.int32), want[k].reshape(-1).view(torch.int32)), k

@@ -2,13 +2,13 @@
 ``field.Components``, ``field.SkipGrid.cleaned``): every array against its numpy statement (tests/_components_restate.py) with
 ``torch.equal``.  The shapes come from the kernel's tile ``(TI, TJ, TK)``: volumes smaller than a tile, one exact tile, two tiles along
 every axis (so every face, edge and corner between tiles exists) and dims that are no multiple of the tile."""
-import types
 
 import numpy as np
 import pytest
 import torch
 
 import _components_restate as CR
+import _gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -19,11 +19,10 @@ REF = {}                                                             # restated 
 
 @pytest.fixture(scope="module")
 def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, editing as Ed, field as F
-    _lib.load()
-    TI, TJ, TK = F.COMPONENTS_TILE
-    return types.SimpleNamespace(F=F, Ed=Ed, T=(TI, TJ, TK), two=(2 * TI, 2 * TJ, 2 * TK))
+    ns = _gpu.namespace()
+    TI, TJ, TK = ns.F.COMPONENTS_TILE
+    ns.T, ns.two = (TI, TJ, TK), (2 * TI, 2 * TJ, 2 * TK)
+    return ns
 
 
 def grid_of(A, v, C, cells=None):

@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 from oracle import analytic_scene as S
 
 pytestmark = pytest.mark.gpu
@@ -151,7 +152,7 @@ def _run_trajectory(mode, steps, eval_at, max_wgs=None):
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
     import make_train_traj as T
     from dm_nerf_amd import autograd as G
-    from dm_nerf_amd.networks import dm_nerf as M, evaluator as E, helpers as Hh, penalizer as P, render as R
+    from dm_nerf_amd.networks import evaluator as E, helpers as Hh, penalizer as P, render as R
     dev = torch.device("cuda:0")
     poses, ims, labs, K, test_rays = _setup(T.H, T.W, T.VIEWS, dev)
     rays_v = []
@@ -160,9 +161,7 @@ def _run_trajectory(mode, steps, eval_at, max_wgs=None):
         rays_v.append(torch.stack([ro.reshape(-1, 3), rd.reshape(-1, 3)]))
     d_ims, d_labs = ims.to(dev), labs.to(dev)
     sd_c, sd_f = T.start_weights()
-    mc, mf = M.DM_NeRF(8, 256, 63, 27, [4], T.INS_NUM), M.DM_NeRF(8, 256, 63, 27, [4], T.INS_NUM)
-    mc.load_state_dict(sd_c); mf.load_state_dict(sd_f)
-    mc, mf = mc.to(dev).train(), mf.to(dev).train()
+    mc, mf = _gpu.models(T.INS_NUM, train=True, state_dicts=(sd_c, sd_f), device=dev)
     opt = torch.optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=5e-4, betas=(0.9, 0.999))
     args = types.SimpleNamespace(perturb=1.0, N_importance=128, is_train=True, N_ins=None, tolerance=T.TOL, deta_w=T.DW, mfma_split=mode or False)
     z = Hh.z_val_sample(T.BATCH, S.NEAR, S.FAR, 64, device=dev)

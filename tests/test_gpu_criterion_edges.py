@@ -37,13 +37,14 @@ whole matched columns 16.5 ulp off where the oracle is 0.6 ulp off; cause: the p
 a partial sum near 1 in float32, in ray order; it is accumulated in float64 now.  Everything else -- assignments at C, V > 64, ties,
 ragged chunks, label ins_num, bad labels, the work buffer, the two-level entry -- passed unchanged.
 """
-import types
 
 import numpy as np
 import pytest
 import torch
 
 import _criterion_restate as CR
+import _gpu
+from _gpu import cpu
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -53,18 +54,9 @@ STATS = {}
 
 @pytest.fixture(scope="module")
 def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib
-    from dm_nerf_amd.networks import evaluator as E
-    _lib.load()
-    yield types.SimpleNamespace(E=E, lib=_lib)
+    yield _gpu.namespace()
     for fam, st in STATS.items():
         print(f"\n[criterion edges] {fam}: largest error {st.get('ulps', 0.0):.2f} ulp of the scale, needs {st.get('ratio', 0.0):.2f} x the oracle's error + 8 ulp")
-
-
-def cpu(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu()
 
 
 def stats(family, what):
@@ -136,7 +128,7 @@ def test_label_flags(A):
 
 def _raw(A, cs, fill, gouts):
     """The C entry points on one or two predictions (the *2 entries for two) with work buffers pre-filled with ``fill``."""
-    L = A.lib
+    L = A.L
     lib = L.load()
     N, C = cs[0].N, cs[0].C
     nbytes = lib.dmnerf_ins_criterion_work_bytes(N, C)

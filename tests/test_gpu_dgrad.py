@@ -24,14 +24,14 @@ the f32 kernel per ELEMENT |got - want| <= n 2^-24 sum|terms| with n = 259 per G
 OBSERVED on an MI355X (the module prints these figures per kernel and tensor when it finishes): see OBSERVED below the imports.
 """
 import math
-import types
 
-import numpy as np
 import pytest
 import torch
 
 import _dgrad_restate as DR
+import _gpu
 import _wgrad_restate as WR
+from _gpu import ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -77,10 +77,7 @@ MODELS = {}
 
 @pytest.fixture(scope="module")
 def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib
-    from dm_nerf_amd.networks import dm_nerf as M
-    yield types.SimpleNamespace(M=M, L=_lib, lib=_lib.load())
+    yield _gpu.namespace()
     MODELS.clear()
     for (kern, name), st in sorted(STATS.items()):
         print(f"\n[dgrad] {kern:12s} {name:5s}: needs {st['ratio']:.2f} x the float32 yardstick's error + 8 ulp ({st['where']}); largest error "
@@ -90,9 +87,7 @@ def A():
 def model(A, key, params, ins_num):
     """One DM_NeRF per parameter set, kept on the device (its four blobs are packed once)."""
     if key not in MODELS:
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(params)
-        MODELS[key] = m.cuda().train()
+        MODELS[key] = _gpu.model_from(params, ins_num, train=True)
     return MODELS[key]
 
 
@@ -164,10 +159,6 @@ def test_integer_operands_give_the_float64_gradients_exactly(A, case):
     for kern in KERNELS:
         dsave, gt = run(A, m, kern, case.M, save, gr)
         exact(DR.case_id(case), kern, dsave, gt, ref["want"], case.M, case.ins_num + 1)
-
-
-def ulp32(x):
-    return 2.0 ** (np.floor(np.log2(x)) - 23) if x > 0 else 0.0
 
 
 @pytest.mark.parametrize("case", DR.CASES, ids=DR.case_id)

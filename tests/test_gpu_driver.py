@@ -7,35 +7,17 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu import A, models  # noqa: F401  (fresh models per call; D / W other than 8 / 256 give a generic-path shape)
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, D=D)
-
-
-def models(A, ins_num=13, D=8, W=256):
-    """Coarse and fine DM_NeRF with synthetic weights; D / W other than 8 / 256 give a generic-path shape (dm_nerf_amd/generic.py)."""
-    out = []
-    for seed in (61, 62):
-        m = A.M.DM_NeRF(D, W, 63, 27, [4], ins_num)
-        m.load_state_dict(O.make_weights(seed, ins_num, W=W, D=D, gain=1.7, sigma_bias=0.3))
-        out.append(m.cuda().eval())
-    return out
 
 
 def test_render_frame_ragged_chunks_equal_one_shot_render(A):
     """A 9 x 13 frame in chunks of 50 rays (two full chunks + a ragged one of 17, tester.py:65-67) assembles to exactly
     what one dm_nerf call over all 117 rays returns: rays are independent, so chunking must not change a bit."""
     H, W = 9, 13
-    mc, mf = models(A)
+    mc, mf = models()
     K = np.array([[20.0, 0, W / 2], [0, -20.0, H / 2], [0, 0, -1]])
     c2w = O.pose_spherical(30.0, -65.0, 7.0).cuda()
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
@@ -59,7 +41,7 @@ def test_render_frame_ragged_chunks_equal_one_shot_render(A):
 def test_render_path_on_the_device(A):
     """The pose loop through the HIP path: two poses, ScanNet-style crop window, ground truth for the device PSNR."""
     H, W = 9, 13
-    mc, mf = models(A)
+    mc, mf = models()
     K = np.array([[20.0, 0, W / 2], [0, -20.0, H / 2], [0, 0, -1]])
     poses = torch.stack([O.pose_spherical(30.0, -65.0, 7.0), O.pose_spherical(80.0, -65.0, 7.0)]).cuda()
     mask = torch.zeros(H, W, dtype=torch.int64)
@@ -96,7 +78,7 @@ def test_render_step_is_graph_capturable(A):
     """No allocation, free or synchronisation inside the library: a dm_nerf render step records into a HIP graph and
     the replay on new ray data reproduces the eager result bit for bit."""
     N = 256
-    mc, mf = models(A)
+    mc, mf = models()
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(50.0, -65.0, 7.0))
     ro, rd = ro.reshape(-1, 3), rd.reshape(-1, 3)
@@ -145,7 +127,7 @@ def test_training_step_is_graph_capturable(A, mode):
                                  mfma_split=mode or False)
 
     def fresh():
-        mc, mf = models(A)
+        mc, mf = models()
         mc.train(); mf.train()
         opt = torch.optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=torch.tensor(5e-4, device="cuda"), capturable=True)
         return mc, mf, opt
@@ -160,7 +142,7 @@ def test_training_step_is_graph_capturable(A, mode):
     # graphed: constructed (and warmed up) on another batch, then the same three batches
     mc2, mf2, opt2 = fresh()
     gs = GraphedTrainStep((mc2, mf2), opt2, args, ins_num, batches[0][0], z, batches[0][1], batches[0][2])
-    start = [p.detach().clone() for m in models(A) for p in m.parameters()]
+    start = [p.detach().clone() for m in models() for p in m.parameters()]
     assert all(torch.equal(a, b) for a, b in zip(start, [p for m in (mc2, mf2) for p in m.parameters()])), "warm-up was not undone"
     torch.cuda.manual_seed(123)
     graph_losses = []
@@ -204,7 +186,7 @@ def eager_render_between_graph_replays(A, depth, width):
     eval_rays = torch.stack([ro[150000:150000 + N], rd[150000:150000 + N]]).cuda()
 
     def fresh():
-        mc, mf = models(A, D=depth, W=width)
+        mc, mf = models(D=depth, W=width)
         mc.train(); mf.train()
         opt = torch.optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=torch.tensor(5e-4, device="cuda"), capturable=True)
         return mc, mf, opt

@@ -9,34 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu import A, cpu, maxrel, model_from  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, autograd
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, manipulator as MA, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, G=autograd, MA=MA, lib=_lib)
-
-
-def cpu(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu()
-
-
-def maxrel(a, b):
-    return float(((a - b).abs() / (1 + b.abs())).max())
-
-
-def model_from(A, sd, ins_num, train=False):
-    m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-    m.load_state_dict(sd)
-    m = m.cuda()
-    return m.train() if train else m.eval()
 
 
 def _rays(n, seed, theta=33.0):
@@ -58,7 +34,7 @@ def test_n_importance_zero(A, perturb):
     args = types.SimpleNamespace(perturb=perturb, N_importance=0, is_train=False, N_ins=None)
     with torch.no_grad():
         want = O.dm_nerf(rays, sd_c, sd_f, z, perturb=perturb, N_importance=0, t_rand=t_rand)
-        mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+        mc, mf = model_from(sd_c, ins_num), model_from(sd_f, ins_num)
         got = A.R.dm_nerf(rays.cuda(), None, None, mc, mf, z.cuda(), args, t_rand=None if t_rand is None else t_rand.cuda())
     assert set(got) == set(want)
     assert got['raw_fine'].shape == (N, 64, 18) and got['z_vals_fine'].shape == (N, 64)
@@ -68,7 +44,7 @@ def test_n_importance_zero(A, perturb):
     for k in ('rgb_coarse', 'rgb_fine', 'ins_coarse', 'ins_fine', 'depth_coarse', 'depth_fine'):
         assert torch.allclose(cpu(got[k]), want[k], rtol=2e-6, atol=2e-6), k
     # training mode: same values, gradients reach both models
-    mc, mf = model_from(A, sd_c, ins_num, True), model_from(A, sd_f, ins_num, True)
+    mc, mf = model_from(sd_c, ins_num, train=True), model_from(sd_f, ins_num, train=True)
     targs = types.SimpleNamespace(perturb=perturb, N_importance=0, is_train=True, N_ins=None)
     out = A.R.dm_nerf(rays.cuda(), None, None, mc, mf, z.cuda(), targs, t_rand=None if t_rand is None else t_rand.cuda())
     assert torch.allclose(cpu(out['rgb_fine']), want['rgb_fine'], rtol=2e-6, atol=2e-6)
@@ -89,7 +65,7 @@ def test_model_forward_on_embedded_rows_is_differentiable(A):
         sdg = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
         want = O.mlp_forward(sdg, x)
         (want * cot).sum().backward()
-        m = model_from(A, sd, ins_num, train=True)
+        m = model_from(sd, ins_num, train=True)
         y = m(x.cuda())
         assert y.requires_grad and y.shape == want.shape
         assert maxrel(cpu(y), want.detach()) <= 1e-5
@@ -109,8 +85,8 @@ def test_frozen_fine_model_still_trains_the_coarse_one(A):
     """Training is decided from the parameters of BOTH models: with model_fine frozen, a loss on the coarse level must
     still produce gradients for model_coarse (it used to take the non-differentiable path)."""
     ins_num, N = 13, 24
-    mc = model_from(A, O.make_weights(87, ins_num, gain=1.7, sigma_bias=0.3), ins_num, True)
-    mf = model_from(A, O.make_weights(88, ins_num, gain=1.7, sigma_bias=0.3), ins_num, True)
+    mc = model_from(O.make_weights(87, ins_num, gain=1.7, sigma_bias=0.3), ins_num, train=True)
+    mf = model_from(O.make_weights(88, ins_num, gain=1.7, sigma_bias=0.3), ins_num, train=True)
     for p in mf.parameters():
         p.requires_grad_(False)
     args = types.SimpleNamespace(perturb=0.0, N_importance=128, is_train=True, N_ins=None)
@@ -124,7 +100,7 @@ def test_frozen_fine_model_still_trains_the_coarse_one(A):
 def test_wrong_shaped_random_draws_are_refused(A):
     """Caller-supplied t_rand / u reach the kernels as raw pointers: a wrong shape must raise, not read out of bounds."""
     ins_num, N = 13, 16
-    mc, mf = model_from(A, O.make_weights(1, ins_num), ins_num), model_from(A, O.make_weights(2, ins_num), ins_num)
+    mc, mf = model_from(O.make_weights(1, ins_num), ins_num), model_from(O.make_weights(2, ins_num), ins_num)
     rays, z = _rays(N, 3).cuda(), A.H.z_val_sample(N, 4.0, 15.0, 64)
     jit = types.SimpleNamespace(perturb=1.0, N_importance=128, is_train=False, N_ins=None)
     det = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
@@ -154,7 +130,7 @@ def test_wrong_shaped_random_draws_are_refused(A):
 def test_invalidate_blobs_after_a_data_update(A):
     """An in-place op on the parameter bumps ``_version`` and refreshes the packed weights by itself; an update THROUGH
     ``.data`` does not (no version bump) -- ``invalidate_blobs()`` is the documented way to make it visible."""
-    m = model_from(A, O.make_weights(4, 13, gain=1.7), 13)
+    m = model_from(O.make_weights(4, 13, gain=1.7), 13)
     x = torch.randn(64, 90).cuda()
     with torch.no_grad():
         y0 = m(x)
@@ -208,14 +184,14 @@ def test_manipulation_with_the_maximum_number_of_moved_objects_composites(A):
 
 def test_error_messages_are_per_thread(A):
     """``dmnerf_last_error()`` is thread-local: two host threads failing with different messages each read their own."""
-    lib = A.lib.load()
+    lib = A.lib
     seen = {}
 
     def fail(tag, S):
         rc = lib.dmnerf_composite_fwd(None, None, None, 4, S, 14, None, None, None, None, None)
         for _ in range(200):                                                  # give the other thread every chance to interfere
             lib.dmnerf_composite_fwd(None, None, None, 4, S, 14, None, None, None, None, None)
-        seen[tag] = (rc, A.lib.last_error())
+        seen[tag] = (rc, A.L.last_error())
 
     ts = [threading.Thread(target=fail, args=("a", 5000)), threading.Thread(target=fail, args=("b", 64))]
     for t in ts:
@@ -254,11 +230,10 @@ def test_training_batches_beyond_the_launch_limit_run_as_several_launches(monkey
     independent), gradients equal to the single launch's up to the summation order; an over-long direct C-ABI call is refused."""
     import types
     from dm_nerf_amd import _lib, autograd as G
-    from dm_nerf_amd.networks import dm_nerf as M
     lib = _lib.load()
     torch.manual_seed(3)
     ins_num, N, S = 13, 100, 64
-    m = M.DM_NeRF(8, 256, 63, 27, [4], ins_num).cuda().train()
+    m = model_from(None, ins_num, train=True)
     g = torch.Generator(device="cuda").manual_seed(4)
     ro, rd = torch.randn(N, 3, device="cuda", generator=g), torch.randn(N, 3, device="cuda", generator=g)
     z = torch.sort(torch.rand(N, S, device="cuda", generator=g) * 5 + 1, -1)[0]
@@ -304,8 +279,8 @@ def test_training_batches_beyond_the_launch_limit_run_as_several_launches(monkey
 def test_more_objects_than_the_abi_supports_is_refused_loudly():
     """C = ins_num + 1 <= DMNERF_MAX_LOGITS = 128 (include/dmnerf_hip.h; Replica room_0 has 94): ins_num = 128 constructs (it is
     an ordinary nn.Module) but every path into a kernel raises instead of truncating the object-code head."""
-    from dm_nerf_amd.networks import dm_nerf as M, render as R
-    m = M.DM_NeRF(8, 256, 63, 27, [4], 128).cuda()
+    from dm_nerf_amd.networks import render as R
+    m = model_from(None, 128, train=True)
     with pytest.raises((ValueError, RuntimeError)):
         m.blob()
     ro, rd = torch.randn(4, 3, device="cuda"), torch.randn(4, 3, device="cuda")
@@ -319,7 +294,7 @@ def test_more_objects_than_the_abi_supports_is_refused_loudly():
 def test_empty_training_batch_gives_zero_gradients(A):
     """An empty batch (a rank whose shard of a tiny batch is empty) trains without error: raw [0, S, 4 + C], zero gradients."""
     from dm_nerf_amd import autograd as G
-    m = A.M.DM_NeRF(8, 256, 63, 27, [4], 13).cuda().train()
+    m = model_from(None, 13, train=True)
     ro, rd = torch.empty(0, 3, device="cuda"), torch.empty(0, 3, device="cuda")
     z = torch.empty(0, 64, device="cuda")
     raw = G.run_network_train(m, ro, rd, z)
@@ -347,7 +322,7 @@ def test_f16x2_range_of_the_two_plane_split(A, capsys):
     for gain in (4.5, 8.0):
         sd = O.make_weights(21, ins_num, gain=gain)
         want = O.mlp_forward(sd, x).reshape(N, S, -1)
-        m = model_from(A, sd, ins_num)
+        m = model_from(sd, ins_num)
         with torch.no_grad():
             got32 = cpu(A.R.run_network(m, ro.cuda(), rd.cuda(), z.cuda()))
             got16 = cpu(A.R.run_network(m, ro.cuda(), rd.cuda(), z.cuda(), split="f16x2"))
@@ -376,7 +351,7 @@ def test_f16x2_saturation_is_reported_when_the_check_is_on(A, monkeypatch):
     z = O.z_val_sample(N, 4.0, 15.0, 64).contiguous().cuda()
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None, mfma_split="f16x2", check_f16=True)
     for gain, expect in ((1.7, False), (8.0, True)):
-        mc, mf = model_from(A, O.make_weights(21, ins_num, gain=gain), ins_num), model_from(A, O.make_weights(22, ins_num, gain=gain), ins_num)
+        mc, mf = model_from(O.make_weights(21, ins_num, gain=gain), ins_num), model_from(O.make_weights(22, ins_num, gain=gain), ins_num)
         with warnings.catch_warnings(record=True) as w:
             warnings.simplefilter("always")
             with torch.no_grad():
@@ -402,7 +377,7 @@ def test_f16x2_saturation_is_reported_when_the_check_is_on(A, monkeypatch):
         flags = G.check_f16x2()
     assert flags & G.F16_ACT_SATURATED
     assert G.check_f16x2(warn=False) == 0
-    small_c, small_f = model_from(A, O.make_weights(21, ins_num, gain=1.7), ins_num).train(), model_from(A, O.make_weights(22, ins_num, gain=1.7), ins_num).train()
+    small_c, small_f = model_from(O.make_weights(21, ins_num, gain=1.7), ins_num).train(), model_from(O.make_weights(22, ins_num, gain=1.7), ins_num).train()
     o = R.dm_nerf(rays, None, None, small_c, small_f, z, targs)
     (o['rgb_fine'].sum() + o['rgb_coarse'].sum()).backward()
     assert G.check_f16x2(warn=False) == 0                                      # inside the range (ragged M too): no false alarm
@@ -415,10 +390,9 @@ def test_overlapped_backward_with_three_launches_per_model_sends_only_the_first_
     4096 samples a 150-ray x 64-sample batch is 3 launches per model; two models as in a training step.  The gradients equal the
     one-stream pass bit for bit, over several repetitions, and the side stream is taken exactly once per model-pass that may."""
     from dm_nerf_amd import autograd as G
-    from dm_nerf_amd.networks import dm_nerf as M
     torch.manual_seed(5)
     ins_num, N, S = 13, 150, 64
-    ms = [M.DM_NeRF(8, 256, 63, 27, [4], ins_num).cuda().train() for _ in range(2)]
+    ms = [model_from(None, ins_num, train=True) for _ in range(2)]
     g = torch.Generator(device="cuda").manual_seed(6)
     ro, rd = torch.randn(N, 3, device="cuda", generator=g), torch.randn(N, 3, device="cuda", generator=g)
     z = torch.sort(torch.rand(N, S, device="cuda", generator=g) * 5 + 1, -1)[0]
@@ -467,7 +441,7 @@ def test_f16x2_check_via_args_reaches_training_and_the_probe_runs_in_pieces(A, m
     rays = torch.stack([ro.reshape(-1, 3)[5000:5000 + N], rd.reshape(-1, 3)[5000:5000 + N]]).cuda()
     z = O.z_val_sample(N, 4.0, 15.0, 64).contiguous().cuda()
     assert G.CHECK_F16 is None and not G.f16_check_enabled()
-    big_c, big_f = model_from(A, O.make_weights(21, ins_num, gain=8.0), ins_num).train(), model_from(A, O.make_weights(22, ins_num, gain=8.0), ins_num).train()
+    big_c, big_f = model_from(O.make_weights(21, ins_num, gain=8.0), ins_num).train(), model_from(O.make_weights(22, ins_num, gain=8.0), ins_num).train()
     for chk, expect in ((True, True), (None, False)):
         targs = types.SimpleNamespace(perturb=0.0, N_importance=128, is_train=True, N_ins=None, mfma_split="f16x2", check_f16=chk)
         o = R.dm_nerf(rays, None, None, big_c, big_f, z, targs)

@@ -9,6 +9,7 @@ import types
 import pytest
 import torch
 
+import _gpu
 import _edit_kinds_restate as RS
 from oracle import ref_cpu as O
 
@@ -77,12 +78,9 @@ NR, NS, NI, INS = 67, 8, 16, 3
 @pytest.fixture(scope="module")
 def scene():
     assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd.networks import dm_nerf as DM
 
     def mk(seed):
-        m = DM.DM_NeRF(8, 256, 63, 27, [4], INS)
-        m.load_state_dict(O.make_weights(seed, INS, **O.PEAKY))
-        return m.cuda().eval()
+        return _gpu.model_from(O.make_weights(seed, INS, **O.PEAKY), INS)
     K = O.dmsr_intrinsics(24, 32)
     ro, rd = O.get_rays_k(24, 32, K, O.pose_spherical(75.0, -65.0, 7.0))
     sel = torch.arange(NR) * 11 % (24 * 32)

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -28,10 +29,7 @@ SIZES = (64, 64, 32)
 
 
 def _mk(seed, ins_num):
-    from dm_nerf_amd.networks import dm_nerf as M
-    m = M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-    m.load_state_dict(O.make_weights(int(seed), ins_num, **O.PEAKY))
-    return m.cuda().eval()
+    return _gpu.model_from(O.make_weights(int(seed), ins_num, **O.PEAKY), ins_num)
 
 
 @functools.lru_cache(maxsize=None)

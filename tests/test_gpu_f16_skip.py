@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-import _skip_restate as RS
+import _gpu
+from _gpu import A, frame_rays, model_from, random_grid  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -18,46 +19,17 @@ POISON = 0x40000000                    # an int32 far beyond every sample index 
 SENTINEL = 777.0
 SHAPES = [(1, 1), (3, 5), (7, 64), (130, 192)]
 
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D, field as F
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, D=D, F=F, lib=_lib)
-
-
 _cache = {}
 
 
-def models(A, ins_num=13):
-    if ins_num not in _cache:
-        out = []
-        for seed in (61, 62):
-            m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-            m.load_state_dict(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3))
-            out.append(m.cuda().eval())
-        _cache[ins_num] = out
-    return _cache[ins_num]
-
-
-def frame_rays(n, start=0):
-    K = O.dmsr_intrinsics(480, 640)
-    ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(30.0, -65.0, 7.0))
-    ro, rd = ro.reshape(-1, 3)[start:start + n * 97:97], rd.reshape(-1, 3)[start:start + n * 97:97]
-    return ro.contiguous().cuda(), rd.contiguous().cuda()
-
-
-def random_grid(A, dims, lo, hi, frac, seed, outside="evaluate"):
-    occ = np.random.RandomState(seed).rand(*dims) < frac
-    return A.F.SkipGrid.from_bits(RS.pack_bits(occ), lo, hi, dims, outside=outside)
+def models(ins_num=13):
+    return _gpu.models(ins_num, cache=_cache)
 
 
 def select(A, grid, ro, rd, z):
     """``dmnerf_skip_select`` -> (flag [N,S] uint8, sel int32 [N*S] (poison beyond count), count int32 [1])."""
     N, S = z.shape
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     flag = torch.full((N, S), 77, dtype=torch.uint8, device="cuda")
     sel = torch.full((N * S,), POISON, dtype=torch.int32, device="cuda")
     count = torch.full((2,), POISON, dtype=torch.int32, device="cuda")
@@ -79,10 +51,10 @@ def dense_f16(A, ins_num, n, s):
     """(ro, rd, z, raw) of ``dmnerf_mlp_fwd_rays_f16`` with the fine model: computed once per shape, shared, never written again."""
     key = (ins_num, n, s)
     if key not in _dense:
-        mf = models(A, ins_num)[1]
+        mf = models(ins_num)[1]
         ro, rd = frame_rays(n, start=4000)
         z = depths(n, s)
-        L, lib = A.lib, A.lib.load()
+        L, lib = A.L, A.lib
         raw = torch.full((n, s, 4 + ins_num + 1), SENTINEL, device="cuda")
         L.check(lib.dmnerf_mlp_fwd_rays_f16(L.ptr(mf.blob_f16()), ins_num, L.ptr(ro), L.ptr(rd), L.ptr(z), n, s, L.ptr(raw), L.stream()), "f16")
         assert not bool((raw == SENTINEL).any()) and float(raw[..., 3].abs().max()) > 0
@@ -93,9 +65,9 @@ def dense_f16(A, ins_num, n, s):
 # ---- 1. density-only, dense
 @pytest.mark.parametrize("n,s,ins_num", [(n, s, 13) for n, s in SHAPES] + [(3, 5, 93)])
 def test_density_f16_equals_the_density_channel_of_the_full_kernel(A, n, s, ins_num):
-    mf = models(A, ins_num)[1]
+    mf = models(ins_num)[1]
     ro, rd, z, raw = dense_f16(A, ins_num, n, s)
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     blob = mf.blob_f16_density()
     assert blob.numel() == lib.dmnerf_blob_f16_density_words(ins_num) and blob is mf.blob_f16_density()
     sigma = torch.full((n, s), SENTINEL, device="cuda")
@@ -106,10 +78,8 @@ def test_density_f16_equals_the_density_channel_of_the_full_kernel(A, n, s, ins_
 def test_density_blob_refreshes_after_load_state_dict(A):
     ins_num, n, s = 13, 3, 5
     ro, rd, z, raw = dense_f16(A, ins_num, n, s)
-    L, lib = A.lib, A.lib.load()
-    m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-    m.load_state_dict(O.make_weights(7, ins_num, gain=1.7, sigma_bias=0.3))
-    m = m.cuda().eval()
+    L, lib = A.L, A.lib
+    m = model_from(O.make_weights(7, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
 
     def sigma_of(model):
         out = torch.full((n, s), SENTINEL, device="cuda")
@@ -127,7 +97,7 @@ def sel_lists(A, n, s, ro, rd, z):
     M = n * s
     perm = torch.randperm(M, generator=torch.Generator().manual_seed(M)).to(torch.int32)          # deliberately unsorted
     out = [(c, perm[:c].cuda()) for c in (0, 1, 31, 32, 33, 128, 129, M) if c <= M]
-    grid = random_grid(A, (8, 8, 8), (-4.0, -4.0, -4.0), (4.0, 4.0, 4.0), 0.4, seed=11)
+    grid = random_grid((8, 8, 8), (-4.0, -4.0, -4.0), (4.0, 4.0, 4.0), 0.4, seed=11)
     _, sel, count = select(A, grid, ro, rd, z)                       # ascending, from the product's own select
     out.append((int(count), sel[:int(count)].clone()))
     return out
@@ -150,9 +120,9 @@ def check_sel(A, run_sel, dense, n, s, lists):
 
 @pytest.mark.parametrize("n,s,ins_num", [(n, s, 13) for n, s in SHAPES] + [(3, 5, 59), (7, 64, 59), (3, 5, 93), (7, 64, 93)])
 def test_f16_sel_writes_the_dense_rows_and_nothing_else(A, n, s, ins_num):
-    mf = models(A, ins_num)[1]
+    mf = models(ins_num)[1]
     ro, rd, z, raw = dense_f16(A, ins_num, n, s)
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     lists = sel_lists(A, n, s, ro, rd, z)
     if n * s >= 448:
         assert 0 < lists[-1][0] < n * s
@@ -164,9 +134,9 @@ def test_f16_sel_writes_the_dense_rows_and_nothing_else(A, n, s, ins_num):
 @pytest.mark.parametrize("n,s", SHAPES)
 def test_density_f16_sel_writes_the_dense_entries_and_nothing_else(A, n, s):
     ins_num = 13
-    mf = models(A, ins_num)[1]
+    mf = models(ins_num)[1]
     ro, rd, z, raw = dense_f16(A, ins_num, n, s)
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     check_sel(A, lambda sel, count, out: L.check(lib.dmnerf_mlp_fwd_rays_density_f16_sel(
         L.ptr(mf.blob_f16_density()), ins_num, L.ptr(ro), L.ptr(rd), L.ptr(z), n, s, L.ptr(sel), L.ptr(count), L.ptr(out), L.stream()),
         "density_f16_sel"), raw[..., 3].contiguous(), n, s, sel_lists(A, n, s, ro, rd, z))
@@ -191,7 +161,7 @@ def render_case(A, perturb=False, n=96):
 
 @pytest.mark.parametrize("perturb", [False, True])
 def test_dm_nerf_fine_f16_equals_dm_nerf(A, perturb):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, draws = render_case(A, perturb)
     rays = torch.stack([ro, rd])
     with torch.no_grad():
@@ -205,7 +175,7 @@ def test_dm_nerf_fine_f16_equals_dm_nerf(A, perturb):
 
 
 def test_fine_f16_eligibility_and_refusals(A):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, _ = render_case(A)
     rays = torch.stack([ro, rd])
     f32 = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
@@ -227,7 +197,7 @@ def test_fine_f16_eligibility_and_refusals(A):
 def restate_render(A, mc, mf, ro, rd, z, args, grid, levels, t_rand=None, u=None):
     """The masked f16x2 render composed from product calls: dense f16 coarse -> raw[..., 3] * flag -> weights -> resampling -> dense
     f16 fine -> rows masked to zero -> compositing."""
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     n, s = z.shape
     n_imp = args.N_importance
     z_c = A.H.stratify(z, t_rand) if t_rand is not None else z
@@ -250,7 +220,7 @@ def restate_render(A, mc, mf, ro, rd, z, args, grid, levels, t_rand=None, u=None
 
 
 def test_f16_skip_with_a_full_grid_equals_dm_nerf_fine_f16(A):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, _ = render_case(A)
     rays = torch.stack([ro, rd])
     with torch.no_grad():
@@ -263,7 +233,7 @@ def test_f16_skip_with_a_full_grid_equals_dm_nerf_fine_f16(A):
 
 
 def test_f16_skip_with_an_empty_grid_is_zero(A):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, _ = render_case(A)
     with torch.no_grad():
         got = A.R.dm_nerf_fine_skip(torch.stack([ro, rd]), None, None, mc, mf, z, args, A.F.SkipGrid.empty(*BOX, outside="empty"))
@@ -275,10 +245,10 @@ def test_f16_skip_with_an_empty_grid_is_zero(A):
 
 @pytest.mark.parametrize("case", ["both", "fine_only", "both_perturb", "fine_only_perturb"])
 def test_f16_skip_with_a_random_grid_equals_the_masked_dense_render(A, case):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, draws = render_case(A, perturb=case.endswith("perturb"))
     levels = ("fine",) if case.startswith("fine_only") else ("coarse", "fine")
-    grid = random_grid(A, BOX[2], BOX[0], BOX[1], 0.3, seed=21)
+    grid = random_grid(BOX[2], BOX[0], BOX[1], 0.3, seed=21)
     with torch.no_grad():
         want, n_eval = restate_render(A, mc, mf, ro, rd, z, args, grid, levels, **draws)
         got = A.R.dm_nerf_fine_skip(torch.stack([ro, rd]), None, None, mc, mf, z, args, grid, levels=levels, **draws)
@@ -297,11 +267,11 @@ def test_f16_skip_with_a_random_grid_equals_the_masked_dense_render(A, case):
 def test_f16_frame_with_skip_equals_the_per_chunk_restatement(A, chunk):
     """24 x 20 = 480 rays: chunk 96 divides them into five whole chunks, chunk 100 leaves a ragged last chunk of 80."""
     H, W = 20, 24
-    mc, mf = models(A)
+    mc, mf = models()
     K = np.array([[30.0, 0, W / 2], [0, -30.0, H / 2], [0, 0, -1]])
     c2w = O.pose_spherical(30.0, -65.0, 7.0).cuda()
     args = f16_args(N_test=chunk, N_samples=64, near=4.0, far=15.0)
-    grid = random_grid(A, BOX[2], BOX[0], BOX[1], 0.3, seed=22)
+    grid = random_grid(BOX[2], BOX[0], BOX[1], 0.3, seed=22)
     with torch.no_grad():
         rgb, ins, depth = A.D.render_frame(H, W, K, c2w, (mc, mf), 4.0, 15.0, args, chunk=chunk, n_samples=64, skip=grid)
         ro, rd = A.H.get_rays_k(H, W, K, c2w)
@@ -328,11 +298,11 @@ def test_f16_frame_with_skip_equals_the_per_chunk_restatement(A, chunk):
 
 # ---- 6. capture
 def test_f16_captured_render_follows_grid_and_rays_overwritten_in_place(A):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, _ = render_case(A)
     ro_b, rd_b = frame_rays(96, start=150000)
-    grid_a = random_grid(A, BOX[2], BOX[0], BOX[1], 0.3, seed=31)
-    grid_b = random_grid(A, BOX[2], BOX[0], BOX[1], 0.7, seed=32)
+    grid_a = random_grid(BOX[2], BOX[0], BOX[1], 0.3, seed=31)
+    grid_b = random_grid(BOX[2], BOX[0], BOX[1], 0.7, seed=32)
     grid = A.F.SkipGrid.from_bits(grid_a.bits.clone(), BOX[0], BOX[1], BOX[2])
     rays = torch.stack([ro, rd])
     with torch.no_grad():

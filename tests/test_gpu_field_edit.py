@@ -12,7 +12,9 @@ import pytest
 import torch
 
 import _field_edit_restate as R
+import _gpu
 import _volume_edit_restate as V
+from _gpu import A  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -22,27 +24,11 @@ INS = 13
 C14 = INS + 1
 
 
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D, editing as Ed, field as F
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, manipulator as MA, render as RD
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=RD, D=D, F=F, MA=MA, Ed=Ed, lib=_lib)
-
-
 _models = {}
 
 
-def models(A):
-    if "m" not in _models:
-        out = []
-        for seed in (61, 62):
-            m = A.M.DM_NeRF(8, 256, 63, 27, [4], INS)
-            m.load_state_dict(O.make_weights(seed, INS, gain=1.7, sigma_bias=0.3))
-            out.append(m.cuda().eval())
-        _models["m"] = out
-    return _models["m"]
+def models():
+    return _gpu.models(INS, cache=_models)
 
 
 def as_trans(A, entries):
@@ -56,7 +42,7 @@ def bits(t):
 
 def c_entries(A, entries):
     E = len(entries)
-    arr = (A.lib.VolumeEditEntry * E)() if E else None
+    arr = (A.L.VolumeEditEntry * E)() if E else None
     for e, (k, l, m) in enumerate(entries):
         arr[e].kind, arr[e].label = k, l
         if k != V.REMOVE:
@@ -73,9 +59,9 @@ def run_select(A, src, lo, inv_cell, entries, o, d, z, C, outside, unowned, tota
     t = {"owner": torch.full((M,), 77, dtype=torch.uint8, device=dev), "o_w": torch.full((M, 3), -7.0, device=dev),
          "d_w": torch.full((M, 3), -7.0, device=dev), "sel": torch.full((M,), -1, dtype=torch.int32, device=dev),
          "count": torch.full((1,), -1, dtype=torch.int32, device=dev), "rows": torch.full((M, 4 + C), 7.0, device=dev)}
-    work = torch.empty(int(A.lib.load().dmnerf_skip_select_work_ints(M)), dtype=torch.int32, device=dev)
+    work = torch.empty(int(A.lib.dmnerf_skip_select_work_ints(M)), dtype=torch.int32, device=dev)
     fill = torch.from_numpy(R.empty_row(C)).cuda()
-    A.lib.launch("dmnerf_field_edit_select", torch.from_numpy(src).cuda(), f3(lo), f3(inv_cell), (ctypes.c_int * 3)(*src.shape), outside, unowned,
+    A.L.launch("dmnerf_field_edit_select", torch.from_numpy(src).cuda(), f3(lo), f3(inv_cell), (ctypes.c_int * 3)(*src.shape), outside, unowned,
                  c_entries(A, entries), len(entries), C, torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda(), torch.from_numpy(z).cuda(), N, S,
                  t["owner"], t["o_w"], t["d_w"], t["sel"], t["count"], work, t["rows"], fill, totals)
     torch.cuda.synchronize()
@@ -129,16 +115,16 @@ def test_filter_equals_the_restatement(A, C):
     fill = torch.from_numpy(R.empty_row(C)).cuda()
     pad = torch.full((M + 2, 4 + C), 3.0, device="cuda")            # the rows sit inside a poisoned buffer
     pad[1:M + 1] = d_raw
-    A.lib.launch("dmnerf_field_edit_filter", pad[1:M + 1], torch.from_numpy(owner).cuda(), M, C, words, E, fill, kept)
+    A.L.launch("dmnerf_field_edit_filter", pad[1:M + 1], torch.from_numpy(owner).cuda(), M, C, words, E, fill, kept)
     want, want_kept = R.filter_rows(raw, owner, masks, R.empty_row(C))
     assert torch.equal(bits(pad[1:M + 1].cpu()), bits(torch.from_numpy(want)))
     assert bool((pad[0] == 3.0).all()) and bool((pad[M + 1] == 3.0).all())
     assert kept.tolist() == want_kept.tolist() and 0 < want_kept[0] and want_kept[3] == 0
-    A.lib.launch("dmnerf_field_edit_filter", pad[1:M + 1], torch.from_numpy(owner).cuda(), M, C, words, E, fill, None)     # no kept: legal
+    A.L.launch("dmnerf_field_edit_filter", pad[1:M + 1], torch.from_numpy(owner).cuda(), M, C, words, E, fill, None)     # no kept: legal
 
 
 def test_entries_refuse_bad_arguments(A):
-    lib = A.lib.load()
+    lib = A.lib
     f3, i3 = (ctypes.c_float * 3)(0, 0, 0), (ctypes.c_int * 3)(4, 4, 4)
     one, ow, dw, rows, fill = (torch.zeros(64, device="cuda") for _ in range(5))
     b = torch.zeros(64, dtype=torch.uint8, device="cuda")
@@ -173,7 +159,7 @@ def field_case(N=37, S=7, seed=9):
 
 @pytest.mark.parametrize("split", [None, "f16x2"])
 def test_identity_edit_equals_run_network(A, split):
-    mc, _ = models(A)
+    mc, _ = models()
     o, d, z = field_case()
     src = torch.zeros(7, 5, 9, dtype=torch.uint8, device="cuda")
     edit = A.Ed.FieldEdit.from_source(src, *R.BOX, [], [], C=C14)
@@ -185,7 +171,7 @@ def test_identity_edit_equals_run_network(A, split):
 
 @pytest.mark.parametrize("split", [None, "f16x2"])
 def test_no_edit_with_empty_policies_equals_the_skip_route(A, split):
-    mc, _ = models(A)
+    mc, _ = models()
     o, d, z = field_case()
     labels, _ = V.random_volume((7, 5, 9), C14, seed=4)
     grid = A.F.LabelGrid.from_labels(torch.from_numpy(labels).cuda(), *R.BOX, C14)
@@ -202,7 +188,7 @@ def test_no_edit_with_empty_policies_equals_the_skip_route(A, split):
 
 @pytest.mark.parametrize("S", [7, 64])
 def test_one_rigid_move_evaluates_each_sample_once_on_the_carried_ray(A, S):
-    mc, _ = models(A)
+    mc, _ = models()
     o, d, z = field_case(S=S)
     dims = (7, 5, 9)
     move = V.translation([0.3, 0.0, 0.0]) @ V.rotation([0.2, 1.0, 0.1], 0.4)
@@ -260,7 +246,7 @@ def test_field_edit_hands_the_kernels_the_restated_masks_and_entries(A):
 
 
 def test_refusals_of_the_python_route(A):
-    mc, _ = models(A)
+    mc, _ = models()
     o, d, z = field_case()
     src = torch.zeros(7, 5, 9, dtype=torch.uint8, device="cuda")
     edit = A.Ed.FieldEdit.from_source(src, *R.BOX, [], [], C=C14)
@@ -301,7 +287,7 @@ def moved_edit(A, seed=12, **kw):
 
 @pytest.mark.parametrize("split", [None, "f16x2"])
 def test_edited_field_equals_the_chain_written_out(A, split):
-    mc, mf = models(A)
+    mc, mf = models()
     o, d, _ = field_case()
     args = chain_args(split)
     edit, _, _ = moved_edit(A)
@@ -321,7 +307,7 @@ def test_edited_field_equals_the_chain_written_out(A, split):
 
 def test_frame_is_the_same_for_world_1_and_the_bands_of_world_3(A):
     H, W, chunk = 12, 16, 64
-    mc, mf = models(A)
+    mc, mf = models()
     K = np.array([[20.0, 0, W / 2], [0, -20.0, H / 2], [0, 0, -1]])
     pose = O.pose_spherical(30.0, -65.0, 1.6).cuda()
     args = types.SimpleNamespace(N_samples=8, N_importance=8, near=0.3, far=3.0, N_test=chunk, target_labels=[])
@@ -372,7 +358,7 @@ def test_frame_is_the_same_for_world_1_and_the_bands_of_world_3(A):
 
 
 def test_captured_chunk_follows_the_source_overwritten_in_place(A):
-    mc, mf = models(A)
+    mc, mf = models()
     o, d, _ = field_case()
     rays = torch.stack([o, d])
     args = chain_args()

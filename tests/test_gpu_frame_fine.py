@@ -8,41 +8,17 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
+from _gpu import A, frame_rays  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, D=D, lib=_lib)
-
-
 _model_cache = {}
 
 
-def models(A, ins_num=13, D=8, W=256):
-    key = (ins_num, D, W)
-    if key not in _model_cache:
-        out = []
-        for seed in (61, 62):
-            m = A.M.DM_NeRF(D, W, 63, 27, [4], ins_num)
-            m.load_state_dict(O.make_weights(seed, ins_num, W=W, D=D, gain=1.7, sigma_bias=0.3))
-            out.append(m.cuda().eval())
-        _model_cache[key] = out
-    return _model_cache[key]
-
-
-def frame_rays(A, n, start=0):
-    """``n`` consecutive rays of the benchmark's camera (640 x 480, pose_spherical(30, -65, 7))."""
-    K = O.dmsr_intrinsics(480, 640)
-    ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(30.0, -65.0, 7.0))
-    ro, rd = ro.reshape(-1, 3)[start:start + n], rd.reshape(-1, 3)[start:start + n]
-    return ro.contiguous().cuda(), rd.contiguous().cuda()
+def models(ins_num=13, D=8, W=256):
+    return _gpu.models(ins_num, D, W, cache=_model_cache)
 
 
 def jittered_z(n, s, seed):
@@ -52,7 +28,7 @@ def jittered_z(n, s, seed):
 
 def density(A, blob, ins_num, ro, rd, z):
     sigma = torch.full(z.shape, float("nan"), dtype=torch.float32, device=z.device)
-    L = A.lib
+    L = A.L
     L.check(L.load().dmnerf_mlp_fwd_rays_density(L.ptr(blob), ins_num, L.ptr(ro), L.ptr(rd), L.ptr(z), z.shape[0], z.shape[1],
                                                  L.ptr(sigma), L.stream()), "dmnerf_mlp_fwd_rays_density")
     return sigma
@@ -64,8 +40,8 @@ def density(A, blob, ins_num, ro, rd, z):
 def test_density_entry_equals_the_full_kernels_sigma(A, ins_num, n, s):
     """N*S = 512 (a multiple of 128), 192 (of 32 but not 128: duplicate waves in the last workgroup), 119 and 1 (tail lanes),
     19200 (many workgroups); ins_num moves the table offsets of density_linear with the logit-block count."""
-    mc, _ = models(A, ins_num)
-    ro, rd = frame_rays(A, n, start=1000 * ins_num)
+    mc, _ = models(ins_num)
+    ro, rd = frame_rays(n, start=1000 * ins_num, stride=1)
     z = jittered_z(n, s, seed=n * 100 + s)
     with torch.no_grad():
         raw = A.R.run_network(mc, ro, rd, z)
@@ -83,11 +59,11 @@ def test_weights_kernel_equals_render_trains_weights(A, s):
     g = torch.Generator().manual_seed(s)
     raw = torch.randn(n, s, 4 + C, generator=g).cuda()
     raw[..., 3] = raw[..., 3] * 3.0                              # negative densities (relu), opaque and thin samples
-    _, rd = frame_rays(A, n, start=5000)
+    _, rd = frame_rays(n, start=5000, stride=1)
     z = jittered_z(n, s, seed=7 + s)
     sigma = raw[..., 3].contiguous()
     got = torch.full((n, s), float("nan"), dtype=torch.float32, device="cuda")
-    L = A.lib
+    L = A.L
     with torch.no_grad():
         _, want, _, _ = A.R.render_train(raw, z, rd)
         L.check(L.load().dmnerf_weights_from_sigma(L.ptr(sigma), L.ptr(z), L.ptr(rd), n, s, L.ptr(got), L.stream()), "dmnerf_weights_from_sigma")
@@ -114,8 +90,8 @@ def test_fine_entry_equals_dm_nerf(A, case):
     if case == "bench4096":
         pe, ve, mc, mf = bench_models(A)
     else:
-        mc, mf = models(A, 59 if case == "ins59" else 13)
-    ro, rd = frame_rays(A, n, start=640 * 200 + 100)
+        mc, mf = models(59 if case == "ins59" else 13)
+    ro, rd = frame_rays(n, start=640 * 200 + 100, stride=1)
     rays = torch.stack([ro, rd])
     z = A.H.z_val_sample(n, 4.0, 15.0, 64, device="cuda")
     kw = {}
@@ -139,8 +115,8 @@ def test_fine_entry_equals_dm_nerf(A, case):
 def test_fine_entry_draws_like_dm_nerf(A):
     """perturb > 0 without injected draws: t_rand [N,S] first, then u [N,n_imp], from the device generator -- the same stream
     state gives the same render."""
-    mc, mf = models(A)
-    ro, rd = frame_rays(A, 64, start=90000)
+    mc, mf = models()
+    ro, rd = frame_rays(64, start=90000, stride=1)
     rays = torch.stack([ro, rd])
     z = A.H.z_val_sample(64, 4.0, 15.0, 64, device="cuda")
     args = types.SimpleNamespace(perturb=1.0, N_importance=128, is_train=False, N_ins=None)
@@ -154,8 +130,8 @@ def test_fine_entry_draws_like_dm_nerf(A):
 
 
 def test_fine_entry_refuses_what_it_cannot_serve(A):
-    mc, mf = models(A)
-    ro, rd = frame_rays(A, 8)
+    mc, mf = models()
+    ro, rd = frame_rays(8, stride=1)
     z = A.H.z_val_sample(8, 4.0, 15.0, 64, device="cuda")
     for bad in (dict(mfma_split=True), dict(mfma_split="f16x2"), dict(N_importance=0)):
         args = types.SimpleNamespace(**{**dict(perturb=False, N_importance=128, is_train=False, N_ins=None), **bad})
@@ -195,7 +171,7 @@ def test_frame_renderer_step_on_the_bench_configuration(A):
 @pytest.mark.parametrize("case", ["mfma_split", "f16x2", "generic_6x128", "n_importance_0"])
 def test_fallbacks_still_render_and_equal_dm_nerf(A, case):
     H, W = 9, 13
-    mc, mf = models(A, 13, 6, 128) if case == "generic_6x128" else models(A)
+    mc, mf = models(13, 6, 128) if case == "generic_6x128" else models()
     args = types.SimpleNamespace(perturb=False, N_importance=0 if case == "n_importance_0" else 128, is_train=False, N_ins=None)
     if case == "mfma_split":
         args.mfma_split = True
@@ -218,8 +194,8 @@ def test_fallbacks_still_render_and_equal_dm_nerf(A, case):
 # ---- 6. no allocation, free or synchronisation inside the library
 def test_fine_entry_is_graph_capturable(A):
     N = 256
-    mc, mf = models(A)
-    pick = lambda s: torch.stack(frame_rays(A, N, start=s))
+    mc, mf = models()
+    pick = lambda s: torch.stack(frame_rays(N, start=s, stride=1))
     z = A.H.z_val_sample(N, 4.0, 15.0, 64, device="cuda")
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
     rays = pick(1000)

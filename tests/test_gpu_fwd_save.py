@@ -32,15 +32,15 @@ What the padding columns M .. Mp - 1 hold is unspecified and not looked at.
 
 OBSERVED on an MI355X: see OBSERVED below the imports (the module prints these figures when it finishes).
 """
-import types
 
-import numpy as np
 import pytest
 import torch
 
 import _dgrad_restate as DR
 import _fwd_save_restate as FR
+import _gpu
 import _wgrad_restate as WR
+from _gpu import ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -77,10 +77,7 @@ STATS, ENC_STATS, MODELS = {}, {}, {}
 
 @pytest.fixture(scope="module")
 def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib
-    from dm_nerf_amd.networks import dm_nerf as M
-    yield types.SimpleNamespace(M=M, L=_lib, lib=_lib.load())
+    yield _gpu.namespace()
     MODELS.clear()
     for entry, st in sorted(ENC_STATS.items()):
         print(f"\n[fwd save] encoding {entry:8s}: largest (|got - want| - 1/2 ulp) = {st['over']:.3e} = {st['over'] / ALG_ABS:.2f} x ALG_ABS (the rule allows 4) at {st['where']}; "
@@ -93,14 +90,8 @@ def A():
 def model(A, key, params, ins_num):
     """One DM_NeRF per parameter set, kept on the device (its blobs are packed once)."""
     if key not in MODELS:
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(params)
-        MODELS[key] = m.cuda().train()
+        MODELS[key] = _gpu.model_from(params, ins_num, train=True)
     return MODELS[key]
-
-
-def ulp32(x):
-    return 2.0 ** (np.floor(np.log2(x)) - 23) if x > 0 else 0.0
 
 
 def run(A, m, entry, M, rays=None, x=None):

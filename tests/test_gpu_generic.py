@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu import A, cpu, maxrel  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -20,24 +21,6 @@ SHAPES = [dict(D=6, W=128, multires=6, multires_views=2, ins_num=5),          # 
           dict(D=6, W=64, multires=4, multires_views=1, ins_num=3)]           # two out-blocks, a 9-column direction encoding
 
 
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, config as Cfg, generic as G
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, Cfg=Cfg, G=G, lib=_lib)
-
-
-def cpu(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu()
-
-
-def maxrel(a, b):
-    return float(((a - b).abs() / (1 + b.abs())).max())
-
-
 def test_strided_gemm_three_forms(A):
     """forward  Y = relu(X W^T + b),  data gradient  (dY W) . [H > 0] (+ accumulate),  weight gradient  dY^T X  (split-K) and
     the column sums -- ragged sizes, operands inside wider buffers -- against float64."""
@@ -47,20 +30,20 @@ def test_strided_gemm_three_forms(A):
     Wt = (torch.randn(N, K, generator=g) / K ** 0.5).cuda()
     b = torch.randn(N, generator=g).cuda()
     Y = torch.empty(M_, N + 3, device="cuda")
-    A.G._linear(X, K + 5, Wt, b, A.G._col(Y, 3), N + 3, M_, relu=True)
+    A.Gen._linear(X, K + 5, Wt, b, A.Gen._col(Y, 3), N + 3, M_, relu=True)
     want = torch.relu(X[:, :K].double() @ Wt.double().t() + b.double())
     assert float((Y[:, 3:].double() - want).abs().max()) <= 2e-5
     dY = torch.randn(M_, N, generator=g).cuda()
     H = torch.randn(M_, K, generator=g).cuda()
     dX = torch.full((M_, K), 0.5, device="cuda")
-    A.G._dgrad(dY, N, Wt, K, dX, K, M_, mask=H, ldm=K, accumulate=True)
+    A.Gen._dgrad(dY, N, Wt, K, dX, K, M_, mask=H, ldm=K, accumulate=True)
     want = (dY.double() @ Wt.double() + 0.5) * (H > 0)
     assert float((dX.double() - want).abs().max()) <= 2e-5
-    dW, db = A.G._wgrad(dY, N, N, X, K + 5, K, M_)
+    dW, db = A.Gen._wgrad(dY, N, N, X, K + 5, K, M_)
     want = dY.double().t() @ X[:, :K].double()
     assert float((dW.double() - want).abs().max()) <= 2e-4 * float(want.abs().max())
     assert float((db.double() - dY.double().sum(0)).abs().max()) <= 1e-4
-    assert A.G._splits(N, K, 10 ** 6) > 1
+    assert A.Gen._splits(N, K, 10 ** 6) > 1
 
 
 @pytest.mark.parametrize("M_,K0,K1,N", [(1000, 167, 0, 130), (257, 63, 0, 128), (4097, 320, 63, 320), (300, 192, 27, 96), (129, 96, 0, 18),
@@ -70,7 +53,7 @@ def test_gemm_nt_forward_and_data_gradient_forms(A, M_, K0, K1, N):
     input as two K ranges, output into a column slice of a wider buffer with its pad columns zeroed; the data-gradient form
     (W^T packed transposed, ReLU-derivative mask, accumulate); ragged M, K not a multiple of 32, N of 1 .. 13 out-blocks (two tiles), both epilogue forms (16-byte stores when the row's
     pad allows, dword stores into a 4 + C wide output)."""
-    G = A.G
+    G = A.Gen
     g = torch.Generator().manual_seed(M_ + N)
     x0 = G._Act.empty(M_, K0, "cuda"); x0.buf.copy_(torch.randn(M_, x0.ld, generator=g)); x0.buf[:, K0:] = 0
     x1 = None
@@ -206,7 +189,7 @@ def test_chained_trunk_equals_the_layer_by_layer_trunk_bit_for_bit(A, D, W, mult
     m = A.M.DM_NeRF(D, W, inp, inv, [4], ins_num)
     m.load_state_dict(sd)
     m = m.cuda().eval()
-    assert not m._fused_ok() and bool(A.lib.load().dmnerf_mlp_chain_supported(W, inp))
+    assert not m._fused_ok() and bool(A.lib.dmnerf_mlp_chain_supported(W, inp))
     g = torch.Generator().manual_seed(M_)
     pts = (torch.rand(M_, 3, generator=g) * 2 - 1) * 5.0
     dirs = torch.nn.functional.normalize(torch.randn(M_, 3, generator=g), dim=-1)
@@ -232,7 +215,7 @@ def test_ray_embed_rows_against_the_reference_formulas(A, N, S, Lp, Lv, ldp, ldv
     """dmnerf_ray_embed (csrc/gemm_nt.hip): pts = o + d z (render.py:49), viewdirs = d / |d| (render.py:37), both encodings
     (dm_nerf.py:22-38) as row-padded operands: [x, sin(2^k x), cos(2^k x) ...] per row, pad columns zero, nothing beyond row M - 1."""
     import ctypes
-    lib = A.lib.load()
+    lib = A.lib
     g = torch.Generator().manual_seed(N * 100 + S)
     ro = (torch.rand(N, 3, generator=g) * 2 - 1) * 3.0
     rd = torch.randn(N, 3, generator=g)
@@ -241,8 +224,8 @@ def test_ray_embed_rows_against_the_reference_formulas(A, N, S, Lp, Lv, ldp, ldv
     xp = torch.full((M_ + 3, ldp), 7.0, device="cuda")                   # (three guard rows behind the last sample)
     xv = torch.full((M_ + 3, ldv), 7.0, device="cuda")
     d_ro, d_rd, d_z = ro.cuda(), rd.cuda(), z.cuda().contiguous()
-    A.lib.check(lib.dmnerf_ray_embed(A.lib.ptr(d_ro), A.lib.ptr(d_rd), A.lib.ptr(d_z), N, S, Lp, Lv, A.lib.ptr(xp), ldp,
-                                     A.lib.ptr(xv), ldv, A.lib.stream()), "dmnerf_ray_embed")
+    A.L.check(lib.dmnerf_ray_embed(A.L.ptr(d_ro), A.L.ptr(d_rd), A.L.ptr(d_z), N, S, Lp, Lv, A.L.ptr(xp), ldp,
+                                     A.L.ptr(xv), ldv, A.L.stream()), "dmnerf_ray_embed")
     xp, xv = cpu(xp), cpu(xv)
     pts = (ro[:, None, :] + rd[:, None, :] * z[..., None]).reshape(M_, 3)
     vd = (rd / rd.norm(dim=-1, keepdim=True))[:, None, :].expand(N, S, 3).reshape(M_, 3)
@@ -264,7 +247,7 @@ def test_gemm_tn_weight_and_bias_gradient(A, M_, n_out, n_in):
     """dmnerf_gemm_tn (csrc/gemm_tn.hip): dW = dy^T x and db = column sums of dy over M sample-major rows -- every tile shape class
     (1 x 4, 1 x 8, 4 x 1, 8 x 1, 2 x 2 .. 6 x 6 blocks, several output tiles), ragged last chunk, fewer chunks than slices, a column range of
     a wider dW (the cat inputs' halves), pad columns holding other data; against float64, and bit-reproducible from run to run."""
-    G = A.G
+    G = A.Gen
     g = torch.Generator().manual_seed(M_ + n_out)
     dy, x = G._Act.empty(M_, n_out, "cuda"), G._Act.empty(M_, n_in, "cuda")
     dy.buf.copy_(torch.randn(dy.buf.shape, generator=g))               # (pad columns too: they must not reach dW / db)
@@ -291,7 +274,7 @@ def test_generic_entry_points_reject_what_they_cannot_do(A):
     that is too small, operand rows that are not 16-byte aligned, a width the chained trunk has no room for, a layer whose packed
     weights do not match its inputs, layer 0 reading activations that do not exist yet; M = 0 is not an error (zero gradients)."""
     import ctypes
-    lib, L = A.lib.load(), A.lib
+    lib, L = A.lib, A.L
     dev = "cuda"
     dy, x = torch.randn(64, 32, device=dev), torch.randn(64, 64, device=dev)
     dW, db = torch.full((32, 64), 7.0, device=dev), torch.full((32,), 7.0, device=dev)
@@ -318,7 +301,7 @@ def test_generic_entry_points_reject_what_they_cannot_do(A):
     assert lib.dmnerf_mlp_chain_supported(128, 63) == 1 and lib.dmnerf_mlp_chain_supported(160, 63) == 1
     assert lib.dmnerf_mlp_chain_supported(192, 63) == 0 and lib.dmnerf_mlp_chain_supported(100, 63) == 0 and lib.dmnerf_mlp_chain_supported(128, 0) == 0
     W_, inp = 128, 63
-    G = A.G
+    G = A.Gen
     xp = G._Act.empty(256, inp, dev)
     p0 = G._Packed(torch.randn(W_, inp, device=dev), torch.zeros(W_, device=dev), [(0, inp)])
     p1 = G._Packed(torch.randn(W_, W_, device=dev), torch.zeros(W_, device=dev), [(0, W_)])
@@ -398,7 +381,7 @@ def test_generic_shape_sweep_against_float64(A, cfg, monkeypatch):
     m.load_state_dict(sd)
     m = m.cuda()
     assert not m._fused_ok()
-    lib = A.lib.load()
+    lib = A.lib
     calls = spy_on(lib, monkeypatch, ["dmnerf_mlp_chain"])
     g = torch.Generator().manual_seed(100 + D)
     Mr = 300
@@ -444,7 +427,7 @@ def test_skip_after_the_last_trunk_layer_is_refused_before_any_launch(A, monkeyp
     x = torch.randn(40, inp + inv, device="cuda")
     ro, rd, z = torch.zeros(4, 3, device="cuda"), torch.ones(4, 3, device="cuda"), torch.rand(4, 8, device="cuda")
     torch.cuda.synchronize()
-    lib = A.lib.load()
+    lib = A.lib
     calls = spy_on(lib, monkeypatch, ["dmnerf_copy_cols_pad", "dmnerf_ray_embed", "dmnerf_pack_nt", "dmnerf_gemm_nt", "dmnerf_mlp_chain",
                                       "dmnerf_gemm_tn"])
     with torch.no_grad(), pytest.raises(ValueError, match="skip after the last trunk layer"):
@@ -455,7 +438,7 @@ def test_skip_after_the_last_trunk_layer_is_refused_before_any_launch(A, monkeyp
     with torch.no_grad(), pytest.raises(ValueError, match="skip after the last trunk layer"):
         A.R.run_network(m, ro, rd, z)
     with pytest.raises(ValueError, match="skip after the last trunk layer"):
-        A.G.run_network(m, ro, rd, z, train=True)
+        A.Gen.run_network(m, ro, rd, z, train=True)
     assert all(v == 0 for v in calls.values()), calls
 
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 import _img_metrics_restate as RS
 
 pytestmark = pytest.mark.gpu
@@ -145,13 +146,8 @@ def test_graph_capture_and_replay(E):
 def _driver_setup():
     """The small models and poses of tests/test_gpu_driver.py (synthetic weights 61 / 62, a 9 x 13 frame, two poses)."""
     from dm_nerf_amd import distributed as D
-    from dm_nerf_amd.networks import dm_nerf as M
     from oracle import ref_cpu as O
-    mods = []
-    for seed in (61, 62):
-        m = M.DM_NeRF(8, 256, 63, 27, [4], 13)
-        m.load_state_dict(O.make_weights(seed, 13, W=256, D=8, gain=1.7, sigma_bias=0.3))
-        mods.append(m.cuda().eval())
+    mods = _gpu.models(13)
     H, W = 9, 13
     K = np.array([[20.0, 0, W / 2], [0, -20.0, H / 2], [0, 0, -1]])
     poses = torch.stack([O.pose_spherical(30.0, -65.0, 7.0), O.pose_spherical(80.0, -65.0, 7.0)]).cuda()

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 import _ins_eval_restate as RS
 
 pytestmark = pytest.mark.gpu
@@ -159,14 +160,9 @@ def test_ins_eval_device_graph_replay(E):
 
 def test_render_path_gt_labels_crop(E):
     from dm_nerf_amd import distributed as D
-    from dm_nerf_amd.networks import dm_nerf as M
     from oracle import ref_cpu as O
     ins_num = 13
-    mods = []
-    for seed in (1, 2):
-        m = M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3))
-        mods.append(m.cuda().eval())
+    mods = _gpu.models(ins_num, seeds=(1, 2))
     H, W = 24, 32
     K = O.dmsr_intrinsics(H, W)
     poses = torch.stack([O.pose_spherical(30.0, -65.0, 7.0), O.pose_spherical(90.0, -50.0, 7.0)]).cuda()

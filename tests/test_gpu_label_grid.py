@@ -12,7 +12,6 @@ The labels below ``C - 1`` are, on the small grid, 8 (94 cells), 11 (3), 3 and 1
 thousand times the f32 and f16x2 deviation.  (Seeds 71 and 73, and ``sigma_bias=0.3``, gave sigma > 0 everywhere or one dominant
 label.)  The tests assert both conditions on what the GPU returns."""
 import ctypes
-import types
 
 import numpy as np
 import pytest
@@ -20,6 +19,7 @@ import torch
 
 import _label_grid_restate as LR
 import _skip_restate as RS
+from _gpu import A, model_from  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -29,21 +29,12 @@ LO, HI = (-1.5, -1.2, -1.0), (1.5, 1.3, 2.0)
 GRIDS = ((5, 6, 7), (8, 8, 33))                 # 210 cells: 6 words and 18 bits; 2112 cells = 66 whole words, dz no multiple of 16
 
 
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, editing as Ed, field as F
-    from dm_nerf_amd.networks import dm_nerf as M, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, R=R, F=F, Ed=Ed, lib=_lib)
-
-
 # ---- the kernels on crafted inputs
 def cells_kernel(A, raw, C, thr=0.0):
     raw = torch.from_numpy(np.ascontiguousarray(raw, dtype=np.float32)).cuda()
     M = raw.shape[0]
     out = torch.full((M + 1,), 77, dtype=torch.uint8, device="cuda")          # one guard byte behind the labels
-    A.lib.check(A.lib.load().dmnerf_label_cells(A.lib.ptr(raw), M, C, thr, A.lib.ptr(out), A.lib.stream()), "dmnerf_label_cells")
+    A.L.check(A.lib.dmnerf_label_cells(A.L.ptr(raw), M, C, thr, A.L.ptr(out), A.L.stream()), "dmnerf_label_cells")
     assert int(out[M]) == 77
     return out[:M].cpu()
 
@@ -108,7 +99,7 @@ def stats_kernel(A, labels, C):
     s = torch.full((C + 1, 3), -7, dtype=torch.int64, device="cuda")
     lo = torch.full((C + 1, 3), -7, dtype=torch.int32, device="cuda")
     hi = torch.full((C + 1, 3), -7, dtype=torch.int32, device="cuda")
-    L = A.lib
+    L = A.L
     L.check(L.load().dmnerf_label_stats(L.ptr(lab), *dims, C, L.ptr(count), L.ptr(s), L.ptr(lo), L.ptr(hi), L.stream()), "dmnerf_label_stats")
     for t in (count, s, lo, hi):
         assert bool((t[C] == -7).all())
@@ -158,7 +149,7 @@ def bits_kernel(A, labels, words4):
     n_words = (n + 31) // 32
     bits = torch.full((n_words + 1,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")       # poisoned: every word must be written
     mask = (ctypes.c_uint32 * 4)(*words4)
-    L = A.lib
+    L = A.L
     L.check(L.load().dmnerf_skip_grid_from_labels(L.ptr(lab), n, mask, L.ptr(bits), L.stream()), "dmnerf_skip_grid_from_labels")
     assert int(bits[n_words]) == 0x5A5A5A5A
     return bits[:n_words].cpu().numpy().view(np.uint32)
@@ -188,9 +179,7 @@ _models = {}
 
 def model(A, ins_num):
     if ins_num not in _models:
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(O.make_weights(72, ins_num, gain=1.7, sigma_bias=0.0))
-        _models[ins_num] = m.cuda().eval()
+        _models[ins_num] = model_from(O.make_weights(72, ins_num, gain=1.7, sigma_bias=0.0), ins_num)
     return _models[ins_num]
 
 

@@ -13,20 +13,13 @@ import pytest
 import torch
 
 import _label_trace_restate as T
+from _gpu import A  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 C = T.C_TEST
 KEEP = (1, 4, 9, 13)
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D, editing as Ed, field as F
-    _lib.load()
-    return types.SimpleNamespace(F=F, Ed=Ed, D=D, lib=_lib)
 
 
 def bits(t):
@@ -45,7 +38,7 @@ def assert_same(got, want, what=""):
 def kernel(A, labels, consts, rays, masks, near, far, Cn=C):
     """The raw entry with one guard element behind every output."""
     lo, cell, inv_cell, dims = consts
-    L = A.lib
+    L = A.L
     vol = torch.from_numpy(labels).cuda()
     r = torch.from_numpy(np.ascontiguousarray(rays, dtype=f32)).cuda()
     R, _, N, _ = r.shape
@@ -127,7 +120,7 @@ def test_kernel_equal_t_goes_to_the_lowest_set_and_C_bounds_the_labels(A):
 
 
 def test_entry_validates_its_arguments(A):
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     f3, i3 = (ctypes.c_float * 3)(0, 0, 0), (ctypes.c_int * 3)(4, 4, 4)
     w = (ctypes.c_uint32 * 64)()
     x = torch.zeros(64, dtype=torch.float32, device="cuda")

@@ -22,13 +22,11 @@ def run(reverse):
     """Every entry of PAIRS on both shapes -> {label: output tensor on the CPU}; inputs come from seeded CPU generators."""
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
+    import _gpu                            # after ROOT is on the path: the child process starts without it
     from dm_nerf_amd import _lib as L
-    from dm_nerf_amd.networks import dm_nerf as M
     from oracle import ref_cpu as O
     lib = L.load()
-    model = M.DM_NeRF(8, 256, 63, 27, [4], INS_NUM)
-    model.load_state_dict(O.make_weights(61, INS_NUM, gain=1.7, sigma_bias=0.3))
-    model = model.cuda().eval()
+    model = _gpu.model_from(O.make_weights(61, INS_NUM, gain=1.7, sigma_bias=0.3), INS_NUM)
     blob, blob_hd = model.blob(), model.blob_f16_density()
     out = {}
 

@@ -8,27 +8,16 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
+from _gpu import A  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
 INS = 13
 
 
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D, losses as L
-    from dm_nerf_amd.networks import dm_nerf as M, evaluator as E, helpers as H, penalizer as P, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, D=D, E=E, P=P, L=L)
-
-
 def _scene(A, N, ins_num=INS):
-    models = []
-    for seed in (91, 92):
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3))
-        models.append(m.cuda().train())
+    models = _gpu.models(ins_num, seeds=(91, 92), train=True)
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(40.0, -65.0, 7.0))
     sel = torch.from_numpy(np.random.RandomState(4).choice(480 * 640, N, replace=False))
@@ -76,7 +65,7 @@ def test_fused_tail_equals_the_drop_in_losses(A, penalize, n_ins, ins_num, ref_p
         terms_ref += t
     grads_ref = torch.autograd.grad(loss_ref, leaves if penalize else leaves[:4], retain_graph=True)
 
-    total, terms = A.L.train_losses(out, rays[1], target, labels, ins_num, args,
+    total, terms = A.Lo.train_losses(out, rays[1], target, labels, ins_num, args,
                                     rgb_ins=(out['rgb_fine'], out['rgb_coarse'], cut(out['ins_fine']), cut(out['ins_coarse'])))
     grads = torch.autograd.grad(total, leaves if penalize else leaves[:4], retain_graph=True)
     assert terms.shape == (6,) and not terms.requires_grad and total.requires_grad
@@ -107,12 +96,12 @@ def test_fused_tail_reports_label_conditions_like_the_criterion(A):
     bad = torch.randint(0, 5, (N,), generator=g)
     bad[7] = INS + 3                                            # outside [0, ins_num]: the reference's one_hot would raise
     with pytest.raises(ValueError, match="outside"):
-        A.L.train_losses(out, rays[1], target, bad.cuda(), INS, args, check=True)
-    total, _ = A.L.train_losses(out, rays[1], target, bad.cuda(), INS, args)       # default: no sync, no raise
+        A.Lo.train_losses(out, rays[1], target, bad.cuda(), INS, args, check=True)
+    total, _ = A.Lo.train_losses(out, rays[1], target, bad.cuda(), INS, args)       # default: no sync, no raise
     assert torch.isfinite(total)
     many = torch.arange(N) % (INS + 1)                          # 14 distinct labels for 13 channels
     with pytest.raises(ValueError, match="distinct labels"):
-        A.L.train_losses(out, rays[1], target, many.cuda(), INS, args, check=True)
+        A.Lo.train_losses(out, rays[1], target, many.cuda(), INS, args, check=True)
 
 
 def test_step_with_the_fused_tail_equals_the_step_without(A, monkeypatch):

@@ -17,6 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _gpu
 import _lpips_restate as RS
 
 pytestmark = pytest.mark.gpu
@@ -170,13 +171,8 @@ def test_independence_and_determinism(model):
 def _driver_setup():
     """The small models of tests/test_gpu_img_metrics.py's driver test, a 17 x 19 frame, two poses."""
     from dm_nerf_amd import distributed as D
-    from dm_nerf_amd.networks import dm_nerf as M
     from oracle import ref_cpu as O
-    mods = []
-    for seed in (61, 62):
-        m = M.DM_NeRF(8, 256, 63, 27, [4], 13)
-        m.load_state_dict(O.make_weights(seed, 13, W=256, D=8, gain=1.7, sigma_bias=0.3))
-        mods.append(m.cuda().eval())
+    mods = _gpu.models(13)
     H, W = 17, 19
     K = np.array([[20.0, 0, W / 2], [0, -20.0, H / 2], [0, 0, -1]])
     poses = torch.stack([O.pose_spherical(30.0, -65.0, 7.0), O.pose_spherical(80.0, -65.0, 7.0)]).cuda()
@@ -216,14 +212,9 @@ def test_render_path_plumbing(model):
 
 def test_manipulate_eval_path_plumbing(model):
     from dm_nerf_amd import distributed as D, editing as ED
-    from dm_nerf_amd.networks import dm_nerf as M
     from oracle import ref_cpu as O
     H, W, INS = 16, 18, 7
-    mods = []
-    for seed in (721, 722):
-        m = M.DM_NeRF(8, 256, 63, 27, [4], INS)
-        m.load_state_dict(O.make_weights(seed, INS, gain=1.7, sigma_bias=0.3))
-        mods.append(m.cuda().eval())
+    mods = _gpu.models(INS, seeds=(721, 722))
     K = O.dmsr_intrinsics(H, W)
     poses = [O.pose_spherical(75.0, -65.0, 7.0), O.pose_spherical(60.0, -60.0, 7.0)]
     trans = torch.tensor([[1., 0., 0., 0.3], [0., 1., 0., -0.2], [0., 0., 1., 0.1], [0., 0., 0., 1.]])

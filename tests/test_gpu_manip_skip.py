@@ -12,8 +12,10 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 import _manip_skip_restate as MR
 import _skip_restate as RS
+from _gpu import A  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -23,28 +25,13 @@ N, NS, NI = 130, 8, 8                   # rays (no multiple of a wave or of a 32
 DIMS = (9, 11, 10)                      # 990 cells: 30 full words and 30 bits of the last one
 
 
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D, editing as Ed, field as F
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, manipulator as MA, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, D=D, F=F, MA=MA, Ed=Ed, lib=_lib)
-
-
 _models = {}
 
 
-def models(A, ins_num=13, power=False):
+def models(ins_num=13, power=False):
     key = (ins_num, power)
     if key not in _models:
-        sds = MR.power_weights(O) if power else [O.make_weights(s, ins_num, gain=1.7, sigma_bias=0.3) for s in (61, 62)]
-        out = []
-        for sd in sds:
-            m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-            m.load_state_dict(sd)
-            out.append(m.cuda().eval())
-        _models[key] = out
+        _models[key] = _gpu.models(ins_num, state_dicts=MR.power_weights(O) if power else None)
     return _models[key]
 
 
@@ -107,7 +94,7 @@ def assert_same(got, want, what=""):
 # ---- 1. the select-and-fill kernel against the restatement
 def select_fill(A, grid, ro, rd, z, width, rows=True, totals=None):
     n, s = z.shape
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     flag = torch.full((n, s), 77, dtype=torch.uint8, device="cuda")
     sel = torch.full((n * s,), POISON, dtype=torch.int32, device="cuda")
     count = torch.full((2,), POISON, dtype=torch.int32, device="cuda")
@@ -127,7 +114,7 @@ def select_fill(A, grid, ro, rd, z, width, rows=True, totals=None):
 
 def select_plain(A, grid, ro, rd, z):
     n, s = z.shape
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     flag = torch.full((n, s), 77, dtype=torch.uint8, device="cuda")
     sel = torch.full((n * s,), POISON, dtype=torch.int32, device="cuda")
     count = torch.full((2,), POISON, dtype=torch.int32, device="cuda")
@@ -185,16 +172,16 @@ def test_select_fill_equals_the_restatement(A, n, s, outside):
 
 
 def test_select_fill_refuses_2_31_samples_without_a_launch(A):
-    lib = A.lib.load()
+    lib = A.lib
     g = A.F.SkipGrid.empty((0, 0, 0), (1, 1, 1), 2).c_struct()
     rc = lib.dmnerf_skip_select_fill(ctypes.byref(g), None, None, None, 1 << 20, 1 << 11, None, None, None, None, None, None, 18, None, None)
-    assert rc == -1 and "int32" in A.lib.last_error()
+    assert rc == -1 and "int32" in A.L.last_error()
     rc = lib.dmnerf_skip_select_fill(ctypes.byref(g), None, None, None, 4, 0, None, None, None, None, None, None, 18, None, None)
     assert rc == -1
     rc = lib.dmnerf_skip_select_fill(ctypes.byref(g), None, None, None, 4, 4, None, None, None, None, None, None, 18, None, None)
-    assert rc == -1 and "null" in A.lib.last_error()
+    assert rc == -1 and "null" in A.L.last_error()
     with pytest.raises(ValueError, match="int32"):
-        mc, _ = models(A)
+        mc, _ = models()
         z = torch.zeros(1, 1, device="cuda").expand(1 << 20, 1 << 11)                  # (a view: no 8 GiB of depths)
         A.R.run_network_skip(mc, torch.zeros(1 << 20, 3, device="cuda"), torch.zeros(1 << 20, 3, device="cuda"), z,
                              A.F.SkipGrid.empty((0, 0, 0), (1, 1, 1), 2))
@@ -203,7 +190,7 @@ def test_select_fill_refuses_2_31_samples_without_a_launch(A):
 # ---- 2. a full grid is the dense call
 @pytest.mark.parametrize("name", CONFIGS)
 def test_full_grid_equals_the_dense_manipulator(A, name):
-    mc, mf = models(A)
+    mc, mf = models()
     a = make_args([])
     grid = A.F.SkipGrid.full(MR.BOX_LO, MR.BOX_HI, DIMS)
     counts = torch.zeros(2, dtype=torch.int64, device="cuda")
@@ -219,7 +206,7 @@ def test_full_grid_equals_the_dense_manipulator(A, name):
 @pytest.mark.parametrize("levels", [("coarse", "fine"), ("fine",)])
 @pytest.mark.parametrize("name", CONFIGS)
 def test_random_grid_equals_the_restated_chain(A, name, levels, outside):
-    mc, mf = models(A)
+    mc, mf = models()
     a = make_args([])
     spec = MR.random_spec(DIMS, 0.3, 21, outside)
     counts = torch.zeros(2, dtype=torch.int64, device="cuda")
@@ -240,7 +227,7 @@ def test_a_skipped_sample_is_never_the_moved_object(A):
     ``manipulator``: there the two variants differ by more than 1e-3 on 96 of the 130 rays
     (tests/test_manip_skip_restate.py::test_the_power_case_tells_empty_rows_from_zero_rows_on_the_oracle)."""
     P = MR.POWER
-    mc, mf = models(A, P["ins_num"], power=True)
+    mc, mf = models(P["ins_num"], power=True)
     a = make_args([P["label"]])
     spec = MR.random_spec(P["dims"], P["frac"], P["grid_seed"], P["outside"])
     ori, tars, us = rays_and_draws(1)
@@ -258,7 +245,7 @@ def test_a_skipped_sample_is_never_the_moved_object(A):
 # ---- 5. an empty grid
 @pytest.mark.parametrize("name", ["ref_T1", "ref_T2", "move_copy"])
 def test_empty_grid_evaluates_nothing(A, name):
-    mc, mf = models(A)
+    mc, mf = models()
     a = make_args([])
     spec = MR.GridSpec(np.zeros(DIMS, bool), MR.BOX_LO, MR.BOX_HI, "empty")
     grid = product_grid(A, spec)
@@ -285,7 +272,7 @@ def test_empty_grid_evaluates_nothing(A, name):
 
 # ---- 6. f16x2
 def test_f16x2_full_and_random_grid(A):
-    mc, mf = models(A)
+    mc, mf = models()
     a = make_args([], split="f16x2")
     for name in ("ref_T1", "move_copy"):
         want = run_product(A, mc, mf, name, a)
@@ -302,7 +289,7 @@ def test_f16x2_full_and_random_grid(A):
 
 # ---- 7. refusals
 def test_refusals(A):
-    mc, mf = models(A)
+    mc, mf = models()
     grid = A.F.SkipGrid.full(MR.BOX_LO, MR.BOX_HI, DIMS)
     with pytest.raises(ValueError, match="bf16x3"):
         run_product(A, mc, mf, "ref_T1", make_args([], split="bf16x3"), skip=grid)
@@ -347,7 +334,7 @@ def frame_scene():
 
 
 def test_frame_with_skip_equals_the_per_chunk_restatement(A):
-    mc, mf = models(A)
+    mc, mf = models()
     K, pose, trans = frame_scene()
     a = make_args([2], chunk=CHUNK)
     spec = MR.random_spec(DIMS, 0.3, 25, "evaluate")
@@ -425,7 +412,7 @@ def test_frame_with_skip_equals_the_per_chunk_restatement(A):
 
 def test_path_drivers_hand_the_grid_on(A):
     """``manipulate_eval_path`` / ``manipulate_demo_path`` with ``skip=``: the frames are ``manipulate_frame(skip=)``'s."""
-    mc, mf = models(A)
+    mc, mf = models()
     K, pose, trans = frame_scene()
     a = make_args([2], chunk=CHUNK)
     a.target_label = 2

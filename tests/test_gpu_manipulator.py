@@ -7,21 +7,10 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu import A, cpu, model_from  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available()
-    from dm_nerf_amd.networks import dm_nerf as M, manipulator as MA
-    return types.SimpleNamespace(M=M, MA=MA)
-
-
-def cpu(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu()
 
 
 def test_exchanger_golden_exact(A, golden):
@@ -60,9 +49,7 @@ def test_manipulator_render_z_and_sort(A, golden):
 
 
 def _mk(A, seed, ins_num, **kw):
-    m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-    m.load_state_dict(O.make_weights(int(seed), ins_num, **kw))
-    return m.cuda().eval()
+    return model_from(O.make_weights(int(seed), ins_num, **kw), ins_num)
 
 
 def test_manipulator_stage_by_stage_on_reference_intermediates(A, golden, capsys):

@@ -17,6 +17,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import _gpu
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -26,10 +27,7 @@ CHUNK_R = 160
 
 
 def _mk(seed):
-    from dm_nerf_amd.networks import dm_nerf as M
-    m = M.DM_NeRF(8, 256, 63, 27, [4], INS)
-    m.load_state_dict(O.make_weights(seed, INS, **O.PEAKY))
-    return m.cuda().eval()
+    return _gpu.model_from(O.make_weights(seed, INS, **O.PEAKY), INS)
 
 
 def _scene():
@@ -178,16 +176,11 @@ def test_against_the_reference_manipulator_eval_run(golden, capsys):
     five evaluations when the tolerance is measured without it) and power (it rejects a frame with 20 % or 2 % of its pixels
     mis-routed) are shown on the CPU: tests/test_manip_conditioning.py."""
     from dm_nerf_amd import distributed as D
-    from dm_nerf_amd.networks import dm_nerf as M
     from oracle import manip_margins as MM
     g = golden("manipulator_frame")
     H_, W_, N_test = [int(v) for v in g["HWN"]]
     ins_num, label = int(g["ins_num"]), int(g["label"])
-    models = []
-    for seed in g["seeds"]:
-        m = M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(O.make_weights(int(seed), ins_num, **O.PEAKY))
-        models.append(m.cuda().eval())
+    models = [_gpu.model_from(O.make_weights(int(seed), ins_num, **O.PEAKY), ins_num) for seed in g["seeds"]]
     n_chunks = -(-H_ * W_ // N_test)
     us = [[g[f"u{c}_{i}"].cuda() for i in range(3)] for c in range(n_chunks)]
     k = [0]

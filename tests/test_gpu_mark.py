@@ -2,7 +2,7 @@
 ``field.SkipGrid.mark`` / ``.dilated`` / ``|`` / ``.from_views``, ``render.dm_nerf_fine_mark`` and the ``mark=`` route of the frame
 drivers.  The kernels are compared with the numpy restatement (tests/_mark_restate.py, checked on the CPU by
 tests/test_mark_restate.py), the renders with the existing dense and skipping product calls.  Bits and rendered values are compared
-exactly: there is no tolerance anywhere.  ``models``, ``frame_rays`` and ``random_grid`` restate the helpers of test_gpu_skip.py."""
+exactly: there is no tolerance anywhere.  ``frame_rays``, ``random_grid`` and ``words_of`` are the shared ones of tests/_gpu.py."""
 import ctypes
 import types
 
@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 import _mark_restate as RM
-import _skip_restate as RS
+from _gpu import A, frame_rays, random_grid, words_of  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -26,43 +27,11 @@ SCENE = ((-12.0, -12.0, -12.0), (12.0, 12.0, 12.0), (32, 32, 32))         # hold
 KEYS = ("rgb_fine", "ins_fine", "depth_fine", "z_vals_fine", "raw_fine")
 
 
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D, field as F
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, D=D, F=F, lib=_lib)
-
-
 _cache = {}
 
 
-def models(A, ins_num=13):
-    if ins_num not in _cache:
-        out = []
-        for seed in (61, 62):
-            m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-            m.load_state_dict(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=SIGMA_BIAS))
-            out.append(m.cuda().eval())
-        _cache[ins_num] = out
-    return _cache[ins_num]
-
-
-def frame_rays(n, start=0):
-    K = O.dmsr_intrinsics(480, 640)
-    ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(30.0, -65.0, 7.0))
-    ro, rd = ro.reshape(-1, 3)[start:start + n * 97:97], rd.reshape(-1, 3)[start:start + n * 97:97]
-    return ro.contiguous().cuda(), rd.contiguous().cuda()
-
-
-def words_of(grid):
-    return grid.bits.cpu().numpy().view(np.uint32)
-
-
-def random_grid(A, dims, lo, hi, frac, seed, outside="evaluate"):
-    occ = np.random.RandomState(seed).rand(*dims) < frac
-    return A.F.SkipGrid.from_bits(RS.pack_bits(occ), lo, hi, dims, outside=outside)
+def models(ins_num=13):
+    return _gpu.models(ins_num, sigma_bias=SIGMA_BIAS, cache=_cache)
 
 
 def restate_mark(grid, words, ro, rd, z, w, thr):
@@ -72,7 +41,7 @@ def restate_mark(grid, words, ro, rd, z, w, thr):
 def select_flags(A, grid, ro, rd, z):
     """``dmnerf_skip_select`` (pinned against its restatement by test_gpu_skip.py) -> flag [N,S] bool."""
     N, S = z.shape
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     flag = torch.full((N, S), 77, dtype=torch.uint8, device="cuda")
     sel = torch.empty(N * S, dtype=torch.int32, device="cuda")
     count = torch.empty(1, dtype=torch.int32, device="cuda")
@@ -112,7 +81,7 @@ def test_mark_equals_the_restatement(A, n, s, dims):
     lo, hi = (-1.0, -2.0, 0.0), (1.0, 2.0, 3.0)
     cells = dims[0] * dims[1] * dims[2]
     for tau in (0.0, 1e-3):
-        pre = random_grid(A, dims, lo, hi, 0.1, seed=n + s)
+        pre = random_grid(dims, lo, hi, 0.1, seed=n + s)
         before = words_of(pre).copy()
         o, d, z, w = mark_inputs(n, s, lo, hi, tau, seed=n * s + dims[0])
         want = RM.mark(before, o, d, z, w, lo, hi, dims, tau)
@@ -135,8 +104,8 @@ def test_mark_equals_the_restatement(A, n, s, dims):
 
 
 def test_mark_argument_checks(A):
-    L, lib = A.lib, A.lib.load()
-    grid = random_grid(A, (5, 7, 9), (0, 0, 0), (1, 1, 1), 0.1, seed=1)
+    L, lib = A.L, A.lib
+    grid = random_grid((5, 7, 9), (0, 0, 0), (1, 1, 1), 0.1, seed=1)
     before = grid.bits.clone()
     ro, rd = torch.zeros(4, 3, device="cuda") + 0.5, torch.zeros(4, 3, device="cuda")
     z, w = torch.zeros(4, 8, device="cuda"), torch.ones(4, 8, device="cuda")
@@ -186,7 +155,7 @@ def test_dilated_equals_the_build_with_that_dilation(A, dims):
         assert got.outside == "empty" and got.dims == base.dims and got.bits.data_ptr() != base.bits.data_ptr()
     assert torch.equal(base.bits, keep)
     assert 0 < float(base.occupancy()) < 0.1 < float(base.dilated(1).occupancy()) < 1.0
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     out = torch.zeros_like(base.bits)
     assert lib.dmnerf_skip_grid_dilate(L.ptr(base.bits), *dims, 1, L.ptr(base.bits), L.stream()) == -1 and "different buffers" in L.last_error()
     assert lib.dmnerf_skip_grid_dilate(L.ptr(base.bits), *dims, 5, L.ptr(out), L.stream()) == -1 and "0..4" in L.last_error()
@@ -198,7 +167,7 @@ def test_dilated_equals_the_build_with_that_dilation(A, dims):
 
 def test_or_copy_and_their_refusals(A):
     lo, hi, dims = (0, 0, 0), (1, 1, 1), (5, 7, 9)
-    a, b = random_grid(A, dims, lo, hi, 0.2, seed=3), random_grid(A, dims, lo, hi, 0.2, seed=4)
+    a, b = random_grid(dims, lo, hi, 0.2, seed=3), random_grid(dims, lo, hi, 0.2, seed=4)
     wa, wb = words_of(a).copy(), words_of(b).copy()
     assert np.array_equal(words_of(a | b), wa | wb) and np.array_equal(words_of(a), wa)
     assert np.array_equal(words_of(a | A.F.SkipGrid.empty(lo, hi, dims)), wa)                     # empty is neutral
@@ -207,8 +176,8 @@ def test_or_copy_and_their_refusals(A):
     ptr = c.bits.data_ptr()
     c |= b
     assert c.bits.data_ptr() == ptr and np.array_equal(words_of(c), wa | wb) and np.array_equal(words_of(a), wa)
-    for other in (random_grid(A, (5, 7, 8), lo, hi, 0.2, seed=5), random_grid(A, dims, lo, (1, 1, 2), 0.2, seed=5),
-                  random_grid(A, dims, lo, hi, 0.2, seed=5, outside="empty")):
+    for other in (random_grid((5, 7, 8), lo, hi, 0.2, seed=5), random_grid(dims, lo, (1, 1, 2), 0.2, seed=5),
+                  random_grid(dims, lo, hi, 0.2, seed=5, outside="empty")):
         with pytest.raises(ValueError):
             a | other
         with pytest.raises(ValueError):
@@ -230,7 +199,7 @@ def render_case(A, perturb=False, n=130, split=None):
 def dense_weights(A, mc, ro, rd, z, out, t_rand=None):
     """The two (depths, weights) pairs of a dense render from the existing product calls: the fine one from ``render_train`` of the
     returned ``raw_fine``, the coarse one as ``restate_render`` of test_gpu_skip.py recomputes it (density, ``dmnerf_weights_from_sigma``)."""
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     n, s = z.shape
     w_f = A.R.render_train(out["raw_fine"], out["z_vals_fine"], rd)[1]
     z_c = A.H.stratify(z, t_rand) if t_rand is not None else z
@@ -248,7 +217,7 @@ def marked_case(A, perturb, tau=0.0):
     """The n = 130 case rendered dense and by ``dm_nerf_fine_mark`` at both levels (computed once per (perturb, tau))."""
     key = (perturb, tau)
     if key not in _render_cache:
-        mc, mf = models(A)
+        mc, mf = models()
         ro, rd, z, args, draws = render_case(A, perturb)
         grid = A.F.SkipGrid.empty(*SCENE)
         with torch.no_grad():
@@ -262,7 +231,7 @@ def marked_case(A, perturb, tau=0.0):
 
 @pytest.mark.parametrize("perturb", [False, True])
 def test_marking_render_leaves_the_render_alone_and_marks_what_it_used(A, perturb):
-    mc, mf = models(A)
+    mc, mf = models()
     c = marked_case(A, perturb)
     assert set(c.got) == set(KEYS)
     for k in KEYS:
@@ -294,7 +263,7 @@ def test_skip_render_through_the_marked_grid_equals_the_dense_render(A, case):
     """With ``sigma_bias = 60`` the dense render alone leaves well over a quarter of the samples with weight exactly 0 (asserted
     below on the device's own weights; on the CPU with the oracle: 84 % coarse / 83 % fine, with jitter 84 % / 60 %), so the grid
     leaves samples out and the equality is not vacuous: ``0 < n_eval <= 0.75 N S`` at every level that is skipped."""
-    mc, mf = models(A)
+    mc, mf = models()
     perturb = case == "perturb"
     levels = ("fine",) if case == "fine_only" else ("coarse", "fine")
     if case == "f16x2":
@@ -353,7 +322,7 @@ def test_positive_threshold_leaves_out_only_weights_up_to_it(A):
 
 # ---- 6. the frame drivers
 def frame_setup(A, chunk):
-    mc, mf = models(A)
+    mc, mf = models()
     K = O.dmsr_intrinsics(480, 640)
     c2w = O.pose_spherical(30.0, -65.0, 7.0).cuda()
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None, N_test=chunk, N_samples=64, near=4.0, far=15.0)
@@ -403,7 +372,7 @@ def test_frame_with_mark_is_the_dense_frame_and_marks_every_chunk(A, chunk):
 
 def test_from_views_is_the_or_of_the_single_pose_grids(A):
     H, W = 20, 24
-    mc, mf = models(A)
+    mc, mf = models()
     K = np.array([[30.0, 0, W / 2], [0, -30.0, H / 2], [0, 0, -1]])
     poses = [O.pose_spherical(30.0, -65.0, 7.0).cuda(), O.pose_spherical(75.0, -40.0, 7.0).cuda()]
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None, N_test=100, N_samples=64, near=4.0, far=15.0)
@@ -421,7 +390,7 @@ def test_from_views_is_the_or_of_the_single_pose_grids(A):
 
 # ---- 7. capture
 def test_captured_marking_render_gives_the_eager_words(A):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, _ = render_case(A, n=96)
     rays = torch.stack([ro, rd])
     eager_grid, grid = A.F.SkipGrid.empty(*SCENE), A.F.SkipGrid.empty(*SCENE)

@@ -4,7 +4,6 @@ compared with ``torch.equal``.  (Where a case plants NaN values, a NaN must sit 
 must be equal: ``torch.equal`` itself calls no NaN equal to another.)"""
 import os
 import re
-import types
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import torch
 
 import _object_surface_restate as OS
 import _surface_restate as S
+from _gpu import A  # noqa: F401
 from dm_nerf_amd import editing as E
 from dm_nerf_amd import field as F
 
@@ -25,14 +25,6 @@ def tile():
     src = open(os.path.join(ROOT, "dm_nerf_amd", "csrc", "object_surface.hip")).read()
     m = re.search(r"constexpr int OS_TI = (\d+), OS_TJ = (\d+), OS_TK = (\d+);", src)
     return tuple(int(x) for x in m.groups())
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib
-    _lib.load()
-    return types.SimpleNamespace(lib=_lib)
 
 
 def same(t, a):

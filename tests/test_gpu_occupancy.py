@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu import A, model_from  # noqa: F401
 from dm_nerf_amd import field as F
 from oracle import ref_cpu as O
 
@@ -16,15 +17,6 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "occupancy.npz")
 EXP_ULP2 = 2.4e-7                        # the project's 2-ulp bound for a transcendental with a result in [0, 1]
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, lib=_lib)
 
 
 @pytest.fixture(scope="module")
@@ -39,9 +31,7 @@ _model_cache = {}
 def model(A, ins_num, seed, D=8, W=256, **kw):
     key = (ins_num, seed, D, W, tuple(sorted(kw.items())))
     if key not in _model_cache:
-        m = A.M.DM_NeRF(D, W, 63, 27, [4], ins_num)
-        m.load_state_dict(O.make_weights(seed, ins_num, W=W, D=D, **kw))
-        _model_cache[key] = m.cuda().eval()
+        _model_cache[key] = model_from(O.make_weights(seed, ins_num, W=W, D=D, **kw), ins_num, D, W)
     return _model_cache[key]
 
 
@@ -56,7 +46,7 @@ def random_points(m, seed, radius=15.0):
 
 def rays_density(A, blob, ins_num, ro, rd, z):
     sigma = torch.full(z.shape, float("nan"), dtype=torch.float32, device=z.device)
-    L = A.lib
+    L = A.L
     L.check(L.load().dmnerf_mlp_fwd_rays_density(L.ptr(blob), ins_num, L.ptr(ro), L.ptr(rd), L.ptr(z), z.shape[0], z.shape[1],
                                                  L.ptr(sigma), L.stream()), "dmnerf_mlp_fwd_rays_density")
     return sigma
@@ -224,10 +214,10 @@ def test_arguments_are_validated(A):
     with pytest.raises(ValueError):
         F.query_density(mdl, torch.zeros(4, 3, device="cuda"), voxel=-1.0)
     assert F.query_density(mdl, torch.zeros(0, 3, device="cuda")).shape == (0,)
-    lib = A.lib.load()
+    lib = A.lib
     import ctypes
     s, T = (ctypes.c_float * 3)(), (ctypes.c_float * 12)()
-    assert lib.dmnerf_occupancy_slab(None, 13, None, 8, s, T, 500, 13, None, 0.1, None) == -1 and "leaves" in A.lib.last_error()
+    assert lib.dmnerf_occupancy_slab(None, 13, None, 8, s, T, 500, 13, None, 0.1, None) == -1 and "leaves" in A.L.last_error()
     assert lib.dmnerf_occupancy_slab(None, 13, None, 2000, s, T, 0, 1, None, 0.1, None) == -1
     assert lib.dmnerf_occupancy_slab(None, 13, None, 8, s, T, 512, 0, None, 0.1, None) == 0      # an empty slab at the end
-    assert lib.dmnerf_mlp_fwd_points_density(None, 13, None, 4, None, -1.0, None) == -1 and "null" in A.lib.last_error()
+    assert lib.dmnerf_mlp_fwd_points_density(None, 13, None, 4, None, -1.0, None) == -1 and "null" in A.L.last_error()

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -14,13 +15,7 @@ INS = 13
 
 
 def models(seeds=(61, 62), ins_num=INS):
-    from dm_nerf_amd.networks import dm_nerf as M
-    out = []
-    for seed in seeds:
-        m = M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3))
-        out.append(m.cuda().train())
-    return out
+    return _gpu.models(ins_num, seeds=seeds, train=True)
 
 
 def test_flat_adam_follows_torch_adam_on_identical_gradients(capsys):

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 import _optim_restate as RS
 from oracle import ref_cpu as O
 
@@ -473,13 +474,7 @@ def test_repack_head_product_against_float64(L, packs, capsys, gather):
 
 # ------------------------------------------------------------------------------------------ FlatAdam with other model counts
 def make_models(specs):
-    from dm_nerf_amd.networks import dm_nerf as M
-    out = []
-    for seed, ins in specs:
-        m = M.DM_NeRF(8, 256, 63, 27, [4], ins)
-        m.load_state_dict(O.make_weights(seed, ins, gain=1.7, sigma_bias=0.3))
-        out.append(m.cuda().train())
-    return out
+    return [_gpu.model_from(O.make_weights(seed, ins, gain=1.7, sigma_bias=0.3), ins, train=True) for seed, ins in specs]
 
 
 COUNTS = {"one": ((61, 13),), "three": ((61, 13), (62, 59), (63, 13)), "four": ((61, 13), (62, 59), (63, 13), (64, 13))}

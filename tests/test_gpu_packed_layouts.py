@@ -16,6 +16,7 @@ if __name__ == "__main__":
 import pytest
 import torch
 
+import _gpu
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -30,11 +31,8 @@ IN_EVERY_LAYOUT = "mlps.3.weight"                      # (mlps.0 has no W^T: the
 
 
 def make_model(ins_num, seed=5):
-    from dm_nerf_amd.networks import dm_nerf as M
     assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    m = M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-    m.load_state_dict(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3))
-    return m.cuda().eval()
+    return _gpu.model_from(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
 
 
 def digest(t):

@@ -10,38 +10,14 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu import A, cpu, maxrel, model_from  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    from dm_nerf_amd import config as Cfg
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, Cfg=Cfg, lib=_lib)
-
-
 def dev(t):
     return t.cuda()
-
-
-def cpu(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu()
-
-
-def maxrel(a, b):
-    return float(((a - b).abs() / (1 + b.abs())).max())
-
-
-def model_from(A, sd, ins_num):
-    m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-    m.load_state_dict(sd)
-    return m.cuda().eval()
 
 
 # ------------------------------------------------------------------------------------------
@@ -61,7 +37,7 @@ def test_mlp_embedded_golden(A, golden):
     g = golden("mlp")
     for ins_num in (13, 59, 93):
         sd = O.make_weights(int(g[f"seed_{ins_num}"]), ins_num, gain=float(g["gain"]))
-        m = model_from(A, sd, ins_num)
+        m = model_from(sd, ins_num)
         with torch.no_grad():
             y = cpu(m(dev(g[f"x_{ins_num}"])))
         want = g[f"y_{ins_num}"]
@@ -71,7 +47,7 @@ def test_mlp_embedded_golden(A, golden):
 
 def test_mlp_embedded_vs_oracle_ragged_sizes(A):
     sd = O.make_weights(3, 13, gain=1.7)
-    m = model_from(A, sd, 13)
+    m = model_from(sd, 13)
     g = torch.Generator().manual_seed(3)
     for M_rows in (1, 31, 32, 33, 127, 1000):
         pts = (torch.rand(M_rows, 3, generator=g) * 2 - 1) * 8
@@ -89,7 +65,7 @@ def test_mlp_embedded_vs_oracle_ragged_sizes(A):
 
 def test_blob_refreshes_after_inplace_update(A):
     sd = O.make_weights(4, 13, gain=1.7)
-    m = model_from(A, sd, 13)
+    m = model_from(sd, 13)
     x = torch.randn(64, 90)
     with torch.no_grad():
         y0 = cpu(m(dev(x)))
@@ -226,8 +202,8 @@ def test_dm_nerf_dict_golden(A, golden):
     g = golden("dm_nerf")
     ins_num = int(g["ins_num"])
     kw = dict(gain=float(g["gain"]), sigma_bias=float(g["sigma_bias"]))
-    mc = model_from(A, O.make_weights(int(g["seed_c"]), ins_num, **kw), ins_num)
-    mf = model_from(A, O.make_weights(int(g["seed_f"]), ins_num, **kw), ins_num)
+    mc = model_from(O.make_weights(int(g["seed_c"]), ins_num, **kw), ins_num)
+    mf = model_from(O.make_weights(int(g["seed_f"]), ins_num, **kw), ins_num)
     pe, _ = A.M.get_embedder(10, 0); ve, _ = A.M.get_embedder(4, 0)
     rays = dev(g["rays"])
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
@@ -246,7 +222,7 @@ def test_dm_nerf_vs_oracle_1024_rays(A):
     ins_num = 13
     sd_c = O.make_weights(11, ins_num, gain=1.7, sigma_bias=0.3)
     sd_f = O.make_weights(12, ins_num, gain=1.7, sigma_bias=0.3)
-    mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+    mc, mf = model_from(sd_c, ins_num), model_from(sd_f, ins_num)
     K = O.dmsr_intrinsics(480, 640)
     c2w = O.pose_spherical(20.0, -65.0, 7.0)
     ro, rd = O.get_rays_k(480, 640, K, c2w)
@@ -276,7 +252,7 @@ def test_dm_nerf_vs_oracle_wide_object_heads(A, ins_num):
     stage of the rays kernel): the whole dm_nerf dict against the oracle on 96 rays."""
     sd_c = O.make_weights(100 + ins_num, ins_num, gain=1.7, sigma_bias=0.3)
     sd_f = O.make_weights(200 + ins_num, ins_num, gain=1.7, sigma_bias=0.3)
-    mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+    mc, mf = model_from(sd_c, ins_num), model_from(sd_f, ins_num)
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(75.0, -65.0, 7.0))
     sel = torch.from_numpy(np.random.RandomState(ins_num).choice(480 * 640, 96, replace=False))
@@ -307,7 +283,7 @@ def test_end_to_end_labels_4096_rays(A, ins_num, near, far, capsys):
     import json
     sd_c = O.make_weights(300 + ins_num, ins_num, gain=1.7, sigma_bias=0.3)
     sd_f = O.make_weights(400 + ins_num, ins_num, gain=1.7, sigma_bias=0.3)
-    mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+    mc, mf = model_from(sd_c, ins_num), model_from(sd_f, ins_num)
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(140.0, -65.0, 7.0))
     sel = torch.from_numpy(np.random.RandomState(1000 + ins_num).choice(480 * 640, 4096, replace=False))
@@ -338,8 +314,8 @@ def test_end_to_end_labels_4096_rays(A, ins_num, near, far, capsys):
 def test_full_size_properties(A):
     """BASELINE config 1 size (4096 rays x 64+128) without the oracle: structural invariants."""
     ins_num = 13
-    mc = model_from(A, O.make_weights(21, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
-    mf = model_from(A, O.make_weights(22, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
+    mc = model_from(O.make_weights(21, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
+    mf = model_from(O.make_weights(22, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
     K = O.dmsr_intrinsics(480, 640)
     c2w = O.pose_spherical(20.0, -65.0, 7.0)
     ro, rd = A.H.get_rays_k(480, 640, K, dev(c2w))
@@ -370,8 +346,8 @@ def test_one_call_beyond_2_31_elements_equals_chunked(A):
     behind one base pointer), N is not a multiple of the 32-sample tile -- equals the 4096-ray chunks the drivers use,
     bit for bit: at the start, across the 2^31-element boundary (ray 621 378) and in the ragged tail."""
     ins_num, N = 13, 700001
-    mc = model_from(A, O.make_weights(23, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
-    mf = model_from(A, O.make_weights(24, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
+    mc = model_from(O.make_weights(23, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
+    mf = model_from(O.make_weights(24, ins_num, gain=1.7, sigma_bias=0.3), ins_num)
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = A.H.get_rays_k(480, 640, K, dev(O.pose_spherical(20.0, -65.0, 7.0)))
     idx = torch.arange(N, device="cuda") % (480 * 640)
@@ -406,7 +382,7 @@ def test_create_nerf_and_state_dict_roundtrip(A):
 
 
 def test_errors_are_loud(A):
-    m = model_from(A, O.make_weights(1, 13), 13)
+    m = model_from(O.make_weights(1, 13), 13)
     with pytest.raises(RuntimeError):
         with torch.no_grad():
             m(torch.randn(4, 90))                           # CPU tensor: no fallback
@@ -423,7 +399,7 @@ def test_dm_nerf_with_unusual_sample_counts(A, S, n_imp, N):
     (N_samples / N_importance are config values, config.py:41-43).  Whole dict against the oracle."""
     ins_num = 13
     sd_c, sd_f = O.make_weights(83, ins_num, gain=1.7, sigma_bias=0.3), O.make_weights(84, ins_num, gain=1.7, sigma_bias=0.3)
-    mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+    mc, mf = model_from(sd_c, ins_num), model_from(sd_f, ins_num)
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(15.0, -65.0, 7.0))
     sel = torch.from_numpy(np.random.RandomState(S).choice(480 * 640, N, replace=False))
@@ -450,7 +426,7 @@ def test_empty_and_single_ray_batches(A):
     sample tile; the other lanes compute on clamped duplicates and store nothing)."""
     ins_num = 13
     sd_c, sd_f = O.make_weights(81, ins_num, gain=1.7, sigma_bias=0.3), O.make_weights(82, ins_num, gain=1.7, sigma_bias=0.3)
-    mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+    mc, mf = model_from(sd_c, ins_num), model_from(sd_f, ins_num)
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None)
     with torch.no_grad():
         out = A.R.dm_nerf(torch.zeros(2, 0, 3, device="cuda"), None, None, mc, mf, torch.zeros(0, 64, device="cuda"), args)
@@ -512,17 +488,16 @@ def test_fused_heads_inference_matches_layerwise(A):
     against the layer-by-layer kernel; the 10-key dict of dm_nerf stays within the end-to-end tolerances."""
     for ins_num, seed in ((13, 3), (59, 4)):
         sd = O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3)
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(sd); m = m.cuda()
+        m = model_from(sd, ins_num, train=True)
         g = torch.Generator().manual_seed(seed)
         N, S = 37, 64
         ro, rd = torch.randn(N, 3, generator=g), torch.randn(N, 3, generator=g)
         z = torch.sort(torch.rand(N, S, generator=g) * 5 + 1, -1)[0]
-        lib = A.lib.load()
+        lib = A.lib
         raw_f = torch.empty(N, S, 4 + ins_num + 1, device="cuda")
         ro_d, rd_d, z_d = dev(ro), dev(rd), dev(z)                    # (kept alive across the raw-pointer call)
-        A.lib.check(lib.dmnerf_mlp_fwd_rays_fused(A.lib.ptr(m.blob_fused()), ins_num, A.lib.ptr(ro_d), A.lib.ptr(rd_d), A.lib.ptr(z_d),
-                                                N, S, A.lib.ptr(raw_f), A.lib.stream()), "fused")
+        A.L.check(lib.dmnerf_mlp_fwd_rays_fused(A.L.ptr(m.blob_fused()), ins_num, A.L.ptr(ro_d), A.L.ptr(rd_d), A.L.ptr(z_d),
+                                                N, S, A.L.ptr(raw_f), A.L.stream()), "fused")
         raw_l = A.R.run_network(m, ro_d, rd_d, z_d)
         pts = ro[:, None, :] + rd[:, None, :] * z[:, :, None]
         vd = rd / torch.norm(rd, dim=-1, keepdim=True)
@@ -534,8 +509,7 @@ def test_fused_heads_inference_matches_layerwise(A):
     # through dm_nerf: args.fuse_heads
     ins_num = 13
     sd_c, sd_f = O.make_weights(11, ins_num, gain=1.7, sigma_bias=0.3), O.make_weights(12, ins_num, gain=1.7, sigma_bias=0.3)
-    mc, mf = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num), A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-    mc.load_state_dict(sd_c); mf.load_state_dict(sd_f); mc, mf = mc.cuda(), mf.cuda()
+    mc, mf = model_from(sd_c, ins_num, train=True), model_from(sd_f, ins_num, train=True)
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(30.0, -65.0, 7.0))
     sel = torch.from_numpy(np.random.RandomState(1).choice(480 * 640, 256, replace=False))
@@ -558,17 +532,16 @@ def test_split_bf16_inference_is_f32_class(A, split):
     and 3 logit blocks and ragged batches (incl. one that ends inside a 128-sample workgroup and one of a single sample)."""
     for ins_num, seed, N, S in ((13, 3, 37, 64), (59, 4, 9, 21), (93, 5, 6, 33), (13, 6, 1, 1), (120, 7, 3, 50)):
         sd = O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3)
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-        m.load_state_dict(sd); m = m.cuda()
+        m = model_from(sd, ins_num, train=True)
         g = torch.Generator().manual_seed(seed)
         ro, rd = torch.randn(N, 3, generator=g), torch.randn(N, 3, generator=g)
         z = torch.sort(torch.rand(N, S, generator=g) * 5 + 1, -1)[0]
-        lib = A.lib.load()
+        lib = A.lib
         raw_s = torch.empty(N, S, 4 + ins_num + 1, device="cuda")
         ro_d, rd_d, z_d, blob = dev(ro), dev(rd), dev(z), (m.blob_split() if split == "bf16x3" else m.blob_f16())
         fn = lib.dmnerf_mlp_fwd_rays_split if split == "bf16x3" else lib.dmnerf_mlp_fwd_rays_f16
-        A.lib.check(fn(A.lib.ptr(blob), ins_num, A.lib.ptr(ro_d), A.lib.ptr(rd_d), A.lib.ptr(z_d),
-                                                N, S, A.lib.ptr(raw_s), A.lib.stream()), "split")
+        A.L.check(fn(A.L.ptr(blob), ins_num, A.L.ptr(ro_d), A.L.ptr(rd_d), A.L.ptr(z_d),
+                                                N, S, A.L.ptr(raw_s), A.L.stream()), "split")
         pts = ro[:, None, :] + rd[:, None, :] * z[:, :, None]
         vd = rd / torch.norm(rd, dim=-1, keepdim=True)
         x = torch.cat([O.embed(pts.reshape(-1, 3), 10), O.embed(vd[:, None].expand(pts.shape).reshape(-1, 3), 4)], -1)
@@ -578,8 +551,7 @@ def test_split_bf16_inference_is_f32_class(A, split):
     # through dm_nerf
     ins_num = 13
     sd_c, sd_f = O.make_weights(11, ins_num, gain=1.7, sigma_bias=0.3), O.make_weights(12, ins_num, gain=1.7, sigma_bias=0.3)
-    mc, mf = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num), A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-    mc.load_state_dict(sd_c); mf.load_state_dict(sd_f); mc, mf = mc.cuda(), mf.cuda()
+    mc, mf = model_from(sd_c, ins_num, train=True), model_from(sd_f, ins_num, train=True)
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(30.0, -65.0, 7.0))
     sel = torch.from_numpy(np.random.RandomState(1).choice(480 * 640, 256, replace=False))
@@ -606,7 +578,7 @@ def test_opt_in_inference_modes_full_dict_vs_oracle(A, mode, ins_num, near, far,
     import json
     sd_c = O.make_weights(500 + ins_num, ins_num, gain=1.7, sigma_bias=0.3)
     sd_f = O.make_weights(600 + ins_num, ins_num, gain=1.7, sigma_bias=0.3)
-    mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+    mc, mf = model_from(sd_c, ins_num), model_from(sd_f, ins_num)
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(160.0, -65.0, 7.0))
     sel = torch.from_numpy(np.random.RandomState(2000 + ins_num).choice(480 * 640, 1024, replace=False))

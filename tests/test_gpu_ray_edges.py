@@ -34,12 +34,13 @@ than ATen's (almost always the correctly rounded float); the error of the factor
 now round exp once through double (expf_rn); on the CPU the same arithmetic lands 7.7 ulp away on that ray.
 Also exposed: C = 1 (an object-code map of width 0) was refused by the C entry points as a null pointer; they accept it now.
 """
-import types
 
 import pytest
 import torch
 
+import _gpu
 import _ray_restate as RR
+from _gpu import cpu
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -49,19 +50,10 @@ STATS = {}
 
 @pytest.fixture(scope="module")
 def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, autograd
-    from dm_nerf_amd.networks import helpers as H, manipulator as MN, penalizer as P, render as R
-    _lib.load()
-    yield types.SimpleNamespace(H=H, R=R, P=P, G=autograd, MN=MN, lib=_lib)
+    yield _gpu.namespace()
     for fam, st in STATS.items():
         print(f"\n[ray edges] {fam}: needs {st.get('ratio', 0.0):.2f} x the oracle's error + 8 ulp, largest error {st.get('ulps', 0.0):.2f} ulp of the scale"
               + (f", largest cdf error {st['cdf']:.2e}" if "cdf" in st else ""))
-
-
-def cpu(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu()
 
 
 def stats(family):
@@ -103,7 +95,7 @@ def test_composite_vs_float64(A, S, C, batch):
         if cot == "ins":                                                    # the object-code path is detached from the density
             assert float(g[..., :4].abs().max()) == 0.0, name
     # the weights-only pass on the same density: the compositing weights bit for bit
-    L = A.lib
+    L = A.L
     sigma = raw[..., 3].contiguous()
     w = torch.full((raw.shape[0], S), float("nan"), dtype=torch.float32, device="cuda")
     L.check(L.load().dmnerf_weights_from_sigma(L.ptr(sigma), L.ptr(z), L.ptr(d), raw.shape[0], S, L.ptr(w), L.stream()), "dmnerf_weights_from_sigma")
@@ -222,7 +214,7 @@ def test_importance_resample_ties(A, S, n_imp):
 def test_sort_rows_ties(A, K):
     for N in ((7, 5) if K == 65 else (7,)):
         x = RR.sort_case(K, N)
-        got = cpu(A.MN.sort_rows(x.cuda()))
+        got = cpu(A.MA.sort_rows(x.cuda()))
         want = torch.sort(x, -1).values
         assert got.shape == want.shape and not bool(torch.isnan(got).any()), (K, N)
         assert torch.equal(got, want), (K, N, (got != want).nonzero()[:8].tolist())

@@ -10,20 +10,11 @@ import types
 import pytest
 import torch
 
-from oracle import ref_cpu as O
+from _gpu import A, frame_rays, models  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 N, S, N_IMP = 33, 3, 2
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, lib=_lib)
 
 
 _cache = {}
@@ -32,15 +23,7 @@ _cache = {}
 def case(A, ins_num, perturb):
     """-> (coarse model, fine model, rays_o, rays_d, z, args, draws); the models and rays are made once per ins_num."""
     if ins_num not in _cache:
-        ms = []
-        for seed in (61, 62):
-            m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-            m.load_state_dict(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3))
-            ms.append(m.cuda().eval())
-        K = O.dmsr_intrinsics(480, 640)
-        ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(30.0, -65.0, 7.0))
-        ro, rd = ro.reshape(-1, 3)[90000:90000 + N * 97:97], rd.reshape(-1, 3)[90000:90000 + N * 97:97]
-        _cache[ins_num] = (*ms, ro.contiguous().cuda(), rd.contiguous().cuda(), A.H.z_val_sample(N, 4.0, 15.0, S, device="cuda"))
+        _cache[ins_num] = (*models(ins_num), *frame_rays(N, start=90000), A.H.z_val_sample(N, 4.0, 15.0, S, device="cuda"))
     g = torch.Generator().manual_seed(5)
     t_rand, u = torch.rand(N, S, generator=g).cuda(), torch.rand(N, N_IMP, generator=g).cuda()
     args = types.SimpleNamespace(perturb=1.0 if perturb else False, N_importance=N_IMP, is_train=False, N_ins=None)
@@ -79,7 +62,7 @@ def test_render_rays_fwd_equals_its_stages(A, ins_num, perturb):
 @pytest.mark.parametrize("ins_num,perturb,events", [(i, p, False) for i in (1, 13, 59) for p in (False, True)] + [(13, False, True), (13, True, True)])
 def test_render_rays_fwd_fine_equals_its_stages(A, ins_num, perturb, events):
     mc, mf, ro, rd, z, args, draws = case(A, ins_num, perturb)
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if events else None
     with torch.no_grad():
         z_c = A.H.stratify(z, draws["t_rand"]) if perturb else z

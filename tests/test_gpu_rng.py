@@ -15,29 +15,16 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
+from _gpu import A  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
 N, INS = 160, 13
 
 
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, manipulator as MA, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, D=D, MA=MA)
-
-
 def _models(A, train=False):
-    out = []
-    for seed in (81, 82):
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], INS)
-        m.load_state_dict(O.make_weights(seed, INS, gain=1.7, sigma_bias=0.3))
-        m = m.cuda()
-        out.append(m.train() if train else m.eval())
-    return out
+    return _gpu.models(INS, seeds=(81, 82), train=train)
 
 
 def _rays(start, n=N, theta=50.0):

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu import A  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -28,15 +29,6 @@ NAN, INF = float("nan"), float("inf")
 SHIPPED = (8, 256, 10, 4, 13)
 GENERIC = [(6, 128, 6, 4, 13),                 # 39- and 27-column encodings (rows of 40 / 28 floats before padding)
            (3, 64, 0, 0, 5)]                   # 3-column encodings: one chunk spans the row and seven more
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib
-    from dm_nerf_amd.networks import dm_nerf as M, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, R=R, lib=_lib)
 
 
 def make_model(A, shape, seed):
@@ -105,7 +97,7 @@ def test_embedded_rows_generic_shapes(A, shape, chain, monkeypatch):
     """DM_NeRF.forward on pre-embedded rows through the generic path, with its trunk chained (csrc/gemm_chain.hip) and layer by
     layer (csrc/gemm_nt.hip)."""
     m, sd = make_model(A, shape, 72)
-    assert not m._fused_ok() and bool(A.lib.load().dmnerf_mlp_chain_supported(shape[1], 3 + 6 * shape[2]))
+    assert not m._fused_ok() and bool(A.lib.dmnerf_mlp_chain_supported(shape[1], 3 + 6 * shape[2]))
     run_embedded_poison(A, m, sd, shape, embedded_rows(shape, 6), monkeypatch, chain)
 
 

@@ -11,6 +11,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import _gpu
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -20,12 +21,7 @@ INS, N, N_INS = 13, 131, 70          # 131 rays -> slices of 66 + 65; the last 7
 
 def _two_steps(flat_adam=False):
     from dm_nerf_amd import distributed as D
-    from dm_nerf_amd.networks import dm_nerf as M
-    models = []
-    for seed in (71, 72):
-        m = M.DM_NeRF(8, 256, 63, 27, [4], INS)
-        m.load_state_dict(O.make_weights(seed, INS, gain=1.7, sigma_bias=0.3))
-        models.append(m.cuda().train())
+    models = _gpu.models(INS, seeds=(71, 72), train=True)
     K = O.dmsr_intrinsics(480, 640)
     ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(35.0, -65.0, 7.0))
     sel = torch.from_numpy(np.random.RandomState(9).choice(480 * 640, N, replace=False))

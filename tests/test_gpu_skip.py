@@ -9,57 +9,26 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 import _skip_restate as RS
+from _gpu import A, frame_rays, random_grid, words_of  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
 
 POISON = 0x40000000                    # an int32 far beyond every sample index used here
 
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D, field as F
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, D=D, F=F, lib=_lib)
-
-
 _cache = {}
 
 
-def models(A, ins_num=13):
-    if ins_num not in _cache:
-        out = []
-        for seed in (61, 62):
-            m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-            m.load_state_dict(O.make_weights(seed, ins_num, gain=1.7, sigma_bias=0.3))
-            out.append(m.cuda().eval())
-        _cache[ins_num] = out
-    return _cache[ins_num]
-
-
-def frame_rays(n, start=0):
-    K = O.dmsr_intrinsics(480, 640)
-    ro, rd = O.get_rays_k(480, 640, K, O.pose_spherical(30.0, -65.0, 7.0))
-    ro, rd = ro.reshape(-1, 3)[start:start + n * 97:97], rd.reshape(-1, 3)[start:start + n * 97:97]
-    return ro.contiguous().cuda(), rd.contiguous().cuda()
-
-
-def words_of(grid):
-    return grid.bits.cpu().numpy().view(np.uint32)
-
-
-def random_grid(A, dims, lo, hi, frac, seed, outside="evaluate"):
-    occ = np.random.RandomState(seed).rand(*dims) < frac
-    return A.F.SkipGrid.from_bits(RS.pack_bits(occ), lo, hi, dims, outside=outside)
+def models(ins_num=13):
+    return _gpu.models(ins_num, cache=_cache)
 
 
 def select(A, grid, ro, rd, z):
     """``dmnerf_skip_select`` -> (flag [N,S] uint8, sel int32 [N*S] (valid below count), count int32 [1])."""
     N, S = z.shape
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     flag = torch.full((N, S), 77, dtype=torch.uint8, device="cuda")
     sel = torch.full((N * S,), POISON, dtype=torch.int32, device="cuda")
     count = torch.full((2,), POISON, dtype=torch.int32, device="cuda")
@@ -120,7 +89,7 @@ def select_rays(n, s, seed):
 @pytest.mark.parametrize("n,s", [(1, 1), (3, 5), (7, 64), (130, 192)])
 def test_select_equals_the_restatement(A, n, s, outside):
     dims, lo, hi = (8, 8, 8), (0.0, 0.0, 0.0), (2.0, 2.0, 2.0)
-    grid = random_grid(A, dims, lo, hi, 0.4, seed=11, outside=outside)
+    grid = random_grid(dims, lo, hi, 0.4, seed=11, outside=outside)
     o, d, z = select_rays(n, s, seed=n + s)
     want_flag, want_sel, want_count = RS.select(o, d, z, words_of(grid), lo, hi, dims, outside)
     ro, rd, zz = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda(), torch.from_numpy(z).cuda()
@@ -139,9 +108,9 @@ def test_select_refuses_2_31_samples(A):
     import ctypes
     grid = A.F.SkipGrid.empty((0, 0, 0), (1, 1, 1), 2)
     g = grid.c_struct()
-    rc = A.lib.load().dmnerf_skip_select(ctypes.byref(g), None, None, None, 1 << 20, 1 << 11, None, None, None, None, None)
-    assert rc == -1 and "int32" in A.lib.last_error()
-    assert A.lib.load().dmnerf_skip_select_work_ints(1 << 31) == -1
+    rc = A.lib.dmnerf_skip_select(ctypes.byref(g), None, None, None, 1 << 20, 1 << 11, None, None, None, None, None)
+    assert rc == -1 and "int32" in A.L.last_error()
+    assert A.lib.dmnerf_skip_select_work_ints(1 << 31) == -1
 
 
 # ---- 3. the networks over a selection against their dense twins
@@ -174,10 +143,10 @@ def check_sparse(A, run_sel, dense, M):
 @pytest.mark.parametrize("variant", ["full14", "full60", "fused14", "density"])
 def test_sparse_networks_equal_the_dense_rows(A, variant, n, s):
     ins_num = 59 if variant == "full60" else 13
-    mc, mf = models(A, ins_num)
+    mc, mf = models(ins_num)
     ro, rd = frame_rays(n, start=4000)
     z = (4.0 + 11.0 * torch.rand(n, s, generator=torch.Generator().manual_seed(n * s))).sort(-1).values.cuda()
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     M = n * s
     with torch.no_grad():
         if variant == "density":
@@ -214,7 +183,7 @@ def render_case(A, perturb=False, n=130):
 def restate_render(A, mc, mf, ro, rd, z, args, grid, levels, t_rand=None, u=None):
     """The masked render from the existing dense product calls: dense density, flags applied in torch, weights, resampling, the dense
     full network, rows masked to zero, compositing."""
-    L, lib = A.lib, A.lib.load()
+    L, lib = A.L, A.lib
     n, s = z.shape
     n_imp = args.N_importance
     z_c = A.H.stratify(z, t_rand) if t_rand is not None else z
@@ -238,7 +207,7 @@ def restate_render(A, mc, mf, ro, rd, z, args, grid, levels, t_rand=None, u=None
 
 
 def test_render_with_a_full_grid_equals_dm_nerf_fine(A):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, _ = render_case(A)
     grid = A.F.SkipGrid.full(*BOX)
     with torch.no_grad():
@@ -254,7 +223,7 @@ def test_render_with_an_empty_grid_is_zero(A):
     """Nothing is evaluated: rgb, depth and raw_fine are exactly zero and the pre-sigmoid object sum is exactly zero, so ``ins_fine``
     is exactly sigmoid(0) = 0.5 (the reference applies the sigmoid AFTER the weighted sum, render.py:21-23; an all-zero ``ins_fine``
     cannot come out of the existing compositing)."""
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, _ = render_case(A)
     grid = A.F.SkipGrid.empty(*BOX, outside="empty")
     with torch.no_grad():
@@ -272,10 +241,10 @@ def test_render_with_an_empty_grid_is_zero(A):
 
 @pytest.mark.parametrize("case", ["both", "fine_only", "perturb"])
 def test_render_with_a_random_grid_equals_the_masked_dense_render(A, case):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, draws = render_case(A, perturb=case == "perturb")
     levels = ("fine",) if case == "fine_only" else ("coarse", "fine")
-    grid = random_grid(A, BOX[2], BOX[0], BOX[1], 0.3, seed=21)
+    grid = random_grid(BOX[2], BOX[0], BOX[1], 0.3, seed=21)
     with torch.no_grad():
         want, n_eval = restate_render(A, mc, mf, ro, rd, z, args, grid, levels, **draws)
         got = A.R.dm_nerf_fine_skip(torch.stack([ro, rd]), None, None, mc, mf, z, args, grid, levels=levels, **draws)
@@ -292,11 +261,11 @@ def test_render_with_a_random_grid_equals_the_masked_dense_render(A, case):
 def test_frame_with_skip_equals_the_per_chunk_restatement(A, chunk):
     """24 x 20 = 480 rays: chunk 96 divides them into five whole chunks, chunk 100 leaves a ragged last chunk of 80."""
     H, W = 20, 24
-    mc, mf = models(A)
+    mc, mf = models()
     K = np.array([[30.0, 0, W / 2], [0, -30.0, H / 2], [0, 0, -1]])
     c2w = O.pose_spherical(30.0, -65.0, 7.0).cuda()
     args = types.SimpleNamespace(perturb=False, N_importance=128, is_train=False, N_ins=None, N_test=chunk, N_samples=64, near=4.0, far=15.0)
-    grid = random_grid(A, BOX[2], BOX[0], BOX[1], 0.3, seed=22)
+    grid = random_grid(BOX[2], BOX[0], BOX[1], 0.3, seed=22)
     with torch.no_grad():
         rgb, ins, depth = A.D.render_frame(H, W, K, c2w, (mc, mf), 4.0, 15.0, args, chunk=chunk, n_samples=64, skip=grid)
         ro, rd = A.H.get_rays_k(H, W, K, c2w)
@@ -323,11 +292,11 @@ def test_frame_with_skip_equals_the_per_chunk_restatement(A, chunk):
 
 # ---- 6. capture: no size ever passes through the host
 def test_captured_render_follows_the_grid_overwritten_in_place(A):
-    mc, mf = models(A)
+    mc, mf = models()
     ro, rd, z, args, _ = render_case(A, n=96)
     rays = torch.stack([ro, rd])
-    grid_a = random_grid(A, BOX[2], BOX[0], BOX[1], 0.3, seed=31)
-    grid_b = random_grid(A, BOX[2], BOX[0], BOX[1], 0.7, seed=32)
+    grid_a = random_grid(BOX[2], BOX[0], BOX[1], 0.3, seed=31)
+    grid_b = random_grid(BOX[2], BOX[0], BOX[1], 0.7, seed=32)
     grid = A.F.SkipGrid.from_bits(grid_a.bits.clone(), BOX[0], BOX[1], BOX[2])
     with torch.no_grad():
         eager_a = A.R.dm_nerf_fine_skip(rays, None, None, mc, mf, z, args, grid_a)          # (also the warm-up of every kernel)
@@ -350,7 +319,7 @@ def test_captured_render_follows_the_grid_overwritten_in_place(A):
 
 # ---- 7. the grid from the network
 def test_from_model_equals_from_sigma_of_the_queried_centres(A):
-    _, mf = models(A)
+    _, mf = models()
     lo, hi, dims = (-2.0, -1.0, 0.0), (1.0, 2.0, 1.5), (8, 8, 8)
     with torch.no_grad():
         ref = A.F.SkipGrid.empty(lo, hi, dims)

@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+import _gpu
 import _surface_restate as S
+from _gpu import A  # noqa: F401
 from dm_nerf_amd import field as F
 from oracle import ref_cpu as O
 
@@ -19,15 +21,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 T = 32
 FIXTURE_NAMES = ["9x9x9_s0", "9x9x9_s1", "9x9x9_s2", "17x17x17_s0", "17x17x17_s1", "17x17x17_s2", "33x33x33_s0", "33x33x33_s1",
                  "33x33x33_s2", "9x13x17_s0"]
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib
-    from dm_nerf_amd.networks import dm_nerf as M
-    _lib.load()
-    return types.SimpleNamespace(M=M, lib=_lib)
 
 
 @pytest.fixture(scope="module")
@@ -238,12 +231,9 @@ def test_mesh_scene_end_to_end(A, monkeypatch):
     and gain with ``sigma_bias`` 7.5 and ``sigma_gain`` 10 put sigma in about [4, 11] around the 6.96 that the level corresponds to."""
     with np.load(os.path.join(HERE, "golden", "occupancy.npz")) as z:
         G = {k: z[k] for k in z.files}
-    models = []
-    for seed in (int(G["seed_13"]), int(G["seed_13"]) + 1):
-        m = A.M.DM_NeRF(8, 256, 63, 27, [4], 13)
-        m.load_state_dict(O.make_weights(seed, 13, gain=float(G["gain_13"]), sigma_bias=7.5, sigma_gain=10.0))
-        models.append(m.cuda().eval())
-    models = (models[1], models[0])                                     # (coarse, fine): the fine one has the golden seed
+    models = [_gpu.model_from(O.make_weights(seed, 13, gain=float(G["gain_13"]), sigma_bias=7.5, sigma_gain=10.0), 13)
+              for seed in (int(G["seed_13"]), int(G["seed_13"]) + 1)]
+    models = (models[1], models[0])                                   # (coarse, fine): the fine one has the golden seed
     args = types.SimpleNamespace(perturb=False, N_importance=int(G["n_importance"]), N_samples=64, N_test=4096, near=float(G["near"]),
                                  far=float(G["far"]), is_train=False, N_ins=None)
     rng = np.random.default_rng(9)
@@ -285,7 +275,7 @@ def test_mesh_scene_end_to_end(A, monkeypatch):
 
 # ---- 5. arguments
 def test_arguments_are_validated(A):
-    lib, err = A.lib.load(), A.lib.last_error
+    lib, err = A.lib, A.L.last_error
     assert lib.dmnerf_surface_count(None, 4, 4, 4, 0.45, None, None, None) == -1 and "null" in err()
     assert lib.dmnerf_surface_count(None, 1, 4, 4, 0.45, None, None, None) == -1 and ">= 2" in err()
     assert lib.dmnerf_surface_count(None, 4, 4, 1, 0.45, None, None, None) == -1 and ">= 2" in err()

@@ -10,18 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu import A, model_from  # noqa: F401
 from oracle import ref_cpu as O
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available()
-    from dm_nerf_amd import _lib, autograd
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, G=autograd)
 
 
 def tclose(got, want, what, rel=2e-4):
@@ -31,12 +23,6 @@ def tclose(got, want, what, rel=2e-4):
     scale = float(want.abs().max())
     assert err <= rel * scale + 1e-7, (what, err, scale)
     return err / (scale + 1e-30)
-
-
-def model_from(A, sd, ins_num):
-    m = A.M.DM_NeRF(8, 256, 63, 27, [4], ins_num)
-    m.load_state_dict(sd)
-    return m.cuda().train()
 
 
 def test_composite_backward_vs_autograd(A):
@@ -93,7 +79,7 @@ def test_mlp_backward_vs_autograd(A):
         z = torch.sort(torch.rand(N, S, generator=g) * 5 + 1, -1)[0]
         cot = torch.randn(N, S, 4 + ins_num + 1, generator=g)
         raw_want, want = _oracle_mlp_grads(sd, rays_o, rays_d, z, cot)
-        m = model_from(A, sd, ins_num)
+        m = model_from(sd, ins_num, train=True)
         raw = A.G.run_network_train(m, rays_o.cuda(), rays_d.cuda(), z.cuda())
         tclose(raw, raw_want, "raw (training forward)", rel=1e-5)
         (raw * cot.cuda()).sum().backward()
@@ -109,7 +95,7 @@ def test_mlp_backward_vs_autograd(A):
 def test_ins_branch_gradient_barrier(A):
     """h.detach() (dm_nerf.py:95): an ins-only loss reaches only the three ins layers."""
     sd = O.make_weights(9, 13, gain=1.7)
-    m = model_from(A, sd, 13)
+    m = model_from(sd, 13, train=True)
     g = torch.Generator().manual_seed(9)
     ro, rd = torch.randn(4, 3, generator=g).cuda(), torch.randn(4, 3, generator=g).cuda()
     z = torch.sort(torch.rand(4, 32, generator=g) * 5 + 1, -1)[0].cuda()
@@ -141,7 +127,7 @@ def test_dm_nerf_training_grads_vs_oracle(A, capsys):
     C = ins_num + 1
     cts = [torch.randn(N, 3, generator=g), torch.randn(N, 3, generator=g), torch.randn(N, ins_num, generator=g),
            torch.randn(N, ins_num, generator=g), 0.01 * torch.randn(N, 192, C, generator=g), 0.01 * torch.randn(N, 64, C, generator=g)]
-    mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+    mc, mf = model_from(sd_c, ins_num, train=True), model_from(sd_f, ins_num, train=True)
     args = types.SimpleNamespace(perturb=1.0, N_importance=128, is_train=True, N_ins=None)
     out = A.R.dm_nerf(rays.cuda(), None, None, mc, mf, z.cuda(), args, t_rand=t_rand.cuda(), u=u.cuda())
     assert out['rgb_fine'].requires_grad and out['raw_fine'].requires_grad
@@ -207,7 +193,7 @@ def test_large_training_batch_equals_sum_of_chunks(A):
     args = types.SimpleNamespace(perturb=0.0, N_importance=128, is_train=True, N_ins=None)
 
     def grads(chunks):
-        mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+        mc, mf = model_from(sd_c, ins_num, train=True), model_from(sd_f, ins_num, train=True)
         for s0, n in chunks:
             sl = slice(s0, s0 + n)
             out = A.R.dm_nerf(rays[:, sl].contiguous(), None, None, mc, mf, z[sl].contiguous(), args)
@@ -242,7 +228,7 @@ def test_adam_steps_follow_the_oracle_trajectory(A):
         return ((out['rgb_fine'] - tc) ** 2).mean() + ((out['rgb_coarse'] - tc) ** 2).mean() \
             + ((out['ins_fine'] - ti) ** 2).mean() + ((out['ins_coarse'] - ti) ** 2).mean()
 
-    mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+    mc, mf = model_from(sd_c, ins_num, train=True), model_from(sd_f, ins_num, train=True)
     opt = torch.optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=5e-4, betas=(0.9, 0.999))
     args = types.SimpleNamespace(perturb=0.0, N_importance=128, is_train=True, N_ins=None)
     sdc = {k: v.clone().requires_grad_(True) for k, v in sd_c.items()}
@@ -293,7 +279,7 @@ def test_full_training_recipe_follows_the_oracle(A):
             + O.ins_penalizer(o['raw_fine'], o['z_vals_fine'], o['depth_fine'], rays[1], tol, dw).sum() \
             + O.ins_penalizer(o['raw_coarse'], o['z_vals_coarse'], o['depth_coarse'], rays[1], tol, dw).sum()
 
-    mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+    mc, mf = model_from(sd_c, ins_num, train=True), model_from(sd_f, ins_num, train=True)
     opt = torch.optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=5e-4, betas=(0.9, 0.999))
     args = types.SimpleNamespace(perturb=0.0, N_importance=128, is_train=True, N_ins=None)
     sdc = {k: v.clone().requires_grad_(True) for k, v in sd_c.items()}
@@ -342,7 +328,7 @@ def test_opt_in_fused_heads_training(A, mode):
         z = torch.sort(torch.rand(N, S, generator=g) * 5 + 1, -1)[0]
         cot = torch.randn(N, S, 4 + ins_num + 1, generator=g)
         raw_want, want = _oracle_mlp_grads(sd, rays_o, rays_d, z, cot)
-        m = model_from(A, sd, ins_num)
+        m = model_from(sd, ins_num, train=True)
         raw = A.G.run_network_train(m, rays_o.cuda(), rays_d.cuda(), z.cuda(), fused=mode == "fuse_heads", split=split)
         tclose(raw, raw_want, "raw (fused training forward)", rel=1e-5)
         (raw * cot.cuda()).sum().backward()
@@ -362,7 +348,7 @@ def test_opt_in_fused_heads_training(A, mode):
     target = torch.rand(N, 3, generator=torch.Generator().manual_seed(7)).cuda()
     losses = {}
     for fused in (False, True):
-        mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+        mc, mf = model_from(sd_c, ins_num, train=True), model_from(sd_f, ins_num, train=True)
         opt = torch.optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=5e-4)
         args = types.SimpleNamespace(perturb=0.0, N_importance=128, is_train=True, N_ins=None, **{key: ((val or True) if fused else False)})
         tr = []
@@ -387,7 +373,7 @@ def test_split_dgrad_kernel_vs_f32_dgrad_kernel(A, flavour):
     lib = _lib.load()
     for ins_num, N, S, seed in ((13, 9, 64, 31), (59, 4, 33, 32), (93, 3, 70, 33), (1, 2, 17, 34), (120, 2, 40, 35)):
         sd = O.make_weights(seed, ins_num, gain=1.7)
-        m = model_from(A, sd, ins_num)
+        m = model_from(sd, ins_num, train=True)
         g = torch.Generator().manual_seed(seed)
         rays_o, rays_d = torch.randn(N, 3, generator=g).cuda(), torch.randn(N, 3, generator=g).cuda()
         z = torch.sort(torch.rand(N, S, generator=g) * 5 + 1, -1)[0].cuda()
@@ -451,7 +437,7 @@ def test_split_backward_kernels_vs_oracle_autograd(A, mode, capsys):
             rays_o, rays_d = torch.randn(N, 3, generator=g), torch.randn(N, 3, generator=g)
             z = torch.sort(torch.rand(N, S, generator=g) * 5 + 1, -1)[0]
             cot = torch.randn(N, S, 4 + ins_num + 1, generator=g) * cs
-            m = model_from(A, sd, ins_num)
+            m = model_from(sd, ins_num, train=True)
             M_ = N * S
             Mp = A.G._row_len(M_)
             ro_d, rd_d, z_d = rays_o.cuda(), rays_d.cuda(), z.cuda()          # kept alive: the C ABI takes raw pointers
@@ -467,7 +453,7 @@ def test_split_backward_kernels_vs_oracle_autograd(A, mode, capsys):
                 continue
             # ... and for which the ORACLE's masks are those of the f32 kernels too: the default path meets the tolerance
             raw_want, want = _oracle_mlp_grads(sd, rays_o, rays_d, z, cot)
-            md = model_from(A, sd, ins_num)
+            md = model_from(sd, ins_num, train=True)
             (A.G.run_network_train(md, rays_o.cuda(), rays_d.cuda(), z.cuda()) * cot.cuda()).sum().backward()
             if all(float((p.grad.cpu() - want[k]).abs().max()) <= 2e-4 * float(want[k].abs().max()) + 1e-7 * cs for k, p in md.named_parameters()):
                 break
@@ -496,7 +482,7 @@ def test_split_wgrad_kernel_vs_f32_wgrad_kernel(A):
     lib = _lib.load()
     for ins_num, N, S, seed in ((13, 33, 64, 41), (59, 9, 33, 42), (93, 5, 70, 43), (1, 2, 17, 44), (120, 3, 40, 45)):      # logit blocks 1, 2, 3, 1, 4
         sd = O.make_weights(seed, ins_num, gain=1.7)
-        m = model_from(A, sd, ins_num)
+        m = model_from(sd, ins_num, train=True)
         g = torch.Generator().manual_seed(seed)
         rays_o, rays_d = torch.randn(N, 3, generator=g).cuda(), torch.randn(N, 3, generator=g).cuda()
         z = torch.sort(torch.rand(N, S, generator=g) * 5 + 1, -1)[0].cuda()

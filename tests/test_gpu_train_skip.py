@@ -15,19 +15,11 @@ import pytest
 import torch
 
 import _train_skip_restate as T
+from _gpu import A, model_from  # noqa: F401
 from oracle import ref_cpu as O
-from test_gpu_train import _loss_from, model_from, tclose
+from test_gpu_train import _loss_from, tclose
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available()
-    from dm_nerf_amd import _lib, autograd, field, graphed
-    from dm_nerf_amd.networks import dm_nerf as M, helpers as H, render as R
-    _lib.load()
-    return types.SimpleNamespace(M=M, H=H, R=R, G=autograd, F=field, L=_lib, graphed=graphed)
 
 
 def _grid(A, words, outside):
@@ -57,7 +49,7 @@ def _case(ins_num, S, outside, seed):
 @pytest.mark.parametrize("width", [5, 18, 64])
 @pytest.mark.parametrize("n_sel", [0, 1, 63, 64, 65, 300])
 def test_kernels_alone(A, width, n_sel):
-    lib, L = A.L.load(), A.L
+    lib, L = A.lib, A.L
     N, S = 67, 5                                                      # 335 dense rows: two blocks of 256
     g = torch.Generator().manual_seed(100 * width + n_sel)
     sel = torch.sort(torch.randperm(N * S, generator=g)[:n_sel])[0].to(torch.int32).cuda()
@@ -91,7 +83,7 @@ def test_kernels_alone(A, width, n_sel):
 
 
 def test_entries_refuse_bad_arguments(A):
-    lib, L = A.L.load(), A.L
+    lib, L = A.lib, A.L
     t = torch.zeros(64, 5).cuda()
     s = torch.zeros(64, dtype=torch.int32).cuda()
     assert lib.dmnerf_rows_scatter(L.ptr(t), 2, L.ptr(s), 3, L.ptr(t), 64, 5, L.stream()) == -1 and "padded" in L.last_error()
@@ -110,7 +102,7 @@ def test_entries_refuse_bad_arguments(A):
 @pytest.mark.parametrize("ins_num,S,outside", [(13, 5, "empty"), (13, 5, "evaluate"), (13, 7, "empty"), (13, 7, "evaluate"), (59, 7, "empty")])
 def test_forward_rows(A, split, ins_num, S, outside):
     s, sd, _, _, _ = _case(ins_num, S, outside, 7)
-    m = model_from(A, sd, ins_num)
+    m = model_from(sd, ins_num, train=True)
     o, d, z = _dev(s)
     flag = torch.from_numpy(s["flag"] != 0).cuda()
     dense = A.G.run_network_train(m, o, d, z, split=split).detach()
@@ -136,7 +128,7 @@ def test_backward_vs_float64_referee(A, ins_num, S, outside, capsys):
     o, d, z = _dev(s)
     flag = torch.from_numpy(s["flag"] != 0).cuda()
     G = cot.cuda()
-    m = model_from(A, sd, ins_num)
+    m = model_from(sd, ins_num, train=True)
     raw = A.G.run_network_train_skip(m, o, d, z, _grid(A, s["words"], outside), bucket=64)
     tclose(raw.detach()[flag], raw64[torch.from_numpy(s["flag"] != 0)], "raw (flagged rows)", rel=1e-5)
     (raw * G).sum().backward()                                        # unflagged rows are constants: G there reaches nothing
@@ -145,7 +137,7 @@ def test_backward_vs_float64_referee(A, ins_num, S, outside, capsys):
         assert p.grad is not None, k
         worst[k] = tclose(p.grad, want[k], f"grad {k} (skip, ins={ins_num}, S={S}, {outside})")
     # the sanity pair: the dense Function given G * flag meets the same bound
-    md = model_from(A, sd, ins_num)
+    md = model_from(sd, ins_num, train=True)
     (A.G.run_network_train(md, o, d, z) * (G * flag[..., None])).sum().backward()
     for k, p in md.named_parameters():
         tclose(p.grad, want[k], f"grad {k} (dense, masked cotangent)")
@@ -156,7 +148,7 @@ def test_backward_vs_float64_referee(A, ins_num, S, outside, capsys):
 def test_backward_with_the_empty_grid_gives_zero_gradients(A):
     s, sd, cot, _, _ = _case(13, 5, "empty", 7)
     o, d, z = _dev(s)
-    m = model_from(A, sd, 13)
+    m = model_from(sd, 13, train=True)
     raw = A.G.run_network_train_skip(m, o, d, z, A.F.SkipGrid.empty(T.LO, T.HI, T.DIMS, outside="empty"), bucket=64)
     assert raw.requires_grad                                          # documented: zeros, not None
     (raw * cot.cuda()).sum().backward()
@@ -177,12 +169,12 @@ def test_bucket_edges_and_split(A, K, max_samples, monkeypatch):
     _, want = T.masked_oracle_grads(sd, torch.from_numpy(s["o"]), torch.from_numpy(s["d"]), torch.from_numpy(s["z"]), cot, s["flag"])
     o, d, z = _dev(s)
     flag = torch.from_numpy(s["flag"] != 0).cuda()
-    m = model_from(A, sd, 13)
+    m = model_from(sd, 13, train=True)
     counts = torch.zeros(2, dtype=torch.int64, device="cuda")
     raw = A.G.run_network_train_skip(m, o, d, z, _grid(A, s["words"], "empty"), bucket=64, counts=counts)
     assert counts.tolist() == [K, T.N_RAYS * 5]
     monkeypatch.undo()
-    dense = A.G.run_network_train(model_from(A, sd, 13), o, d, z).detach()
+    dense = A.G.run_network_train(model_from(sd, 13, train=True), o, d, z).detach()
     assert torch.equal(raw.detach()[flag], dense[flag]) and bool((raw.detach()[~flag] == 0).all())
     (raw * cot.cuda()).sum().backward()
     for k, p in m.named_parameters():
@@ -212,7 +204,7 @@ def _dm_nerf_setup(A, ins_num=13):
 def test_dm_nerf_train_through_the_grid(A, split):
     s, sd_c, sd_f, rays, z, t_rand, u, cts, args = _dm_nerf_setup(A)
     args.mfma_split = split or False
-    mc, mf = model_from(A, sd_c, 13), model_from(A, sd_f, 13)
+    mc, mf = model_from(sd_c, 13, train=True), model_from(sd_f, 13, train=True)
     dense = A.G.dm_nerf_train(rays, mc, mf, z, args, t_rand=t_rand, u=u)
     full = A.F.SkipGrid.full(T.LO, T.HI, T.DIMS, outside="evaluate")
     out = A.G.dm_nerf_train(rays, mc, mf, z, args, t_rand=t_rand, u=u, skip=full)
@@ -248,7 +240,7 @@ def test_dm_nerf_train_through_the_grid(A, split):
 # ---- 6. refusals ----------------------------------------------------------------------------------------------------------------
 def test_refusals(A):
     s, sd_c, sd_f, rays, z, t_rand, u, cts, args = _dm_nerf_setup(A)
-    mc, mf = model_from(A, sd_c, 13), model_from(A, sd_f, 13)
+    mc, mf = model_from(sd_c, 13, train=True), model_from(sd_f, 13, train=True)
     grid = _grid(A, s["words"], "evaluate")
     o, d = rays[0], rays[1]
     with pytest.raises(ValueError, match="bf16x3"):
@@ -280,7 +272,7 @@ def test_refusals(A):
 # ---- 7. TrainSkip ---------------------------------------------------------------------------------------------------------------
 def test_train_skip_schedule(A):
     sd = O.make_weights(5, 13, gain=1.7)
-    m = model_from(A, sd, 13)
+    m = model_from(sd, 13, train=True)
     lo, hi = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)
     ts = A.F.TrainSkip(lo, hi, dims=16, every=3, warmup=2, threshold=0.0, dilate=1)
     full = A.F.SkipGrid.full(lo, hi, 16)
@@ -316,7 +308,7 @@ def test_short_run_with_a_full_grid_follows_the_dense_run(A):
     z = A.H.z_val_sample(batch, S.NEAR, S.FAR, 64, device=dev)
 
     def run(skip):
-        mc, mf = model_from(A, sd_c, ins_num), model_from(A, sd_f, ins_num)
+        mc, mf = model_from(sd_c, ins_num, train=True), model_from(sd_f, ins_num, train=True)
         opt = torch.optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=5e-4, betas=(0.9, 0.999))
         args = types.SimpleNamespace(perturb=1.0, N_importance=128, is_train=True, N_ins=None, penalize=True, tolerance=0.05, deta_w=0.05,
                                      train_skip=skip)

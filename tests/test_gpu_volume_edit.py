@@ -2,15 +2,17 @@
 (tests/_volume_edit_restate.py) bit for bit, the argument checks, the direction of the map against the ray-set previews, more edits
 than the baked render takes ray sets, chaining, and graph capture.  Shapes: 7 x 5 x 9 (315 cells: less than two workgroups, a ragged
 last wave), 19 x 17 x 23 (30 workgroups, each flushing its LDS table) and the 16^3 scenes of the CPU tests."""
-import types
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import _baked_restate as B
+import _gpu
 import _label_trace_restate as T
 import _volume_edit_restate as V
+from _gpu import A  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -19,14 +21,6 @@ BOX = ((-1.0, -0.8, -1.2), (1.1, 0.9, 1.3))                        # nothing dya
 BOX16 = ((-8.0, -8.0, -8.0), (8.0, 8.0, 8.0))                      # cell 1.0: whole-cell moves are exact
 DIMS16 = (16, 16, 16)
 CS = 14
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, distributed as D, editing as Ed, field as F
-    _lib.load()
-    return types.SimpleNamespace(F=F, Ed=Ed, D=D, lib=_lib)
 
 
 def make_grid(A, labels, cells, box, C):
@@ -148,8 +142,8 @@ def test_every_refusal_comes_before_the_device(A, monkeypatch):
     out_b.labels.fill_(99)
     out_b.cells.fill_(-3.0)
     launches = []
-    real = A.lib.launch
-    monkeypatch.setattr(A.lib, "launch", lambda *a: (launches.append(a[0]), real(*a))[1])
+    real = A.L.launch
+    monkeypatch.setattr(A.L, "launch", lambda *a: (launches.append(a[0]), real(*a))[1])
     eye = np.eye(4)
     for grid, out in ((plain, out_p), (baked, out_b)):
         bad = [(dict(trans_list=[Ed.Deform("sin")], target_labels=[3]), "image row"),
@@ -204,12 +198,7 @@ OBJECT, STEP = 3, (3, -2, 1)                                       # the object 
 MOVE = V.translation([-3.0, 2.0, -1.0])
 
 
-def frame_rays(A, trans_list, target_labels):
-    """The rays ``preview_frame`` / ``render_preview`` use: ``ManipulationFrameRenderer``'s own."""
-    args = types.SimpleNamespace(N_importance=0, target_labels=list(target_labels))
-    fr = A.D.ManipulationFrameRenderer(H, W, K, torch.from_numpy(POSE), trans_list, None, args, ins_num=CS - 1, rank=0, world=1,
-                                       keep_labels=None if trans_list else ())
-    return torch.cat([fr.ori[None], fr.tar], dim=0) if fr.T else fr.ori[None]
+renderer_rays = functools.partial(_gpu.renderer_rays, camera=(H, W, K, POSE), ins_num=CS - 1)
 
 
 def cell_ijk(g):
@@ -232,7 +221,7 @@ def test_direction_label_volume_against_the_ray_sets(A):
     assert torch.equal(edited.labels.cpu(), torch.from_numpy(want["labels"]))
     others = sorted(set(range(CS)) - {OBJECT})
     # on the host
-    rays = frame_rays(A, [MOVE], [OBJECT]).cpu().numpy()
+    rays = renderer_rays(A, [MOVE], [OBJECT]).cpu().numpy()
     a = T.trace_sets(labels, lo, cell, inv_cell, CS, rays, [T.mask_words(others, CS), T.mask_words([OBJECT], CS)], f32(NEAR), f32(FAR))
     b = T.trace_sets(want["labels"], lo, cell, inv_cell, CS, rays[:1], [T.mask_words(range(CS), CS)], f32(NEAR), f32(FAR))
     shifted = lambda cells, source: np.where((source == 1)[:, None], cell_ijk(cells) + np.asarray(STEP), cell_ijk(cells))
@@ -245,8 +234,8 @@ def test_direction_label_volume_against_the_ray_sets(A):
     pb = A.Ed.preview_frame(edited, H, W, K, POSE, near=NEAR, far=FAR)
     assert torch.equal(pa["label"], pb["label"]) and torch.equal(pa["label"].cpu().reshape(-1), torch.from_numpy(a[0]))
     assert torch.equal(torch.isfinite(pa["depth"]), torch.isfinite(pb["depth"])) and torch.equal(torch.isfinite(pa["depth"]), pa["label"] != 255)
-    ta = grid.trace_sets(frame_rays(A, [MOVE], [OBJECT]), [others, [OBJECT]], NEAR, FAR)
-    tb = edited.trace_sets(frame_rays(A, [], []), [range(CS)], NEAR, FAR)
+    ta = grid.trace_sets(renderer_rays(A, [MOVE], [OBJECT]), [others, [OBJECT]], NEAR, FAR)
+    tb = edited.trace_sets(renderer_rays(A, [], []), [range(CS)], NEAR, FAR)
     dev_hit = (ta["label"] != 255).cpu().numpy()
     assert np.array_equal(dev_hit, hit)
     assert np.array_equal(shifted(ta["cell"].cpu().numpy(), ta["source"].cpu().numpy())[hit], cell_ijk(tb["cell"].cpu().numpy())[hit])
@@ -266,7 +255,7 @@ def test_direction_baked_volume_against_the_ray_sets(A):
     assert_equals_restatement(res, want, True, "move")
     assert not bool(res["hits"].any()) and int(res["claimed"][0]) == int(grid.stats()["count"][OBJECT])
     others = sorted(set(range(CS)) - {OBJECT})
-    rays = frame_rays(A, [MOVE], [OBJECT]).cpu().numpy()
+    rays = renderer_rays(A, [MOVE], [OBJECT]).cpu().numpy()
     a = B.render(labels, cells, lo, cell, inv_cell, CS, rays, [T.mask_words(others, CS), T.mask_words([OBJECT], CS)], NEAR, FAR)
     b = B.render(want["labels"], want["cells"], lo, cell, inv_cell, CS, rays[:1], [T.mask_words(range(CS), CS)], NEAR, FAR)
     assert np.array_equal(a["nseg"], b["nseg"]) and np.array_equal(a["label"], b["label"]) and int(a["nseg"].max()) >= 3
@@ -299,7 +288,7 @@ def test_four_moves_at_once_render_as_one_ray_set(A):
     assert_equals_restatement(res, want, True, "four moves")
     assert (want["claimed"] > 0).all() and not np.array_equal(want["labels"], labels)
     got = A.Ed.render_preview(res["grid"], H, W, K, POSE, near=NEAR, far=FAR)
-    rays = frame_rays(A, [], []).cpu().numpy()
+    rays = renderer_rays(A, [], []).cpu().numpy()
     masks = [T.mask_words(range(CS), CS)]
     seg = B.merge(want["labels"], lo, cell, inv_cell, CS, rays, masks, NEAR, FAR)
     r32 = B.render(want["labels"], want["cells"], lo, cell, inv_cell, CS, rays, masks, NEAR, FAR, seg=seg)

@@ -43,13 +43,14 @@ M = 32 on the same tensors are inside the rule.  Training lifts dy and d raw int
 this kernel sees them (the 2^10 test above); these operands are unscaled on purpose.  That family's factor is twice the observed
 multiple; every other family keeps 4.
 """
-import types
 
 import numpy as np
 import pytest
 import torch
 
+import _gpu
 import _wgrad_restate as WR
+from _gpu import ulp32
 
 pytestmark = pytest.mark.gpu
 
@@ -78,9 +79,7 @@ def family(name):
 
 @pytest.fixture(scope="module")
 def A():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    from dm_nerf_amd import _lib, autograd
-    yield types.SimpleNamespace(G=autograd, L=_lib, lib=_lib.load())
+    yield _gpu.namespace()
     for (kern, fam), st in sorted(STATS.items()):
         print(f"\n[wgrad] {kern:7s} {fam:15s}: needs {st['ratio']:.2f} x the float32 yardstick's error + 8 ulp ({st['where']}); largest error "
               f"{st['ulps']:.1f} ulp of max|want|, yardstick {st['ulps_y']:.1f} ulp; f32 hard bound used to {st.get('bound', 0.0):.3f}")
@@ -148,10 +147,6 @@ def test_f16x2_gradient_scale_is_removed_exactly(A):
     finally:
         dev = scaled = None                                        # the ~120 MB workspaces of the largest case do not pile up
         torch.cuda.empty_cache()
-
-
-def ulp32(x):
-    return 2.0 ** (np.floor(np.log2(x)) - 23) if x > 0 else 0.0
 
 
 @pytest.mark.parametrize("case", WR.CASES, ids=WR.case_id)
